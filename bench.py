@@ -13,6 +13,12 @@ timing.  Rank 0 prints ONE JSON line.  Multi-GPU start-up: local
 other rank parses only their headers and receives the packed weight blobs by RCCL broadcast over xGMI; barriers and
 the max-over-ranks of the timer are RCCL all-reduces on the same communicator.  The 128-byte RCCL unique id travels
 through a node-local file (single-node contract); no framework runtime is loaded beside libq3t.so.
+
+A plain run (`--gpus N --steps K --warmup W`) does what the headline figure needs and nothing else: it loads the
+context, warms up, times the K steps and prints the result line.  `--full` adds every secondary measurement to the
+line: the talker / code-predictor stage replays and their rooflines, the vocoder roofline, the batched (`--batched`)
+and serving (`--serve`) sections and the CPU baseline (`--cpu-baseline`); without it those options are not acted on.
+`--dump-outputs DIR` writes what the last timed step returned to its caller (codes and PCM) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -32,6 +38,7 @@ CP_PASS_BYTES = 5 * 15_728_640 * 2
 CP_HEAD_BYTES = 2048 * 1024 * 2
 HBM_PEAK_GBS = 8000.0              # MI355X_MICROARCH.md chip table (spec)
 MFMA_PEAK_TFLOPS = 2500.0          # dense f16/bf16 MFMA, MI355X_MICROARCH.md (spec; sparsity figures excluded)
+DUMP_LIMIT_BYTES = 64_000_000      # --dump-outputs: all files of one run together
 
 
 def log(*a):
@@ -175,6 +182,23 @@ def release_uid():
         pass
 
 
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays: {name: array}, written as out_dir/<name>.npy in float32 (code ids are below 2^24: exact).  If they
+    exceed `limit` bytes together, every array above its even share of the limit is cut to a fixed sample of its
+    flattened elements (seed 0, ascending indices), the same elements in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float32) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        share = limit // len(arrays)
+        for k, a in arrays.items():
+            if a.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, share // 4, replace=False))
+                arrays[k] = a.ravel()[idx]
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def pmc_traffic(slots):
     """HBM bytes per talker-step replay from the newest committed rocprofv3 FETCH_SIZE pass
     (profiles/rNN_pmc_fetch_talker_step[_b64].txt, tools/dev/gpu.sh fetch; x2 gfx950 correction applied there)."""
@@ -217,7 +241,15 @@ def main():
     ap.add_argument("--serve-slots", type=int, default=256,
                     help="slots of the serving measurement (one context: the batched path is latency-bound at 64 "
                          "slots, 288 GB of HBM holds the KV of 256)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary measurement (stage replays and rooflines, "
+                         "--batched, --serve, --cpu-baseline) and report them in the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (codes [utterance][frame][16], PCM [utterance]"
+                         "[sample]) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -228,8 +260,9 @@ def main():
 
     voc_mode = {"full": q3t.VOCODER_FULL, "chunk40": q3t.VOCODER_CHUNK40, "none": None}[args.vocoder]
     max_ctx = max(args.frames, args.roofline_pos) + 32
-    batched = args.batched
-    serve_slots = args.serve_slots if args.serve > 0 and world == 1 else 0
+    # the context holds the slots of the sections that will run: without --full only the timed workload's
+    batched = args.batched if args.full else 0
+    serve_slots = args.serve_slots if args.full and args.serve > 0 and world == 1 else 0
     slots = max(args.batch, batched, serve_slots)
     weights = "local GGUF read"
     if world > 1:
@@ -255,6 +288,7 @@ def main():
     prompts = [prompt] * B
     spks = [np.zeros(H, np.float32)] * B
     stats = {"prefill_ms": 0.0, "frames_ms": 0.0, "vocoder_ms": 0.0}
+    last = {}   # what the latest step returned to its caller (--dump-outputs)
 
     def step(k, prompts=prompts, spks=spks):
         codes = eng.generate(prompts, speakers=spks, max_len=args.frames, temperature=0.9, top_k=50,
@@ -262,13 +296,15 @@ def main():
         pm, fm = eng.last_timing()
         stats["prefill_ms"] += pm
         stats["frames_ms"] += fm
+        pcm = None
         if voc_mode is not None:
             t = time.perf_counter()
             if len(codes) == 1:
-                eng.vocoder(codes[0], voc_mode)
+                pcm = [eng.vocoder(codes[0], voc_mode)]
             else:   # utterance batches through shared launches (q3t_vocoder_decode_batch)
-                eng.vocoder_batch(codes, voc_mode)
+                pcm = eng.vocoder_batch(codes, voc_mode)
             stats["vocoder_ms"] += (time.perf_counter() - t) * 1e3
+        last["codes"], last["pcm"] = codes, pcm
         return codes
 
     for w in range(args.warmup):
@@ -280,6 +316,34 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     total_frames = world * B * args.frames * args.steps
     value = total_frames / elapsed
+
+    if args.dump_outputs:
+        # every utterance of a step has exactly --frames frames (force_frames); one rank's files carry no suffix
+        sfx = f"_rank{rank}" if world > 1 else ""
+        out = {"codes" + sfx: np.stack(last["codes"])}
+        if last["pcm"] is not None:
+            out["pcm" + sfx] = np.stack(last["pcm"])
+        dump_outputs(args.dump_outputs, out, DUMP_LIMIT_BYTES // world)
+
+    head = {
+        "metric": "audio frames/sec (12 Hz frames) + RTF, Qwen3-TTS-0.6B batch=1 and batch=8xN",
+        "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 2), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f16",
+        "data": "synthetic (random-init 0.6B-shaped weights from tools/q3t_synth.c, 16-token prompt)",
+        "config": {"workload": f"configs[1]: Qwen3-TTS-0.6B {B} utterance(s)/GPU x {args.frames} frames, "
+                               f"talker+code-predictor+vocoder({args.vocoder}) HIP path, temp 0.9 top-k 50",
+                   "utterances_per_gpu": B, "frames": args.frames, "vocoder": args.vocoder,
+                   "parallelism": f"utterance-sharded dp{world}", "weights": weights},
+        "rtf": round(ms_per_step / 1e3 / (args.frames * FRAME_SEC), 5),
+        "x_realtime": round(args.frames * FRAME_SEC * B / (ms_per_step / 1e3), 1),
+        "breakdown_ms_per_step": {k: round(v / args.steps, 2) for k, v in main_stats.items()},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        eng.close()
+        return
 
     # ---- per-stage GPU times for the CPU-baseline ratios: decode loop and vocoder per frame of the timed steps, and
     # BASELINE configs[0] (one 32-frame utterance, prefill + frames + vocoder) end to end, median of 5 wall-clock runs
@@ -406,18 +470,7 @@ def main():
 
     if rank == 0:
         res = {
-            "metric": "audio frames/sec (12 Hz frames) + RTF, Qwen3-TTS-0.6B batch=1 and batch=8xN",
-            "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 2), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f16",
-            "data": "synthetic (random-init 0.6B-shaped weights from tools/q3t_synth.c, 16-token prompt)",
-            "config": {"workload": f"configs[1]: Qwen3-TTS-0.6B {B} utterance(s)/GPU x {args.frames} frames, "
-                                   f"talker+code-predictor+vocoder({args.vocoder}) HIP path, temp 0.9 top-k 50",
-                       "utterances_per_gpu": B, "frames": args.frames, "vocoder": args.vocoder,
-                       "parallelism": f"utterance-sharded dp{world}", "weights": weights},
-            "rtf": round(ms_per_step / 1e3 / (args.frames * FRAME_SEC), 5),
-            "x_realtime": round(args.frames * FRAME_SEC * B / (ms_per_step / 1e3), 1),
-            "breakdown_ms_per_step": {k: round(v / args.steps, 2) for k, v in main_stats.items()},
+            **head,
             "talker_step_ms": round(t_talker, 4), "cp_frame_ms": round(t_cp, 4),
             "roofline": {"bound": "hbm", "kernel": f"talker decode step at KV position {p_mid} (28 layers + codec head + "
                                                   "CB0 selection: ONE persistent launch, " + tk_kernel + ")"

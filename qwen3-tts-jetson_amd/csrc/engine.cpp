@@ -223,9 +223,15 @@ bool Engine::load(const std::string &tts_gguf, const std::string &tok_gguf, int 
         if (n > 0 && n < c_.n_layers) { c_.n_layers = n; L_.resize(n); }
     }
 #endif
-    if (!setup_persist()) return false;
-    if (!setup_cpb()) return false;
-    if (!setup_tkb()) return false;
+    int n_cu = 0;
+    Q3T_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device_));
+    if (!setup_persist(n_cu)) return false;
+    if (!setup_cpb(n_cu)) return false;
+    if (!setup_tkb(n_cu)) return false;
+#ifdef Q3T_DEV
+    // development timeline of whichever persistent launch runs (read back through debug_read 5)
+    if ((persist_ || persist_cp_ || cpb_ || tkb_) && std::getenv("Q3T_PERSIST_PROF")) pprof_ = dalloc<uint64_t>((size_t)PROF_WG * PROF_PH * 4);
+#endif
     if (!tok_gguf.empty()) {
         voc_.reset(new Vocoder());
         if (!voc_->load(tok_gguf, stream_, recv_weights)) return false;
@@ -463,11 +469,32 @@ bool Engine::alloc_state() {
     return true;
 }
 
+// the persistent launches' weight pointer tables, each uploaded once per context: a stack's layers (pl_dev_ / pl_cp_dev_)
+bool Engine::upload_layer_table(const std::vector<DevLayer> &layers, PLayerW *&dev) {
+    if (dev) return true;
+    std::vector<PLayerW> pl(layers.size());
+    for (size_t i = 0; i < layers.size(); ++i)
+        pl[i] = PLayerW{layers[i].qkv, layers[i].o, layers[i].gu, layers[i].down, layers[i].attn_norm, layers[i].ffn_norm, layers[i].qn, layers[i].kn};
+    dev = dalloc<PLayerW>(pl.size());
+    if (!dev) { set_error("device allocation failed"); return false; }
+    Q3T_HIP(hipMemcpyAsync(dev, pl.data(), pl.size() * sizeof(PLayerW), hipMemcpyHostToDevice, stream_));
+    Q3T_HIP(hipStreamSynchronize(stream_));
+    return true;
+}
+// and the code predictor's 15 lm_heads (heads_dev_)
+bool Engine::upload_head_table() {
+    if (heads_dev_) return true;
+    heads_dev_ = dalloc<const uint16_t *>(16);
+    if (!heads_dev_) { set_error("device allocation failed"); return false; }
+    std::vector<const uint16_t *> hp(cp_head_.begin(), cp_head_.end());
+    Q3T_HIP(hipMemcpyAsync(heads_dev_, hp.data(), hp.size() * sizeof(void *), hipMemcpyHostToDevice, stream_));
+    Q3T_HIP(hipStreamSynchronize(stream_));
+    return true;
+}
+
 // the persistent single-slot talker step (persist.hip): layer pointer table + zeroed hand-off state; off when the
 // shapes or the device do not match what the kernel is built for (the launch-per-phase graph is used then)
-bool Engine::setup_persist() {
-    int n_cu = 0;
-    Q3T_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device_));
+bool Engine::setup_persist(int n_cu) {
     const bool use = persist_ && fused_select_;
     persist_ = use && persist_supported(c_.hidden, c_.n_heads, c_.n_kv, c_.head_dim, c_.inter, c_.codec_vocab, max_ctx_, n_cu);
     // the code-predictor frame needs the 0.6B code-predictor shapes only: the 1.7B one (a 2,048-wide talker) runs it
@@ -484,45 +511,22 @@ bool Engine::setup_persist() {
     if (!persist_ && !persist_cp_) return wa_.recv || build_persist_tables();   // (the batched path's table)
     pstate_ = dalloc<uint8_t>(persist_state_bytes());
     if (!pstate_) { set_error("device allocation failed"); return false; }
-    if (persist_) {
-        std::vector<PLayerW> pl(L_.size());
-        for (size_t i = 0; i < L_.size(); ++i)
-            pl[i] = PLayerW{L_[i].qkv, L_[i].o, L_[i].gu, L_[i].down, L_[i].attn_norm, L_[i].ffn_norm, L_[i].qn, L_[i].kn};
-        pl_dev_ = dalloc<PLayerW>(pl.size());
-        if (!pl_dev_) { set_error("device allocation failed"); return false; }
-        Q3T_HIP(hipMemcpyAsync(pl_dev_, pl.data(), pl.size() * sizeof(PLayerW), hipMemcpyHostToDevice, stream_));
-        Q3T_HIP(hipStreamSynchronize(stream_));
-    }
+    if (persist_ && !upload_layer_table(L_, pl_dev_)) return false;
     // the code-predictor frame (persist_cp_frame): its 5 layers and 15 lm_heads
     if (persist_cp_) {
-        std::vector<PLayerW> cpl(CP_.size());
-        for (size_t i = 0; i < CP_.size(); ++i)
-            cpl[i] = PLayerW{CP_[i].qkv, CP_[i].o, CP_[i].gu, CP_[i].down, CP_[i].attn_norm, CP_[i].ffn_norm, CP_[i].qn, CP_[i].kn};
-        pl_cp_dev_ = dalloc<PLayerW>(cpl.size());
-        heads_dev_ = dalloc<const uint16_t *>(16);
-        if (!pl_cp_dev_ || !heads_dev_) { set_error("device allocation failed"); return false; }
-        Q3T_HIP(hipMemcpyAsync(pl_cp_dev_, cpl.data(), cpl.size() * sizeof(PLayerW), hipMemcpyHostToDevice, stream_));
-        Q3T_HIP(hipStreamSynchronize(stream_));
-        std::vector<const uint16_t *> hp(cp_head_.begin(), cp_head_.end());
-        Q3T_HIP(hipMemcpyAsync(heads_dev_, hp.data(), hp.size() * sizeof(void *), hipMemcpyHostToDevice, stream_));
-        Q3T_HIP(hipStreamSynchronize(stream_));
+        if (!upload_layer_table(CP_, pl_cp_dev_) || !upload_head_table()) return false;
         // the per-token tables are computed from the weights: a receiving context (replica, non-root rank) builds
         // them once its arena has been filled (finish_weights, after copy_weights_from / the RCCL broadcast)
         if (!wa_.recv && !build_persist_tables()) return false;
     }
     // (pstate_ was zeroed on the context stream by dalloc)
-#ifdef Q3T_DEV
-    if (std::getenv("Q3T_PERSIST_PROF")) pprof_ = dalloc<uint64_t>((size_t)PROF_WG * PROF_PH * 4);
-#endif
     return true;
 }
 
 // the batched code-predictor frame (persist_cpb.hip): the 0.6B code-predictor shapes on the matrix-core family, with
 // layer 0 of passes 1..15 from the per-token QKV table (as decoder_stack_mm reads it), on a device that holds its 256
 // workgroups at one per CU
-bool Engine::setup_cpb() {
-    int n_cu = 0;
-    Q3T_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device_));
+bool Engine::setup_cpb(int n_cu) {
     cpb_ = opt_.cpb && mm_ok_ && max_slots_ > 1 && opt_.mm_cp_table && opt_.cp_qkv_table && !c_.has_mtp &&
            c_.cp_vocab == 2048 && c_.codec_vocab == 3072 && CP_.size() == 5 && cp_head_.size() == 15 && cp_embd_.size() >= 14 &&
            c_.cp_hidden == 1024 && c_.hidden == 1024 && c_.cp_inter == 3072 && c_.cp_heads == 16 && c_.cp_kv == 8 &&
@@ -530,51 +534,18 @@ bool Engine::setup_cpb() {
     if (!cpb_) return true;
     cpb_state_ = dalloc<uint8_t>(cpb_state_bytes());
     if (!cpb_state_) { set_error("device allocation failed"); return false; }
-#ifdef Q3T_DEV
-    if (std::getenv("Q3T_PERSIST_PROF") && !pprof_) pprof_ = dalloc<uint64_t>((size_t)PROF_WG * PROF_PH * 4);
-#endif
-    if (!pl_cp_dev_) {
-        std::vector<PLayerW> cpl(CP_.size());
-        for (size_t i = 0; i < CP_.size(); ++i)
-            cpl[i] = PLayerW{CP_[i].qkv, CP_[i].o, CP_[i].gu, CP_[i].down, CP_[i].attn_norm, CP_[i].ffn_norm, CP_[i].qn, CP_[i].kn};
-        pl_cp_dev_ = dalloc<PLayerW>(cpl.size());
-        if (!pl_cp_dev_) { set_error("device allocation failed"); return false; }
-        Q3T_HIP(hipMemcpyAsync(pl_cp_dev_, cpl.data(), cpl.size() * sizeof(PLayerW), hipMemcpyHostToDevice, stream_));
-        Q3T_HIP(hipStreamSynchronize(stream_));
-    }
-    if (!heads_dev_) {
-        heads_dev_ = dalloc<const uint16_t *>(16);
-        if (!heads_dev_) { set_error("device allocation failed"); return false; }
-        std::vector<const uint16_t *> hp(cp_head_.begin(), cp_head_.end());
-        Q3T_HIP(hipMemcpyAsync(heads_dev_, hp.data(), hp.size() * sizeof(void *), hipMemcpyHostToDevice, stream_));
-        Q3T_HIP(hipStreamSynchronize(stream_));
-    }
-    return true;
+    return upload_layer_table(CP_, pl_cp_dev_) && upload_head_table();
 }
 // the batched talker step (persist_tkb.hip): the 0.6B talker shapes on the matrix-core family, on a device that holds its
 // 256 workgroups at one per CU
-bool Engine::setup_tkb() {
-    int n_cu = 0;
-    Q3T_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device_));
+bool Engine::setup_tkb(int n_cu) {
     tkb_ = opt_.tkb && mm_ok_ && max_slots_ > 1 && !c_.has_mtp && c_.n_layers == 28 && c_.hidden == 1024 &&
            c_.n_heads == 16 && c_.n_kv == 8 && c_.head_dim == 128 && c_.inter == 3072 && c_.codec_vocab == 3072 &&
            n_cu >= 256 && tkb_resident(device_);
     if (!tkb_) return true;
     tkb_state_ = dalloc<uint8_t>(tkb_state_bytes());
     if (!tkb_state_) { set_error("device allocation failed"); return false; }
-#ifdef Q3T_DEV
-    if (std::getenv("Q3T_PERSIST_PROF") && !pprof_) pprof_ = dalloc<uint64_t>((size_t)PROF_WG * PROF_PH * 4);
-#endif
-    if (!pl_dev_) {
-        std::vector<PLayerW> pl(L_.size());
-        for (size_t i = 0; i < L_.size(); ++i)
-            pl[i] = PLayerW{L_[i].qkv, L_[i].o, L_[i].gu, L_[i].down, L_[i].attn_norm, L_[i].ffn_norm, L_[i].qn, L_[i].kn};
-        pl_dev_ = dalloc<PLayerW>(pl.size());
-        if (!pl_dev_) { set_error("device allocation failed"); return false; }
-        Q3T_HIP(hipMemcpyAsync(pl_dev_, pl.data(), pl.size() * sizeof(PLayerW), hipMemcpyHostToDevice, stream_));
-        Q3T_HIP(hipStreamSynchronize(stream_));
-    }
-    return true;
+    return upload_layer_table(L_, pl_dev_);
 }
 // the slot counts the step serves: the per-op family it reproduces (decoder_stack_mm with k_attn_seq: >= 16 policy
 // slots, no forced split attention; split-K 4 for every S_main of these shapes)

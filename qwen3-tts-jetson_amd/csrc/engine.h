@@ -166,7 +166,9 @@ private:
     bool layout_weights(const Gguf &g);
     bool upload_weights_rest();
     bool alloc_state();
-    bool setup_persist();
+    bool setup_persist(int n_cu);
+    bool upload_layer_table(const std::vector<DevLayer> &layers, PLayerW *&dev);
+    bool upload_head_table();
     // after a persistent launch flagged a fault: drain the stream, clear the hand-off state, drop the captured graphs
     // and continue on the launch-per-op graphs (the reference's permanent-fallback pattern, tts_transformer.cpp:2176-2182)
     bool persist_recover();
@@ -294,11 +296,11 @@ private:
     bool tk_roles_ = false;    // the 1-slot talker step runs persist_tk.hip
     bool cpb_ = false;         // the batched code-predictor frame runs persist_cpb.hip (use_cpb)
     uint8_t *cpb_state_ = nullptr;
-    bool setup_cpb();
+    bool setup_cpb(int n_cu);
     bool use_cpb(int S) const;
     bool tkb_ = false;         // the batched talker step runs persist_tkb.hip (use_tkb)
     uint8_t *tkb_state_ = nullptr;
-    bool setup_tkb();
+    bool setup_tkb(int n_cu);
     bool use_tkb(int S) const;
     uint8_t *pstate_ = nullptr;
     int *table_iota_ = nullptr;   // 0..codec_vocab-1: the table builds' token ids

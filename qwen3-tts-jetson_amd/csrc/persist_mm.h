@@ -6,7 +6,12 @@
 //   - the MFMA tile job: 2 row tiles of 32 rows x one 32-token tile with k_gemm_mfma's numerics (gemm_mfma.hip): weights
 //     DMA'd into LDS one job ahead, activations from hand-off buffers in B-fragment order, 4 K quarters summed in LDS
 //   - the granule epilogue
+//   - the decoder layer built on them, which both launches run: hand-off kinds and phase tags, the state layout, the
+//     residual row's fold / norm_pub, the GEMM jobs (job_qkv / job_o / job_gu / job_dn / job_head), the weight issue one
+//     job ahead, the selection's logits poll; and the host helpers of a launch (state error / clear, residency, launch)
+// The .hip files keep their loop nest and job order, attention, selection commit and parameter check.
 #pragma once
+#include "persist.h"
 #include "persist_dev.h"
 
 namespace q3t {
@@ -23,6 +28,7 @@ constexpr int BUF_RSRC = 0x00020000;   // buffer resource word 3 (gfx9 family)
 constexpr int SC1 = 16;                // buffer instruction cache policy: sc1
 constexpr int SC1V = SC1 | (int)0x80000000u;   // sc1, volatile (a poll's load is re-issued every iteration)
 constexpr int FLAGS_PER_KIND = 512;   // flag words per hand-off kind
+constexpr int CTR_ERR = 32, CTR_TICKET = 48;   // counter words of the state block (StateLayout::ctr; seq is word 0)
 
 // The f16 activation buffers behind flags (xna, xnf, attn, h) are kept in the MFMA B-fragment order of their consumers:
 // 16-byte chunk k8 (halves 8 k8 .. 8 k8 + 7) of token tok at ((tok / 32 * kch + k8) * 32 + tok % 32) * 16 bytes, kch =
@@ -102,12 +108,12 @@ __device__ __forceinline__ void publish(Ctx &X, int kind, int j, uint32_t tag) {
     CPROF((int)((tag - 1u) & 1023u), 2);
 }
 
-// the launch's LAST workgroup to finish bumps seq (ctr[0]; an exit ticket in ctr[48]): every workgroup has read seq by
+// the launch's LAST workgroup to finish bumps seq (ctr[0]; an exit ticket in ctr[CTR_TICKET]): every workgroup has read seq by
 // then, whatever order the workgroups were dispatched in.  Every workgroup runs it, idle ones included
 __device__ __forceinline__ void exit_ticket(unsigned *ctr, unsigned seq) {
     __syncthreads();
     if (threadIdx.x == 0) {
-        unsigned *done = ctr + 48;
+        unsigned *done = ctr + CTR_TICKET;
         if (__hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
             __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(ctr, seq + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -265,6 +271,264 @@ __device__ __forceinline__ void epi_gran(Ctx &X, size_t obase, int ldo, int row0
     __syncthreads();   // the LDS region is the next job's DMA target
 }
 
+// ================================================================ the decoder layer both launches run
+#pragma clang fp contract(off)   // every rounding as written: bit-identical to k_gemm_mfma / k_resid_norm
+
+// hand-off kinds; a phase is (layer slot, kind): 8 per layer slot.  k_tkb's layer slots are its layers (28: the final
+// norm / head), k_cpb's are 6 per pass (5: the final norm / head)
+enum Kind { K_RNA = 0, K_QKV = 1, K_ATT = 2, K_O = 3, K_RNF = 4, K_GU = 5, K_DN = 6, K_HEAD = 7 };
+__device__ __forceinline__ int ph_of(int ls, int k) { return ls * 8 + k; }
+
+// ---------------------------------------------------------------- state block (zeroed once)
+// xna / xnf / attn / h: f16 payloads behind flags; qkv, slo, sld, lg: {f32, tag} granules (8 B each, no flag); V = the
+// logits width
+struct StateLayout {
+    size_t xna = 0;
+    size_t xnf = xna + (size_t)SMAX * H * 2;
+    size_t qkv = xnf + (size_t)SMAX * H * 2;
+    size_t attn = qkv + (size_t)SMAX * QKVN * 8;
+    size_t slo = attn + (size_t)SMAX * NH * D * 2;
+    size_t sld = slo + (size_t)4 * SMAX * H * 8;
+    size_t h = sld + (size_t)4 * SMAX * H * 8;
+    size_t lg = h + (size_t)SMAX * INTER * 2;
+    size_t flags;   // 8 kinds x FLAGS_PER_KIND u32
+    size_t ctr;     // own lines: seq at ctr[0], the error word at ctr[32], the exit ticket at ctr[48]
+    size_t total;
+    constexpr explicit StateLayout(int V) : flags(lg + (size_t)SMAX * V * 8), ctr(flags + 8 * FLAGS_PER_KIND * 4), total(ctr + 256) {}
+};
+static_assert(StateLayout(CPV).flags == 8257536 && StateLayout(CPV).ctr == 8273920 && StateLayout(CPV).total == 8274176, "code-predictor state");
+static_assert(StateLayout(VOC).flags == 8781824 && StateLayout(VOC).ctr == 8798208 && StateLayout(VOC).total == 8798464, "talker state");
+static_assert(StateLayout(VOC).qkv == 262144 && StateLayout(VOC).attn == 2359296 && StateLayout(VOC).slo == 2621440 &&
+              StateLayout(VOC).sld == 4718592 && StateLayout(VOC).h == 6815744 && StateLayout(VOC).lg == 7208960, "state offsets");
+
+__device__ __forceinline__ Ctx make_ctx(uint8_t *state, const StateLayout &SL, uint64_t *prof, int S, uint4 (*wl)[32][64]) {
+    unsigned *ctr = reinterpret_cast<unsigned *>(state + SL.ctr);
+    return Ctx{wl, prof, Ctl{ctr + CTR_ERR, false}, __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+               reinterpret_cast<unsigned *>(state + SL.flags), __builtin_amdgcn_make_buffer_rsrc(state, 0, (int)SL.total, BUF_RSRC), S};
+}
+
+// ---------------------------------------------------------------- the residual row of slot b (thread t: x = elements 4t .. 4t+3)
+// RMSNorm of x -> f16 row of slot b (fragment order) in the hand-off buffer `xo`, flag (kind, b); side (optional): the
+// f32 normalised rows [slot][H]
+__device__ __forceinline__ void norm_pub(Ctx &X, const float4 &x, int b, const float *nw, float eps, double *dscr, size_t xo, int kind,
+                                         uint32_t tg, float *side) {
+    const int t = threadIdx.x;
+    double ss = (double)(x.x * x.x) + (double)(x.y * x.y) + (double)(x.z * x.z) + (double)(x.w * x.w);
+    ss = block_sum_d(ss, dscr);
+    const float scale = 1.0f / sqrtf((float)(ss / H) + eps);
+    const float4 wv = ldf4(nw + 4 * t);
+    const float y0 = (x.x * scale) * wv.x, y1 = (x.y * scale) * wv.y, y2 = (x.z * scale) * wv.z, y3 = (x.w * scale) * wv.w;
+    if (side) *reinterpret_cast<float4 *>(side + (size_t)b * H + 4 * t) = make_float4(y0, y1, y2, y3);
+    const u32x2_t hv = {(uint32_t)f2h(y0) | ((uint32_t)f2h(y1) << 16), (uint32_t)f2h(y2) | ((uint32_t)f2h(y3) << 16)};
+    CPROF((int)((tg - 1u) & 1023u), 3);
+    __builtin_amdgcn_raw_buffer_store_b64(hv, X.rs, (int)xo + fragoff(H / 8, b, 4 * t), 0, SC1);
+    publish(X, kind, b, tg);
+}
+// x += the 4 split-K slabs of slot b (k_resid_norm<4> order): thread t polls the 16 granules of its 4 elements
+__device__ __forceinline__ void fold(Ctx &X, float4 &x, int b, size_t slab, uint32_t tg) {
+    const int t = threadIdx.x;
+    const int ph_ = (int)((tg - 1u) & 1023u);
+    (void)ph_;
+    CPROF(ph_, 0);
+    u32x4_t pz[8];
+    poll_gran<8>(X, tg, pz, [&](u32x4_t (&r)[8]) {
+#pragma unroll
+        for (int z = 0; z < 4; ++z)
+#pragma unroll
+            for (int hh2 = 0; hh2 < 2; ++hh2)
+                r[2 * z + hh2] = __builtin_amdgcn_raw_buffer_load_b128(X.rs, (int)(slab + (((size_t)z * SMAX + b) * H + 4 * t + 2 * hh2) * 8), 0, SC1V);
+    });
+    CPROF(ph_, 1);
+#pragma unroll
+    for (int z = 0; z < 4; ++z)
+        x = make_float4(x.x + __uint_as_float(pz[2 * z].x), x.y + __uint_as_float(pz[2 * z].z), x.z + __uint_as_float(pz[2 * z + 1].x),
+                        x.w + __uint_as_float(pz[2 * z + 1].z));
+}
+
+// ---------------------------------------------------------------- GEMM jobs (64 rows x the 32 tokens of tile tt; ls = the layer slot)
+// full-K job j (row panel j % nrp, tile j / nrp) on the normalised rows xna: granules out[tok][64 rp ..] of kind `kout`
+__device__ __forceinline__ void job_rows(Ctx &X, const StateLayout &SL, int j, int nrp, int ls, int kout, size_t obase, int ldo) {
+    const int rp = j % nrp, tt = j / nrp;
+    const int nv = min(32, X.S_ - 32 * tt);
+    wait_flags_wg(X, K_RNA, nv, [&](int i) { return 32 * tt + i; }, X.tag(ph_of(ls, K_RNA)));
+    mm_tile<4>(X, SL.xna, H / 8, 0, 32 * tt);
+    CPROF(ph_of(ls, kout), 3);
+    epi_gran(X, obase, ldo, 64 * rp, 32 * tt, X.tag(ph_of(ls, kout)));
+    CPROF(ph_of(ls, kout), 2);
+}
+__device__ __forceinline__ void job_qkv(Ctx &X, const StateLayout &SL, int w, int ls) { job_rows(X, SL, w, 64, ls, K_QKV, SL.qkv, QKVN); }
+// lm_head / codec head: V logits, nrp = V / 64 row panels
+__device__ __forceinline__ void job_head(Ctx &X, const StateLayout &SL, int w, int ls, int V, int nrp) {
+    job_rows(X, SL, w, nrp, ls, K_HEAD, SL.lg, V);
+}
+// O: split-K slab z (heads 4z .. 4z+3) of rows 64 rp .. +63; wait(z, tt, nv, tag) returns once the tile's attention
+// rows of that slice are published
+template <class Wait>
+__device__ __forceinline__ void job_o(Ctx &X, const StateLayout &SL, int w, int ls, Wait wait) {
+    const int rp = w % 16, z = (w / 16) % 4, tt = w / 64;
+    const int nv = min(32, X.S_ - 32 * tt);
+    wait(z, tt, nv, X.tag(ph_of(ls, K_ATT)));
+    mm_tile<2>(X, SL.attn, NH * D / 8, 512 * z, 32 * tt);
+    CPROF(ph_of(ls, K_O), 3);
+    epi_gran(X, SL.slo + (size_t)z * SMAX * H * 8, H, 64 * rp, 32 * tt, X.tag(ph_of(ls, K_O)));
+    CPROF(ph_of(ls, K_O), 2);
+}
+// GU: 32 SwiGLU units (rows 64 rp .. +63, gate/up interleaved in 16-row blocks) -> h f16, flag (K_GU, gj)
+__device__ __forceinline__ void job_gu(Ctx &X, const StateLayout &SL, int gj, int ls) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int rp = gj % 96, tt = gj / 96;
+    const int nv = min(32, X.S_ - 32 * tt);
+    wait_flags_wg(X, K_RNF, nv, [&](int i) { return 32 * tt + i; }, X.tag(ph_of(ls, K_RNF)));
+    mm_tile<4>(X, SL.xnf, H / 8, 0, 32 * tt);
+    CPROF(ph_of(ls, K_GU), 3);
+    {   // k_gemm_mfma SWIGLU epilogue per row tile: wave = (rt, q)
+        const int rt = wave >> 1, q = wave & 1, r = lane & 31, h = lane >> 5;
+        const int tok = 32 * tt + r;
+        if (tok < X.S_) {
+            const int unit = 32 * rp + 16 * rt + 8 * q + 4 * h;
+            float hv[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) hv[e] = silu_f(sum4(X.wl, rt, 4 * q + e, lane)) * sum4(X.wl, rt, 4 * (q + 2) + e, lane);
+            const u32x2_t o = {(uint32_t)f2h(hv[0]) | ((uint32_t)f2h(hv[1]) << 16), (uint32_t)f2h(hv[2]) | ((uint32_t)f2h(hv[3]) << 16)};
+            __builtin_amdgcn_raw_buffer_store_b64(o, X.rs, (int)SL.h + fragoff(INTER / 8, tok, unit), 0, SC1);
+        }
+    }
+    publish(X, K_GU, gj, X.tag(ph_of(ls, K_GU)));
+}
+// DN: split-K slab z of rows 64 rp .. +63; wave v reads units [768 z + 192 v, +192)
+__device__ __forceinline__ void job_dn(Ctx &X, const StateLayout &SL, int w, int ls) {
+    const int wave = threadIdx.x >> 6;
+    const int rp = w % 16, z = (w / 16) % 4, tt = w / 64;
+    // each wave waits for the 6 gate/up jobs of its own K quarter only (units [768 z + 192 v, +192)): no barrier, no wave
+    // held by another quarter's late producer
+    wait_flags(X, K_GU, 6, [&](int i) { return 24 * z + 6 * wave + i + 96 * tt; }, X.tag(ph_of(ls, K_GU)));
+    mm_tile<3>(X, SL.h, INTER / 8, 768 * z, 32 * tt);
+    CPROF(ph_of(ls, K_DN), 3);
+    epi_gran(X, SL.sld + (size_t)z * SMAX * H * 8, H, 64 * rp, 32 * tt, X.tag(ph_of(ls, K_DN)));
+    CPROF(ph_of(ls, K_DN), 2);
+}
+
+// ---------------------------------------------------------------- weight issue, one job ahead
+// The workgroup's job classes: QKV / O / DN jobs on workgroups [0, 64 NT), lm_head on [0, nhp NT) (nhp row panels), and
+// gate/up job gj on workgroups [0, 128), then the odd slot workgroups 129, 131, ...: the residual rows' workgroups
+// (even) run the norm right before gate/up, so a gate/up job there started ~2 us after the others
+constexpr int SW0 = 128;   // slot workgroups: SW0 + 2b (slot b's residual row) and SW0 + 2b + 1
+struct Jobs {
+    int w, gj;
+    bool hq, hg, hh, slot;
+    __device__ __forceinline__ Jobs(int w_, int NT, int nhp, int S)
+        : w(w_), gj(w_ < SW0 ? w_ : (w_ & 1) ? SW0 + (w_ - SW0 - 1) / 2 : -1), hq(w_ < 64 * NT), hg(gj >= 0 && gj < 96 * NT), hh(w_ < nhp * NT),
+          slot(w_ >= SW0 && w_ - SW0 < 2 * S) {}
+    __device__ __forceinline__ bool has(int k) const { return k == K_GU ? hg : k == K_HEAD ? hh : hq; }
+};
+struct WJob { int pass = 0, l = 0, k = K_QKV; };   // the job whose weights wl holds: (pass, layer or nl = the head, kind)
+// Advance: (WJob &) -> the kernel's next job in program order (pass >= npass: none left); HeadW: (const WJob &) -> the
+// head job's weights
+template <class Advance, class HeadW>
+struct WeightIssue {
+    uint4 (*wl)[32][64];
+    const PLayerW *layers;   // [nl]
+    int nl, npass, nhp;
+    Jobs J;
+    Advance advance;
+    HeadW head;
+    WJob j;
+    bool pending = false;
+    __device__ __forceinline__ void issue() {
+        while (j.pass < npass && !J.has(j.k)) advance(j);
+        if (j.pass >= npass) return;
+        const PLayerW &Lw = layers[j.l < nl ? j.l : 0];
+        const int w = J.w;
+        switch (j.k) {
+            case K_QKV: load_w<4>(wl, Lw.qkv, H, 64 * (w % 64), 0); break;
+            case K_O: load_w<2>(wl, Lw.o, NH * D, 64 * (w % 16), 512 * ((w / 16) % 4)); break;
+            case K_GU: load_w<4>(wl, Lw.gu, H, 64 * (J.gj % 96), 0); break;
+            case K_DN: load_w<3>(wl, Lw.down, INTER, 64 * (w % 16), 768 * ((w / 16) % 4)); break;
+            default: load_w<4>(wl, head(j), H, 64 * (w % nhp), 0); break;
+        }
+    }
+    __device__ __forceinline__ void next_job() { advance(j); issue(); }
+    // a slot workgroup issues the next job's weights after its next attention (the polls of the norm and attention steps
+    // before it then do not queue behind 128 KB of weight DMA), at the latest when that job starts: defer, then flush
+    __device__ __forceinline__ void defer() { pending = true; }
+    __device__ __forceinline__ void after_job() { if (J.slot) pending = true; else next_job(); }
+    __device__ __forceinline__ void flush() { if (pending) { next_job(); pending = false; } }
+};
+template <class Advance, class HeadW>
+__device__ __forceinline__ WeightIssue<Advance, HeadW> weight_issue(uint4 (*wl)[32][64], const PLayerW *layers, int nl, int npass, int nhp,
+                                                                    const Jobs &J, Advance advance, HeadW head) {
+    return WeightIssue<Advance, HeadW>{wl, layers, nl, npass, nhp, J, advance, head};
+}
+
+// ---------------------------------------------------------------- selection input
+// thread t polls logits VPT t .. VPT t + VPT - 1 of slot b's row (select_token's exact-width ownership, V = 256 VPT)
+// into v[], padded with -inf
+template <int VPT, int NV>
+__device__ __forceinline__ void poll_logits(Ctx &X, size_t lg, int b, uint32_t tg, float (&v)[NV]) {
+    const int t = threadIdx.x;
+    u32x4_t lr[VPT / 2];
+    poll_gran<VPT / 2>(X, tg, lr, [&](u32x4_t (&r)[VPT / 2]) {
+#pragma unroll
+        for (int k = 0; k < VPT / 2; ++k)
+            r[k] = __builtin_amdgcn_raw_buffer_load_b128(X.rs, (int)(lg + ((size_t)b * (VPT * 256) + VPT * t + 2 * k) * 8), 0, SC1V);
+    });
+#pragma unroll
+    for (int k = 0; k < VPT / 2; ++k) { v[2 * k] = __uint_as_float(lr[k].x); v[2 * k + 1] = __uint_as_float(lr[k].z); }
+#pragma unroll
+    for (int e = VPT; e < NV; ++e) v[e] = -INFINITY;
+}
+
+// ================================================================ host side of a batched launch
+// K1 / K2: the kernel's instantiations for one / two token tiles; SL: its state layout
+template <class Lds>
+constexpr size_t lds_bytes() {
+    static_assert(sizeof(Lds) <= 160 * 1024, "LDS");
+    return std::max(sizeof(Lds), (size_t)96 * 1024);   // > 80 KB: one workgroup per CU
+}
+template <auto K>
+bool attr(size_t lds) {
+    static bool done = false;
+    if (!done) {
+        Q3T_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        done = true;
+    }
+    return true;
+}
+template <auto K1, auto K2>
+bool resident(int device, size_t lds) {   // both instantiations fit one workgroup per CU, >= G CUs
+    int n_cu = 0, blocks = 0;
+    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < G) return false;
+    for (const void *k : {reinterpret_cast<const void *>(K1), reinterpret_cast<const void *>(K2)}) {
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k, 256, lds) != hipSuccess || blocks < 1) return false;
+    }
+    return true;
+}
+template <auto K1, auto K2, class P>
+bool launch_by_tile_count(const P &p, size_t lds, hipStream_t s) {
+    if (p.S <= 32) {
+        if (!attr<K1>(lds)) return false;
+        hipLaunchKernelGGL(K1, dim3(G), dim3(256), lds, s, p);
+    } else {
+        if (!attr<K2>(lds)) return false;
+        hipLaunchKernelGGL(K2, dim3(G), dim3(256), lds, s, p);
+    }
+    Q3T_HIP(hipGetLastError());
+    return true;
+}
+inline bool state_error(const StateLayout &SL, const uint8_t *state, hipStream_t s, bool *err) {
+    unsigned e = 0;
+    Q3T_HIP(hipMemcpyAsync(&e, state + SL.ctr + CTR_ERR * 4, 4, hipMemcpyDeviceToHost, s));
+    Q3T_HIP(hipStreamSynchronize(s));
+    *err = e != 0;
+    return true;
+}
+inline bool state_clear(const StateLayout &SL, uint8_t *state, hipStream_t s) {   // after a fault: zero the flags and the error word (seq kept)
+    Q3T_HIP(hipMemsetAsync(state + SL.flags, 0, SL.ctr - SL.flags, s));
+    Q3T_HIP(hipMemsetAsync(state + SL.ctr + CTR_ERR * 4, 0, 4, s));
+    Q3T_HIP(hipMemsetAsync(state + SL.ctr + CTR_TICKET * 4, 0, 4, s));   // the exit ticket
+    return true;
+}
 
 }  // namespace pmm
 }  // namespace q3t

@@ -3,12 +3,13 @@
 Every headline number of bench.py runs on a configuration checked here, teacher-forced against the CPU oracle
 (q3t_testutil.check_decisions, partial replay with from_frame so the oracle's time stays bounded):
 
-  B=1, 512 frames, max_ctx 544      bench.py's main workload (configs[1]): k_persist<0,64> with up to 9 attention splits
-                                    per kv group at the last frames (KV positions up to 522).  First and last 64 frames
-                                    checked, greedy and T=0.9 (the bench's sampling parameters).
-  64 slots, 512 frames, max_ctx 544 bench.py's `batched` section (configs[2]): the matrix-core path with k_attn_seq over
-                                    up to nch = 9 64-position chunks.  Slots 0, 31 and 63: the last 64 frames (and the
-                                    first 64 of slot 0), T=0.9.
+  B=1, 512 frames, max_ctx 544      bench.py's main workload (configs[1]): k_tk_roles (persist_tk.hip) with up to 9
+                                    attention splits per kv group at the last frames (KV positions up to 522).  First and
+                                    last 64 frames checked, greedy and T=0.9 (the bench's sampling parameters).
+  64 slots, 512 frames, max_ctx 544 bench.py's `batched` section (configs[2]): the persistent launches k_tkb
+                                    (persist_tkb.hip, its attention over up to nch = 9 64-position chunks) and k_cpb
+                                    (persist_cpb.hip).  Slots 0, 31 and 63: the last 64 frames (and the first 64 of
+                                    slot 0), T=0.9.
   continuous batching, 64 slots,    bench.py's `serving` section in miniature: q3t_generate_queue with 160 utterances of
   160 utterances                    10..40 text tokens (natural EOS), all 64 slots vs 16 in flight bit-identical, three
                                     admitted utterances (first refill, middle, last) teacher-forced against the oracle.
@@ -106,7 +107,7 @@ def batched64(full):
 
 @pytest.mark.parametrize("slot", [0, 31, 63])
 def test_64_slots_512_frames(full, batched64, slot):
-    """the matrix-core step with k_attn_seq over up to 9 chunks (positions up to 522); generate() keys sampling by
+    """k_tkb's step (attention over up to 9 chunks, positions up to 522) and k_cpb's frame; generate() keys sampling by
     slot index"""
     tts, tok, orc = full
     prompts, spk, outs = batched64

@@ -53,6 +53,17 @@ struct ConvParams {
     int xcd_tiles = 0;  // k_conv_mt 1-tap narrow variant: channel tiles of a row tile on one XCD (set by conv())
 };
 bool conv(const ConvParams &p, hipStream_t s);
+// the kernel conv() launches for p (host arithmetic only: the tile count, the channel counts, the tap layout and the
+// Q3T_CONV_* environment switches).  conv() launches by switching on this value, so the two cannot diverge.
+enum { CONV_NONE = 0, CONV_GENERIC = 1, CONV_MT = 2, CONV_PD = 3 };
+struct ConvKernel {
+    int family = CONV_NONE;   // CONV_NONE: nothing is launched (empty or unsupported parameters)
+    int RB = 0, NT = 0;       // k_conv_mt / k_conv_pd: 128 RB rows x NT output channels per workgroup
+    int TW = 0;               // k_conv_mt: TW (taps staged per chunk); k_conv_pd: TAPS
+    int MINB = 0;             // workgroups per CU of the launch bounds
+    int xcd = 0;              // tiles taken in XCD order (ConvParams::xcd_tiles of the launch)
+};
+ConvKernel conv_kernel(const ConvParams &p);
 // one 96-channel decoder residual unit as one launch (vocoder_resunit.hip), bit-identical to its two conv launches:
 //   h = f16(snake2(conv7_dil(xh) + b1)) (kept on chip);  y = x + conv1(h) + b2;  y16 = f16(snake_next(y))
 // xh / y16 are f16 [T][96] (different buffers: a tile's causal window reads rows of its neighbours), x / y f32 (may

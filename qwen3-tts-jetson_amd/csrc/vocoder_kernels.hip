@@ -702,17 +702,6 @@ template <int RB, int NT, int MINB, int TW>
 static bool launch_mt1(const ConvParams &p, hipStream_t s) {
     return p.act ? launch_mt2<RB, NT, MINB, TW, -1>(p, s) : launch_mt2<RB, NT, MINB, TW, 0>(p, s);
 }
-template <int RB, int NT, int MINB = 2>
-static bool launch_mt(const ConvParams &p, hipStream_t s) {
-    if constexpr (MINB == 3) {   // the 1-tap narrow-channel variant only
-        return launch_mt1<RB, NT, MINB, 1>(p, s);
-    } else {
-        if (p.n_taps <= 1) return launch_mt1<RB, NT, MINB, 1>(p, s);
-        if (p.n_taps <= 3) return launch_mt1<RB, NT, MINB, 3>(p, s);
-        return launch_mt1<RB, NT, MINB, 7>(p, s);
-    }
-}
-
 #ifdef Q3T_DEV
 // development builds: Q3T_CONV_VARIANT picks another tile shape for the multi-tap convs (tools/dev experiments)
 static const int g_conv_variant = [] { const char *e = std::getenv("Q3T_CONV_VARIANT"); return e ? std::atoi(e) : 0; }();
@@ -724,6 +713,71 @@ static constexpr int g_conv_variant = 0;
 static const int g_conv_skip = [] { const char *e = std::getenv("Q3T_CONV_SKIP"); return e ? std::atoi(e) : 0; }();
 #endif
 
+// conv()'s argument checks: 0 launch, 1 nothing to do, -1 unsupported (err set)
+static int conv_check(const ConvParams &p, const char *&err) {
+    if (p.ct_st) {   // one launch over every output phase (multi-tile kernels only)
+        const int NT = p.C_out % 96 == 0 ? 96 : p.C_out % 64 == 0 ? 64 : 0;
+        if (!p.xh || !NT || p.C_in % MT_KC != 0 || p.ct_k > p.ct_st * CONV_MAX_TAPS) {
+            err = "conv: unsupported transposed launch";
+            return -1;
+        }
+        if (p.nb <= 0) return 1;
+        if (p.nb > 1 && (p.xbs < p.T_in || p.ybs < p.T_out)) { err = "conv: bad utterance strides"; return -1; }
+        return p.T_out <= 0 ? 1 : 0;
+    }
+    if (p.M <= 0 || p.nb <= 0) return 1;
+    if (p.nb > 1 && (p.xbs < p.T_in || p.ybs <= 0)) { err = "conv: bad utterance strides"; return -1; }
+    if (p.n_taps < 1 || p.n_taps > CONV_MAX_TAPS || p.dmax - p.dmin > CT_MAXWIN - CT_M) {
+        err = "conv: unsupported tap layout";
+        return -1;
+    }
+    if (!p.y && !p.y16) { err = "conv: no output"; return -1; }
+    return 0;
+}
+
+ConvKernel conv_kernel(const ConvParams &p) {
+    ConvKernel k;
+    const char *err = nullptr;
+    if (conv_check(p, err) != 0) return k;
+    const int NT = p.C_out % 96 == 0 ? 96 : p.C_out % 64 == 0 ? 64 : 0;
+    const int xcd = conv_xcd_tiles();
+    auto mt = [&](int RB, int MINB, int TW) { return ConvKernel{CONV_MT, RB, NT, TW, MINB, xcd}; };
+    auto pd = [&](int RB, int TAPS) { return ConvKernel{CONV_PD, RB, NT, TAPS, 1, xcd}; };
+    if (p.ct_st) {
+        const int M = (p.T_out + p.ct_st - 1) / p.ct_st;   // phase 0 has the most rows
+        const int n_taps = (p.ct_k + p.ct_st - 1) / p.ct_st;
+        const long tiles256 = (long)((M + 255) / 256) * (p.C_out / NT) * p.ct_st * p.nb;
+        // the pipelined kernel (512-row tiles, both taps of a phase per K chunk) where a tile has 24+ K chunks (per launch
+        // at 512 frames: C_in 1536 116 -> 94 us, 768 162 -> 157; 384 209 -> 201; 192 275 -> 288 us)
+        if (tiles256 >= 512 && p.C_in >= 768 && conv_pd_mode() == 2 && pd_ok(p) && conv_pd_ct()) return pd(4, 2);
+        return mt(tiles256 >= 512 ? 2 : 1, 2, n_taps <= 1 ? 1 : n_taps <= 3 ? 3 : 7);
+    }
+    if (p.xh && NT && p.C_in % MT_KC == 0) {
+        // RB 2 (256-row tiles) unless that leaves fewer than two workgroups per CU to fill the chip.  1-tap convs over
+        // narrow channel counts are bound by their epilogue traffic (f32 residual in, f32 + f16 out): 128-row tiles
+        // at three workgroups per CU keep more of it in flight
+        const long tiles256 = (long)((p.M + 255) / 256) * (p.C_out / NT) * p.nb;
+        const bool big = tiles256 >= 512;
+        if (big && p.n_taps == 1 && p.C_in <= 192) return mt(1, 3, 1);
+        if (g_conv_variant && big && p.n_taps > 1) {   // (these run without the XCD tile order)
+            switch (g_conv_variant) {
+                case 1: return ConvKernel{CONV_MT, 1, NT, 7, 2, 0};
+                case 2: return ConvKernel{CONV_MT, 2, 32, 7, 3, 0};
+                case 3: return ConvKernel{CONV_MT, 4, 32, 7, 2, 0};
+                case 4: return ConvKernel{CONV_MT, 4, NT, 7, 1, 0};
+                default: break;
+            }
+        }
+        // the pipelined kernel for the wide blocks' 7-tap convs (512 frames, per launch: C_in 768 191 -> 125 us, 384
+        // 278 -> 207 us, 192 301 -> 256 us with 512-row tiles; 256-row tiles: 135 / 202 us, and no gain at 192)
+        const int pm = conv_pd_mode();
+        if (big && p.n_taps > 3 && p.C_in >= conv_pd_minc() && pd_ok(p) && (pm == 1 || pm == 2)) return pd(2 * pm, CONV_MAX_TAPS);
+        return mt(big ? 2 : 1, 2, p.n_taps <= 1 ? 1 : p.n_taps <= 3 ? 3 : 7);
+    }
+    k.family = CONV_GENERIC;
+    return k;
+}
+
 bool conv(const ConvParams &pin, hipStream_t s) {
 #ifdef Q3T_DEV
     ConvParams p = pin;
@@ -731,69 +785,55 @@ bool conv(const ConvParams &pin, hipStream_t s) {
 #else
     const ConvParams &p = pin;
 #endif
-    if (p.ct_st) {   // one launch over every output phase (multi-tile kernel only)
-        const int NT = p.C_out % 96 == 0 ? 96 : p.C_out % 64 == 0 ? 64 : 0;
-        if (!p.xh || !NT || p.C_in % MT_KC != 0 || p.ct_k > p.ct_st * CONV_MAX_TAPS) {
-            set_error("conv: unsupported transposed launch");
-            return false;
-        }
-        if (p.nb <= 0) return true;
-        if (p.nb > 1 && (p.xbs < p.T_in || p.ybs < p.T_out)) { set_error("conv: bad utterance strides"); return false; }
-        ConvParams q = p;
-        q.xcd_tiles = conv_xcd_tiles();
-        q.M = (p.T_out + p.ct_st - 1) / p.ct_st;   // phase 0 has the most rows
+    const char *err = nullptr;
+    const int chk = conv_check(p, err);
+    if (chk < 0) { set_error(err); return false; }
+    if (chk > 0) return true;
+    const ConvKernel k = conv_kernel(p);
+    if (k.family == CONV_GENERIC) {
+        const dim3 grid((p.M + CT_M - 1) / CT_M, (p.C_out + CT_N - 1) / CT_N, p.nb);
+        hipLaunchKernelGGL(k_conv, grid, dim3(256), 0, s, p);
+        Q3T_HIP(hipGetLastError());
+        return true;
+    }
+    ConvParams q = p;
+    q.xcd_tiles = k.xcd;
+    if (p.ct_st) {
+        q.M = (p.T_out + p.ct_st - 1) / p.ct_st;
         q.n_taps = (p.ct_k + p.ct_st - 1) / p.ct_st;
         q.dmin = 0;
         q.dmax = q.n_taps - 1;                      // taps of one phase are consecutive input rows
-        if (q.M <= 0) return true;
-        const long tiles256 = (long)((q.M + 255) / 256) * (p.C_out / NT) * p.ct_st * p.nb;
-        // the pipelined kernel (512-row tiles, both taps of a phase per K chunk) where a tile has 24+ K chunks (per launch
-        // at 512 frames: C_in 1536 116 -> 94 us, 768 162 -> 157; 384 209 -> 201; 192 275 -> 288 us)
-        if (tiles256 >= 512 && p.C_in >= 768 && conv_pd_mode() == 2 && pd_ok(q) && conv_pd_ct())
-            return NT == 96 ? launch_pd<4, 96, 2>(q, s) : launch_pd<4, 64, 2>(q, s);
-        if (NT == 96) return tiles256 >= 512 ? launch_mt<2, 96>(q, s) : launch_mt<1, 96>(q, s);
-        return tiles256 >= 512 ? launch_mt<2, 64>(q, s) : launch_mt<1, 64>(q, s);
     }
-    if (p.M <= 0 || p.nb <= 0) return true;
-    if (p.nb > 1 && (p.xbs < p.T_in || p.ybs <= 0)) { set_error("conv: bad utterance strides"); return false; }
-    if (p.n_taps < 1 || p.n_taps > CONV_MAX_TAPS || p.dmax - p.dmin > CT_MAXWIN - CT_M) {
-        set_error("conv: unsupported tap layout");
-        return false;
-    }
-    const int NT = p.C_out % 96 == 0 ? 96 : p.C_out % 64 == 0 ? 64 : 0;
-    if (p.xh && NT && p.C_in % MT_KC == 0 && (p.y || p.y16)) {
-        // RB 2 (256-row tiles) unless that leaves fewer than two workgroups per CU to fill the chip.  1-tap convs over
-        // narrow channel counts are bound by their epilogue traffic (f32 residual in, f32 + f16 out): 128-row tiles
-        // at three workgroups per CU keep more of it in flight
-        const long tiles256 = (long)((p.M + 255) / 256) * (p.C_out / NT) * p.nb;
-        const bool big = tiles256 >= 512;
-        ConvParams q = p;
-        q.xcd_tiles = conv_xcd_tiles();
-        if (big && p.n_taps == 1 && p.C_in <= 192) return NT == 96 ? launch_mt<1, 96, 3>(q, s) : launch_mt<1, 64, 3>(q, s);
-        if (g_conv_variant && big && p.n_taps > 1) {
-            switch (g_conv_variant) {
-                case 1: return NT == 96 ? launch_mt1<1, 96, 2, 7>(p, s) : launch_mt1<1, 64, 2, 7>(p, s);
-                case 2: return launch_mt1<2, 32, 3, 7>(p, s);
-                case 3: return launch_mt1<4, 32, 2, 7>(p, s);
-                case 4: return NT == 96 ? launch_mt1<4, 96, 1, 7>(p, s) : launch_mt1<4, 64, 1, 7>(p, s);
-                default: break;
-            }
+    // one case per kernel instance: the launch is a function of the choice alone
+#define Q3T_CONV_KEY(RB, NT, MINB, TW) ((((RB) * 100 + (NT)) * 10 + (MINB)) * 10 + (TW))
+#define Q3T_MT(RB, NT, MINB, TW) case Q3T_CONV_KEY(RB, NT, MINB, TW): return launch_mt1<RB, NT, MINB, TW>(q, s)
+#define Q3T_PD(RB, NT, TAPS) case Q3T_CONV_KEY(RB, NT, 1, TAPS): return launch_pd<RB, NT, TAPS>(q, s)
+    const int key = Q3T_CONV_KEY(k.RB, k.NT, k.MINB, k.TW);
+    if (k.family == CONV_MT) {
+        switch (key) {
+            Q3T_MT(1, 96, 2, 1); Q3T_MT(1, 96, 2, 3); Q3T_MT(1, 96, 2, 7);
+            Q3T_MT(1, 64, 2, 1); Q3T_MT(1, 64, 2, 3); Q3T_MT(1, 64, 2, 7);
+            Q3T_MT(2, 96, 2, 1); Q3T_MT(2, 96, 2, 3); Q3T_MT(2, 96, 2, 7);
+            Q3T_MT(2, 64, 2, 1); Q3T_MT(2, 64, 2, 3); Q3T_MT(2, 64, 2, 7);
+            Q3T_MT(1, 96, 3, 1); Q3T_MT(1, 64, 3, 1);
+#ifdef Q3T_DEV
+            Q3T_MT(2, 32, 3, 7); Q3T_MT(4, 32, 2, 7); Q3T_MT(4, 96, 1, 7); Q3T_MT(4, 64, 1, 7);
+#endif
+            default: break;
         }
-        // the pipelined kernel for the wide blocks' 7-tap convs (512 frames, per launch: C_in 768 191 -> 125 us, 384
-        // 278 -> 207 us, 192 301 -> 256 us with 512-row tiles; 256-row tiles: 135 / 202 us, and no gain at 192)
-        const int pm = conv_pd_mode();
-        if (big && p.n_taps > 3 && p.C_in >= conv_pd_minc() && pd_ok(p)) {
-            if (pm == 1) return NT == 96 ? launch_pd<2, 96>(q, s) : launch_pd<2, 64>(q, s);
-            if (pm == 2) return NT == 96 ? launch_pd<4, 96>(q, s) : launch_pd<4, 64>(q, s);
+    } else if (k.family == CONV_PD) {
+        switch (key) {
+            Q3T_PD(4, 96, 2); Q3T_PD(4, 64, 2);
+            Q3T_PD(2, 96, 7); Q3T_PD(2, 64, 7);
+            Q3T_PD(4, 96, 7); Q3T_PD(4, 64, 7);
+            default: break;
         }
-        if (NT == 96) return big ? launch_mt<2, 96>(q, s) : launch_mt<1, 96>(q, s);
-        return big ? launch_mt<2, 64>(q, s) : launch_mt<1, 64>(q, s);
     }
-    if (!p.y && !p.y16) { set_error("conv: no output"); return false; }
-    const dim3 grid((p.M + CT_M - 1) / CT_M, (p.C_out + CT_N - 1) / CT_N, p.nb);
-    hipLaunchKernelGGL(k_conv, grid, dim3(256), 0, s, p);
-    Q3T_HIP(hipGetLastError());
-    return true;
+#undef Q3T_PD
+#undef Q3T_MT
+#undef Q3T_CONV_KEY
+    set_error("conv: no kernel instance for the chosen shape");
+    return false;
 }
 
 __global__ void __launch_bounds__(256) k_snake_f16(const float *x, const float *a, const float *ib, uint16_t *out, int64_t n4, int C) {

@@ -97,8 +97,11 @@ def batched64(full):
         base = prompt("full")
         prompts = [base[:4] + [(t + 31 * i) % 900 + 20 for t in base[4:]] for i in range(n)]
         spk = [np.zeros(eng.cfg["hidden"], np.float32)] * n
+        # the batched persistent frame (16) and step (32): a silent fall-back to the per-op graphs must not pass
+        assert eng.persist_kernels() & 48 == 48, eng.persist_kernels()
         outs = eng.generate(prompts, speakers=spk, max_len=NF, temperature=0.9, top_k=50, seed=4321,
                             force_frames=NF)
+        assert eng.persist_status() == 0
     finally:
         eng.close()
     assert all(o.shape == (NF, 16) for o in outs)

@@ -222,21 +222,9 @@ __global__ void __launch_bounds__(256) k_persist(const PersistParams p) {
                 x = make_float4(h2f(hv.x & 0xffff), h2f(hv.x >> 16), h2f(hv.y & 0xffff), h2f(hv.y >> 16));
             }
         } else if (l == 0) {
-            if (MODE == 0 && p.gather) {
-                const GatherSum &gs = p.gs;
-                const int *tk = gs.tok;
-                uint2 hv[16];
-#pragma unroll
-                for (int j = 0; j < 16; ++j) hv[j] = ld8(gs.tabs[j] + (size_t)tk[j] * H + 4 * t);
-                const int fr = gs.frame[0];
-                const float *extra = fr < gs.tr_len[0] ? gs.tr + (size_t)fr * H : gs.pad;
-                const float4 ex = ldf4(extra + 4 * t);
-                auto h4 = [](uint2 u) { return make_float4(h2f(u.x & 0xffff), h2f(u.x >> 16), h2f(u.y & 0xffff), h2f(u.y >> 16)); };
-                x = h4(hv[0]);
-#pragma unroll
-                for (int j = 1; j < 16; ++j) { const float4 b = h4(hv[j]); x = make_float4(x.x + b.x, x.y + b.y, x.z + b.z, x.w + b.w); }
-                x = make_float4(x.x + ex.x, x.y + ex.y, x.z + ex.z, x.w + ex.w);
-            } else if (MODE == 0 || pass == 0) {
+            if (MODE == 0) {
+                x = pdev::gather_x4(p);   // x_in or the step-embedding gather
+            } else if (pass == 0) {
                 x = ldf4(p.x_in + 4 * t);
             } else {   // code-predictor pass input: table row of the previous pass's token (pass 1: CB0)
                 int tok = p.gs.tok[0];

@@ -25,6 +25,10 @@
 // issued right after its phase for the next layer, a whole layer before they are needed.  Layer 0 of passes 1..15
 // reads its raw QKV row from the per-token table (Engine::build_cp_qkv_table); pass 0's last layer stops after its
 // K/V append (no head consumes its output).
+//
+// The QKV, head-row, gate/up and down bodies are persist_roles.h's, shared with persist_tk.hip; this file keeps the
+// role map, the 16 x 5 loop nest with pass 0's skipped last layer, each phase's input wait (gx / gx2), the O role
+// (a wave K slice + residual), the attention and the selection.
 #include "persist.h"
 #include "persist_dev.h"
 #ifdef Q3T_DEV
@@ -39,6 +43,7 @@ namespace q3t { __device__ uint64_t *g_selprof = nullptr; }
 #include "select.h"
 
 #pragma clang fp contract(off)   // every rounding as written: bit-identical to k_gemv / k_attn / k_persist
+#include "persist_roles.h"       // (after the pragma: the shared bodies round as written too)
 
 #ifndef Q3T_CP_SGATE   // the selection's logits poll behind the same one-lane gate
 #define Q3T_CP_SGATE 1
@@ -68,9 +73,9 @@ namespace q3t { __device__ uint64_t *g_selprof = nullptr; }
 namespace q3t {
 
 namespace {
-using namespace pdev;
+using namespace prole;
 
-constexpr int H = 1024, NH = 16, NKV = 8, D = 128, QKVN = (NH + 2 * NKV) * D, INTER = 3072, VOC = 3072, CPV = 2048;
+constexpr int VOC = 3072, CPV = 2048;
 constexpr int G = 256, NLC = 5, NPASS = 16, PPH = 5 * NLC + 1, MMS = Q3T_CP_MMS;
 constexpr int QW = 0, NQ = 64;      // QKV rows 64 (4 x 16) of 4096; lm_head rows 32 (2 x 16) of 2048
 constexpr int AW = 64, NA = 8;      // attention of kv group w - AW, token selection
@@ -99,52 +104,31 @@ struct CLds {
     const uint16_t *tabs[16];
 };
 
-struct Ctx {
-    const PersistParams &p;
-    CLds &S;
-    Ctl c;
-    unsigned seq;
-    __device__ uint32_t tag(int ph) const { return ((seq * 1024u + (unsigned)ph) << 1) | 1u; }
+using Ctx = RoleCtx<CLds>;
+struct Pol {   // persist_roles.h's policy
+    static constexpr bool WPUB = Q3T_CP_WPUB, PUT_FIRST = Q3T_CP_PUT_FIRST, GATE = Q3T_CP_GATE;
+    template <int N>
+    static __device__ __forceinline__ void wait(const uint64_t *g, uint32_t tag, uint32_t (&u)[N], Ctl &c) { Q3T_CP_WAIT<N>(g, tag, u, c); }
 };
 
-#define PROF(ph, k)                                                                                           \
-    do {                                                                                                      \
-        if (X.p.prof && threadIdx.x == 0 && blockIdx.x < PROF_WG) X.p.prof[((size_t)blockIdx.x * PROF_PH + (ph)) * 4 + (k)] = wall_clock64(); \
-    } while (0)
-
 __device__ __forceinline__ int ph_of(int pass, int l, int k) { return pass * PPH + 5 * l + k; }
+// the layer an O / gate-up / down workgroup runs after (pass, l), whose weights it issues next: pass 0 skips its last
+// layer; -1 after the frame's last phase
+__device__ __forceinline__ int next_layer(int pass, int l) {
+    if (pass + 1 == NPASS && l + 1 == NLC) return -1;
+    return (l + 1 < NLC && !(pass == 0 && l + 1 == NLC - 1)) ? l + 1 : 0;
+}
 
 // ------------------------------------------------------------------ QKV rows (+ lm_head after the last layer)
 __device__ __forceinline__ void role_qkv(Ctx &X) {
     const PersistParams &p = X.p;
     CLds &S = X.S;
-    const int i = blockIdx.x - QW, t = threadIdx.x, l16 = t & 15, grp = t >> 4;
+    const int i = blockIdx.x - QW, t = threadIdx.x, grp = t >> 4;
     const float temp = p.sel.temperature;
     const bool samp = temp > 0.0f && Q3T_CP_RANGE;
     uint4 wq[4][8];
     float4 nw;
-    auto issue_qkv = [&](int l) {
-        const uint16_t *W = S.layers[l].qkv;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            // Q3T_CP_WPUB: wave w owns rows 16w .. 16w + 15 (row 16w + 4j + lane / 16) and publishes them itself
-            const int row = Q3T_CP_WPUB ? 16 * (t >> 6) + 4 * j + (grp & 3) : 16 * j + grp;
-            const uint16_t *r = W + (size_t)(64 * i + row) * H + l16 * 8;
-#pragma unroll
-            for (int tt = 0; tt < 8; ++tt) wq[j][tt] = ld16(r + tt * 128);
-        }
-        nw = ldf4(S.layers[l].attn_norm + 4 * t);
-    };
-    auto issue_head = [&](int pass) {   // lm_head[pass - 1]: rows 32i + 16j + grp
-        const uint16_t *W = S.heads[pass - 1];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const uint16_t *r = W + (size_t)(32 * i + 16 * j + grp) * H + l16 * 8;
-#pragma unroll
-            for (int tt = 0; tt < 8; ++tt) wq[j][tt] = ld16(r + tt * 128);
-        }
-        nw = ldf4(p.out_norm + 4 * t);
-    };
+    auto issue_qkv = [&](int l) { qkv_issue<Pol>(S.layers[l].qkv, S.layers[l].attn_norm, i, wq, nw); };
     issue_qkv(0);
     for (int pass = 0; pass < NPASS; ++pass) {
         for (int l = pass == 0 ? 0 : 1; l < NLC; ++l) {
@@ -155,73 +139,31 @@ __device__ __forceinline__ void role_qkv(Ctx &X) {
             } else {
                 uint32_t u[4];
                 PROF(ph, 0);
-                if (Q3T_CP_GATE) g_gate(p.gx + 4 * t, X.tag(ph_of(pass, l - 1, 4)), X.c);
-                Q3T_CP_WAIT<4>(p.gx + 4 * t, X.tag(ph_of(pass, l - 1, 4)), u, X.c);
+                wait_in<Pol, 4>(X, p.gx + 4 * t, X.tag(ph_of(pass, l - 1, 4)), u);
                 PROF(ph, 1);
                 x = f4_of(u);
             }
-            rms_to_f16(x, nw, p.eps, S.xs, S.dscr, nullptr);
-            __syncthreads();
-            float acc[4];
+            qkv_phase<Pol>(X, i, x, wq, nw, ph);
+            if (l + 1 < NLC) {
+                issue_qkv(l + 1);
+            } else if (pass >= 1) {   // lm_head[pass - 1]: rows 32i + 16j + grp
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc[j] = 0.0f;
-#pragma unroll
-                for (int tt = 0; tt < 8; ++tt) acc[j] = dot8(wq[j][tt], *reinterpret_cast<const uint4 *>(S.xs + l16 * 8 + tt * 128), acc[j]);
-            }
-            if constexpr (Q3T_CP_WPUB) {
-                // each wave publishes its 16 rows as one whole line: lane L < 16 takes row 4j + g (j = L / 4, g = L % 4)
-                // from lane 16 g of the group that reduced it (the l16 == 0 lane, as the LDS form), no barrier
-                float pv = 0.0f;
-                const int lane = t & 63;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float v = __shfl(group_sum<16>(acc[j]), 16 * (lane & 3));
-                    if ((lane >> 2) == j) pv = v;
-                }
-                if (lane < 16) g_put(p.gqkv + 64 * i + 16 * (t >> 6) + lane, __float_as_uint(pv), X.tag(ph));
+                for (int j = 0; j < 2; ++j) issue_row(S.heads[pass - 1], 32 * i + 16 * j + grp, wq[j]);
+                nw = ldf4(p.out_norm + 4 * t);
             } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc[j] = group_sum<16>(acc[j]);
-                    if (l16 == 0) S.outv[16 * j + grp] = acc[j];
-                }
-                __syncthreads();
-                // one store instruction of wave 0 publishes the 64 rows (4 whole lines): single-lane stores from four
-                // waves into shared lines make the next edge slower
-                if (t < 64) g_put(p.gqkv + 64 * i + t, __float_as_uint(S.outv[t]), X.tag(ph));
+                issue_qkv(1);   // pass 0 has no head; layer 0 of the next passes comes from the table
             }
-            PROF(ph, 2);
-            if (Q3T_CP_PUT_FIRST) __syncthreads();   // the publish store enters the CU's memory pipe before the prefetch
-            if (l + 1 < NLC) issue_qkv(l + 1);
-            else if (pass >= 1) issue_head(pass);
-            else issue_qkv(1);   // pass 0 has no head; layer 0 of the next passes comes from the table
         }
         if (pass == 0) continue;
         // ---- head: RMSNorm(output_norm) -> lm_head[pass - 1] logits (granules for the selecting workgroups)
         const int hph = ph_of(pass, NLC, 0);
         uint32_t u[4];
         PROF(hph, 0);
-        if (Q3T_CP_GATE) g_gate(p.gx + 4 * t, X.tag(ph_of(pass, NLC - 1, 4)), X.c);
-        Q3T_CP_WAIT<4>(p.gx + 4 * t, X.tag(ph_of(pass, NLC - 1, 4)), u, X.c);
+        wait_in<Pol, 4>(X, p.gx + 4 * t, X.tag(ph_of(pass, NLC - 1, 4)), u);
         PROF(hph, 1);
         rms_to_f16(f4_of(u), nw, p.eps, S.xs, S.dscr, nullptr);
         __syncthreads();
-        float a0[2], a1[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            a0[j] = 0.0f;
-            a1[j] = 0.0f;
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) a0[j] = dot8(wq[j][tt], *reinterpret_cast<const uint4 *>(S.xs + l16 * 8 + tt * 128), a0[j]);
-#pragma unroll
-            for (int tt = 4; tt < 8; ++tt) a1[j] = dot8(wq[j][tt], *reinterpret_cast<const uint4 *>(S.xs + l16 * 8 + tt * 128), a1[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const float lg = group_sum<16>(a0[j]) + group_sum<16>(a1[j]);
-            if (l16 == 0) S.outv[16 * j + grp] = lg;
-        }
+        head_rows<2>(X, wq);
         __syncthreads();
         PROF(hph, 3);   // (development timeline: head rows reduced)
         if (t < 64) {   // wave 0, ONE store instruction: lanes 0..31 publish the rows, lanes 32 / 33 (sampling) their max
@@ -236,8 +178,7 @@ __device__ __forceinline__ void role_qkv(Ctx &X) {
                       __float_as_uint(t < 32 ? sv : t == 32 ? mx : mn), X.tag(hph));
             if (t < 32) p.logits[32 * i + t] = lg;   // read after the launch only (host, tests)
         }
-        PROF(hph, 2);
-        if (Q3T_CP_PUT_FIRST) __syncthreads();
+        published<Pol>(X, hph);
         if (pass + 1 < NPASS) issue_qkv(1);
     }
 }
@@ -488,8 +429,7 @@ __device__ __forceinline__ void role_o(Ctx &X) {
             }
             uint32_t u[4];
             PROF(ph, 0);
-            if (Q3T_CP_GATE) g_gate(p.gattn + 4 * t, X.tag(ph_of(pass, l, 1)), X.c);
-            Q3T_CP_WAIT<4>(p.gattn + 4 * t, X.tag(ph_of(pass, l, 1)), u, X.c);
+            wait_in<Pol, 4>(X, p.gattn + 4 * t, X.tag(ph_of(pass, l, 1)), u);
             PROF(ph, 1);
             *reinterpret_cast<uint4 *>(S.xs + 8 * t) = make_uint4(u[0], u[1], u[2], u[3]);
             wave_lds_sync();   // wave w polled exactly the K slice [512 w, 512 w + 512) it multiplies
@@ -512,10 +452,8 @@ __device__ __forceinline__ void role_o(Ctx &X) {
                 const float s = rd[0][t] + rd[1][t] + rd[2][t] + rd[3][t];
                 g_put(p.gx2 + 32 * i + t, __float_as_uint(S.xr[t] + s), X.tag(ph));
             }
-            PROF(ph, 2);
-            if (Q3T_CP_PUT_FIRST) __syncthreads();
-            const int nl = (l + 1 < NLC && !(pass == 0 && l + 1 == NLC - 1)) ? l + 1 : 0;
-            if (!(pass + 1 == NPASS && l + 1 == NLC)) issue(nl);
+            published<Pol>(X, ph);
+            if (next_layer(pass, l) >= 0) issue(next_layer(pass, l));
         }
     }
 }
@@ -524,63 +462,21 @@ __device__ __forceinline__ void role_o(Ctx &X) {
 __device__ __forceinline__ void role_gu(Ctx &X) {
     const PersistParams &p = X.p;
     CLds &S = X.S;
-    const int i = blockIdx.x - UW, t = threadIdx.x, l16 = t & 15, grp = t >> 4;
+    const int i = blockIdx.x - UW, t = threadIdx.x;
     uint4 wg[2][8], wu[2][8];
     float4 nw;
-    auto issue = [&](int l) {   // unit 32i + 16j + grp: gate row, up row 16 below (16-row interleaved blocks)
-        const uint16_t *W = S.layers[l].gu;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int unit = 32 * i + 16 * j + grp;
-            const uint16_t *r = W + (size_t)((unit >> 4) * 32 + (unit & 15)) * H + l16 * 8;
-#pragma unroll
-            for (int tt = 0; tt < 8; ++tt) wg[j][tt] = ld16(r + tt * 128);
-#pragma unroll
-            for (int tt = 0; tt < 8; ++tt) wu[j][tt] = ld16(r + 16 * H + tt * 128);
-        }
-        nw = ldf4(S.layers[l].ffn_norm + 4 * t);
-    };
-    issue(0);
+    gu_issue(S.layers[0].gu, S.layers[0].ffn_norm, i, wg, wu, nw);
     for (int pass = 0; pass < NPASS; ++pass) {
         for (int l = 0; l < NLC; ++l) {
             if (pass == 0 && l == NLC - 1) continue;
             const int ph = ph_of(pass, l, 3);
             uint32_t u[4];
             PROF(ph, 0);
-            if (Q3T_CP_GATE) g_gate(p.gx2 + 4 * t, X.tag(ph_of(pass, l, 2)), X.c);
-            Q3T_CP_WAIT<4>(p.gx2 + 4 * t, X.tag(ph_of(pass, l, 2)), u, X.c);
+            wait_in<Pol, 4>(X, p.gx2 + 4 * t, X.tag(ph_of(pass, l, 2)), u);
             PROF(ph, 1);
-            rms_to_f16(f4_of(u), nw, p.eps, S.xs, S.dscr, nullptr);
-            __syncthreads();
-            float a0[2], a1[2], b0[2], b1[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                a0[j] = a1[j] = b0[j] = b1[j] = 0.0f;
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) {
-                    const uint4 xv = *reinterpret_cast<const uint4 *>(S.xs + l16 * 8 + tt * 128);
-                    a0[j] = dot8(wg[j][tt], xv, a0[j]);
-                    b0[j] = dot8(wu[j][tt], xv, b0[j]);
-                }
-#pragma unroll
-                for (int tt = 4; tt < 8; ++tt) {
-                    const uint4 xv = *reinterpret_cast<const uint4 *>(S.xs + l16 * 8 + tt * 128);
-                    a1[j] = dot8(wg[j][tt], xv, a1[j]);
-                    b1[j] = dot8(wu[j][tt], xv, b1[j]);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float ga = group_sum<16>(a0[j]) + group_sum<16>(a1[j]);
-                const float ub = group_sum<16>(b0[j]) + group_sum<16>(b1[j]);
-                if (l16 == 0) S.hs[16 * j + grp] = silu_f(ga) * ub;
-            }
-            __syncthreads();
-            if (t < 16) g_put(p.gh + 16 * i + t, (uint32_t)f2h(S.hs[2 * t]) | ((uint32_t)f2h(S.hs[2 * t + 1]) << 16), X.tag(ph));
-            PROF(ph, 2);
-            if (Q3T_CP_PUT_FIRST) __syncthreads();
-            const int nl = (l + 1 < NLC && !(pass == 0 && l + 1 == NLC - 1)) ? l + 1 : 0;
-            if (!(pass + 1 == NPASS && l + 1 == NLC)) issue(nl);
+            gu_phase<Pol>(X, i, f4_of(u), wg, wu, nw, ph);
+            const int nl = next_layer(pass, l);
+            if (nl >= 0) gu_issue(S.layers[nl].gu, S.layers[nl].ffn_norm, i, wg, wu, nw);
         }
     }
 }
@@ -589,62 +485,22 @@ __device__ __forceinline__ void role_gu(Ctx &X) {
 __device__ __forceinline__ void role_dn(Ctx &X) {
     const PersistParams &p = X.p;
     CLds &S = X.S;
-    const int i = blockIdx.x - DW, t = threadIdx.x, lane = t & 63, wave = t >> 6, l16 = t & 15, grp4 = lane >> 4;
+    const int i = blockIdx.x - DW, t = threadIdx.x;
     const int lo = i * H / ND, n = (i + 1) * H / ND - lo;
     uint4 wd[5][6];
-    auto issue = [&](int l) {   // row lo + 4j + grp4 (clamped: rows past n re-read row lo + n - 1), K slice = wave
-        const uint16_t *W = S.layers[l].down;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const uint16_t *r = W + (size_t)(lo + min(4 * j + grp4, n - 1)) * INTER + wave * 768 + l16 * 8;
-#pragma unroll
-            for (int tt = 0; tt < 6; ++tt) wd[j][tt] = ld16(r + tt * 128);
-        }
-    };
-    issue(0);
+    dn_issue(S.layers[0].down, lo, n, wd);
     int it = 0;   // phase executions: the parity of S.red
     for (int pass = 0; pass < NPASS; ++pass) {
         for (int l = 0; l < NLC; ++l) {
             if (pass == 0 && l == NLC - 1) continue;
-            const int par = it++ & 1;
-            const int ph = ph_of(pass, l, 4);
             if (t < n) {   // the residual rows x'_l (published a phase earlier)
                 uint32_t u1[1];
                 g_wait<1>(p.gx2 + lo + t, X.tag(ph_of(pass, l, 2)), u1, X.c);
                 S.xr[t] = __uint_as_float(u1[0]);
             }
-            uint32_t u[6];
-            PROF(ph, 0);
-            if (Q3T_CP_GATE) g_gate(p.gh + 6 * t, X.tag(ph_of(pass, l, 3)), X.c);
-            Q3T_CP_WAIT<6>(p.gh + 6 * t, X.tag(ph_of(pass, l, 3)), u, X.c);
-            PROF(ph, 1);
-            *reinterpret_cast<uint2 *>(S.xs + 12 * t) = make_uint2(u[0], u[1]);
-            *reinterpret_cast<uint2 *>(S.xs + 12 * t + 4) = make_uint2(u[2], u[3]);
-            *reinterpret_cast<uint2 *>(S.xs + 12 * t + 8) = make_uint2(u[4], u[5]);
-            wave_lds_sync();   // wave w polled exactly the K slice [768 w, 768 w + 768) it multiplies
-            float acc[5];
-#pragma unroll
-            for (int j = 0; j < 5; ++j) {
-                acc[j] = 0.0f;
-#pragma unroll
-                for (int tt = 0; tt < 6; ++tt)
-                    acc[j] = dot8(wd[j][tt], *reinterpret_cast<const uint4 *>(S.xs + wave * 768 + l16 * 8 + tt * 128), acc[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < 5; ++j) {
-                acc[j] = group_sum<16>(acc[j]);
-                if (l16 == 0) S.red[par][wave][4 * j + grp4] = acc[j];
-            }
-            __syncthreads();
-            if (t < n) {
-                const float (&rd)[4][32] = S.red[par];
-                const float s = rd[0][t] + rd[1][t] + rd[2][t] + rd[3][t];
-                g_put(p.gx + lo + t, __float_as_uint(S.xr[t] + s), X.tag(ph));
-            }
-            PROF(ph, 2);
-            if (Q3T_CP_PUT_FIRST) __syncthreads();
-            const int nl = (l + 1 < NLC && !(pass == 0 && l + 1 == NLC - 1)) ? l + 1 : 0;
-            if (!(pass + 1 == NPASS && l + 1 == NLC)) issue(nl);
+            dn_phase<Pol>(X, lo, n, it++ & 1, wd, ph_of(pass, l, 4));
+            const int nl = next_layer(pass, l);
+            if (nl >= 0) dn_issue(S.layers[nl].down, lo, n, wd);
         }
     }
 }

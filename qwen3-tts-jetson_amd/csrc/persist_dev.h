@@ -1,14 +1,22 @@
-// persist_dev.h — device helpers shared by the persistent kernels (persist.hip: the talker step and the 1.7B /
-// fallback code-predictor frame; persist_cp.hip: the role-specialised code-predictor frame): global loads that never
+// persist_dev.h — device helpers shared by every persistent kernel (persist.hip: the all-role talker step and the
+// 1.7B / fallback code-predictor frame; persist_tk.hip / persist_cp.hip through persist_roles.h: the role-specialised
+// step and frame; persist_cpb.hip / persist_tkb.hip through persist_mm.h: the batched ones): global loads that never
 // lower to flat loads, the {payload, tag} granule hand-off (one 8-byte agent-scope store, polled with agent-scope
-// loads until every tag matches; MI355X_MICROARCH.md hand-off rows), the bounded wait and the RMSNorm prologue.
+// loads until every tag matches; MI355X_MICROARCH.md hand-off rows), the bounded wait with its one give-up check, the
+// RMSNorm prologue and the talker step's embedding gather.
+// This header comes before its includers' `#pragma clang fp contract(off)` (select.h, which follows it, is compiled
+// with the default), so it sets no file-scope pragma: the gather's sums carry the pragma in their own bodies, and
+// rms_to_f16 has no multiply that feeds an add.
 #pragma once
-#include "kernels.h"
+#include "persist.h"
 
 namespace q3t {
 namespace pdev {
 
 constexpr unsigned SPIN_LIMIT = 1u << 21;   // polls before a hand-off wait gives up (sets *err)
+#ifndef Q3T_POLL_SLEEP
+#define Q3T_POLL_SLEEP 1
+#endif
 
 template <class V>
 __device__ __forceinline__ V ldgv(const void *p) {
@@ -48,6 +56,17 @@ struct Ctl {
     unsigned *err;
     bool abort;
 };
+// The give-up check of every bounded wait, called once per poll that did not find its tags: every 256th poll reads
+// *err, and after SPIN_LIMIT polls (or once any workgroup has flagged a timeout) the wait must stop: true, with
+// c.abort and *err set, and the launch drains.
+__device__ __forceinline__ bool give_up(Ctl &c, unsigned &it) {
+    if ((++it & 255u) == 0 && (__hip_atomic_load(c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || it >= SPIN_LIMIT)) {
+        c.abort = true;
+        __hip_atomic_fetch_or(c.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return true;
+    }
+    return false;
+}
 
 // spin until granules base[(i / RUN) * STRIDE + i % RUN], i in [0, N), all carry `tag`; payloads to out.  Bounded:
 // after SPIN_LIMIT polls (or once any workgroup has flagged a timeout) the wait gives up, sets *err and lets the launch
@@ -63,17 +82,7 @@ __device__ __forceinline__ void g_wait(const uint64_t *base, uint32_t tag, uint3
 #pragma unroll
         for (int i = 0; i < N; ++i) ok &= (uint32_t)(v[i] >> 32) == tag;
         if (ok || c.abort) break;
-        ++it;
-        if ((it & 255u) == 0) {
-            if (__hip_atomic_load(c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || it >= SPIN_LIMIT) {
-                c.abort = true;
-                __hip_atomic_fetch_or(c.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
-#ifndef Q3T_POLL_SLEEP
-#define Q3T_POLL_SLEEP 1
-#endif
+        if (give_up(c, it)) break;
         if constexpr (Q3T_POLL_SLEEP > 0) __builtin_amdgcn_s_sleep(Q3T_POLL_SLEEP);
     }
 #pragma unroll
@@ -124,14 +133,7 @@ __device__ __forceinline__ void g_wait16(const uint64_t *base, uint32_t tag, uin
 #pragma unroll
         for (int m = 0; m < M; ++m) ok &= r[m].y == tag && r[m].w == tag;
         if (ok || c.abort) break;
-        ++it;
-        if ((it & 255u) == 0) {
-            if (__hip_atomic_load(c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || it >= SPIN_LIMIT) {
-                c.abort = true;
-                __hip_atomic_fetch_or(c.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
+        if (give_up(c, it)) break;
         if constexpr (Q3T_POLL_SLEEP > 0) __builtin_amdgcn_s_sleep(Q3T_POLL_SLEEP);
     }
 #pragma unroll
@@ -159,14 +161,7 @@ __device__ __forceinline__ void g_wait16_pair(const uint64_t *a, const uint64_t 
 #pragma unroll
         for (int m = 0; m < M; ++m) ok &= r[m].y == tag && r[m].w == tag;
         if (ok || c.abort) break;
-        ++it;
-        if ((it & 255u) == 0) {
-            if (__hip_atomic_load(c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || it >= SPIN_LIMIT) {
-                c.abort = true;
-                __hip_atomic_fetch_or(c.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
+        if (give_up(c, it)) break;
         if constexpr (Q3T_POLL_SLEEP > 0) __builtin_amdgcn_s_sleep(Q3T_POLL_SLEEP);
     }
 #pragma unroll
@@ -196,14 +191,7 @@ __device__ __forceinline__ void g_wait_pair(const uint64_t *a, const uint64_t *b
 #pragma unroll
         for (int i = 0; i < N + M; ++i) ok &= (uint32_t)(v[i] >> 32) == tag;
         if (ok || c.abort) break;
-        ++it;
-        if ((it & 255u) == 0) {
-            if (__hip_atomic_load(c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || it >= SPIN_LIMIT) {
-                c.abort = true;
-                __hip_atomic_fetch_or(c.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
+        if (give_up(c, it)) break;
         if constexpr (Q3T_POLL_SLEEP > 0) __builtin_amdgcn_s_sleep(Q3T_POLL_SLEEP);
     }
 #pragma unroll
@@ -219,11 +207,7 @@ __device__ __forceinline__ void g_gate(const uint64_t *g, uint32_t tag, Ctl &c) 
     if ((threadIdx.x & 63) == 0) {
         unsigned it = 0;
         while (!c.abort && (uint32_t)(g_ld(g) >> 32) != tag) {
-            if ((++it & 255u) == 0 && (__hip_atomic_load(c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
-                                       it >= SPIN_LIMIT)) {
-                c.abort = true;
-                __hip_atomic_fetch_or(c.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            give_up(c, it);   // sets c.abort, which the loop condition reads
             __builtin_amdgcn_s_sleep(1);
         }
     }
@@ -279,6 +263,43 @@ __device__ __forceinline__ void rms_to_f16(float4 x, float4 w, float eps, uint16
     h.x = (uint32_t)f2h(y0) | ((uint32_t)f2h(y1) << 16);
     h.y = (uint32_t)f2h(y2) | ((uint32_t)f2h(y3) << 16);
     *reinterpret_cast<uint2 *>(xs + 4 * t) = h;
+}
+
+// The talker step's layer-0 input: p.x_in, or with p.gather the step embedding, the 16 embedding-table rows of the
+// frame's tokens summed in table order ((t0 + t1) + t2 ...) plus the trailing-text row (or the pad row).  gather_x4
+// gives thread t's elements 4t..4t+3 (k_persist<0, *>, the QKV and gate/up roles of k_tk_roles), layer0_x1 one element
+// (the down role's residual rows): every consumer must see the same bits, so both sum in this one order.
+__device__ __forceinline__ float4 gather_x4(const PersistParams &p) {
+#pragma clang fp contract(off)
+    const int t = threadIdx.x;
+    if (!p.gather) return ldf4(p.x_in + 4 * t);
+    const GatherSum &gs = p.gs;
+    uint2 hv[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) hv[j] = ld8(gs.tabs[j] + (size_t)gs.tok[j] * 1024 + 4 * t);
+    const int fr = gs.frame[0];
+    const float *extra = fr < gs.tr_len[0] ? gs.tr + (size_t)fr * 1024 : gs.pad;
+    const float4 ex = ldf4(extra + 4 * t);
+    auto h4 = [](uint2 u) { return make_float4(h2f(u.x & 0xffff), h2f(u.x >> 16), h2f(u.y & 0xffff), h2f(u.y >> 16)); };
+    float4 x = h4(hv[0]);
+#pragma unroll
+    for (int j = 1; j < 16; ++j) { const float4 b = h4(hv[j]); x = make_float4(x.x + b.x, x.y + b.y, x.z + b.z, x.w + b.w); }
+    return make_float4(x.x + ex.x, x.y + ex.y, x.z + ex.z, x.w + ex.w);
+}
+__device__ __forceinline__ float layer0_x1(const PersistParams &p, int e) {
+#pragma clang fp contract(off)
+    if (!p.gather) return p.x_in[e];
+    const GatherSum &gs = p.gs;
+    uint16_t hv[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) hv[j] = gs.tabs[j][(size_t)gs.tok[j] * 1024 + e];
+    const int fr = gs.frame[0];
+    const float *extra = fr < gs.tr_len[0] ? gs.tr + (size_t)fr * 1024 : gs.pad;
+    const float ex = extra[e];
+    float x = h2f(hv[0]);
+#pragma unroll
+    for (int j = 1; j < 16; ++j) x = x + h2f(hv[j]);
+    return x + ex;
 }
 
 }  // namespace pdev

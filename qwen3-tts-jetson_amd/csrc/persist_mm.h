@@ -78,14 +78,7 @@ __device__ __forceinline__ void wait_flags(Ctx &X, int kind, int n, Idx idx, uin
         if (lane < n) ok &= __hip_atomic_load(fa, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == tag;
         if (lane + 64 < n) ok &= __hip_atomic_load(fb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == tag;
         if (__all(ok) || X.c.abort) break;
-        ++it;
-        if ((it & 255u) == 0) {
-            if (__hip_atomic_load(X.c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || it >= SPIN_LIMIT) {
-                X.c.abort = true;
-                __hip_atomic_fetch_or(X.c.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
+        if (give_up(X.c, it)) break;
         __builtin_amdgcn_s_sleep(1);
     }
     __atomic_signal_fence(__ATOMIC_SEQ_CST);   // the payload loads stay behind the poll
@@ -133,11 +126,7 @@ __device__ __forceinline__ void poll_gran(Ctx &X, uint32_t tag, u32x4_t (&r)[M],
 #pragma unroll
             for (int m = 0; m < M; ++m) ok &= r[m].y == tag && r[m].w == tag;
             if (ok || X.c.abort) break;
-            if ((++it & 255u) == 0 && (__hip_atomic_load(X.c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || it >= SPIN_LIMIT)) {
-                X.c.abort = true;
-                __hip_atomic_fetch_or(X.c.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
+            if (give_up(X.c, it)) break;
             __builtin_amdgcn_s_sleep(1);
         }
     }
@@ -149,14 +138,7 @@ __device__ __forceinline__ void poll_gran(Ctx &X, uint32_t tag, u32x4_t (&r)[M],
 #pragma unroll
         for (int m = 0; m < M; ++m) ok &= r[m].y == tag && r[m].w == tag;
         if (__all(ok) || X.c.abort) break;
-        ++it;
-        if ((it & 255u) == 0) {
-            if (__hip_atomic_load(X.c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || it >= SPIN_LIMIT) {
-                X.c.abort = true;
-                __hip_atomic_fetch_or(X.c.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
+        if (give_up(X.c, it)) break;
         __builtin_amdgcn_s_sleep(1);
     }
 }

@@ -30,6 +30,10 @@
 // graph and to k_persist<0, 64> (tests/test_gpu_persist.py).  Every row keeps the per-op GEMVs' lane split and
 // reduction order.  Each workgroup holds only its role's weights (<= 160 VGPRs) or K/V rows, issued right after its
 // phase for the next layer.  Contexts longer than 64 x 32 positions use k_persist<0, CH>.
+//
+// The QKV, head-row, gate/up and down bodies are persist_roles.h's, shared with persist_cp.hip; this file keeps the
+// role map, the one pass over the layers, each phase's input row (the four O K-slice partials summed onto the residual),
+// the O role with its split combine, the attention and the selection.
 #include "persist.h"
 #include "persist_dev.h"
 #include "select.h"
@@ -37,13 +41,14 @@
 #include <algorithm>
 
 #pragma clang fp contract(off)   // every rounding as written: bit-identical to k_gemv / k_attn / k_persist
+#include "persist_roles.h"       // (after the pragma: the shared bodies round as written too)
 
 namespace q3t {
 
 namespace {
-using namespace pdev;
+using namespace prole;
 
-constexpr int H = 1024, NH = 16, NKV = 8, D = 128, QKVN = (NH + 2 * NKV) * D, INTER = 3072, VOC = 3072;
+constexpr int VOC = 3072;
 constexpr int R = NH / NKV, CHK = 64, PSLOT = 264, MAXCH = 32;   // chunk of positions; partial granules; gpart slots
 // Workgroups b and b + 256 share a CU (observed dispatch, tools/dev/cuprobe.hip; speed only, never correctness): the
 // attention splits >= 1 (workgroups 256..) sit beside the down workgroups, then (splits >= 8) the O workgroups.  The
@@ -85,7 +90,6 @@ constexpr int MAXL = 32;
 static_assert(NO + NU + ND + NQ == AW && QW + NQ == AW, "roles");
 static_assert(NQ * 64 == QKVN && NQ * 48 == VOC && NU * 32 == INTER && NO * 32 == H && ND * 19 >= H, "role rows");
 
-template <int CPW>
 struct TLds {
     uint16_t xs[INTER];
     float xr[32];
@@ -95,136 +99,49 @@ struct TLds {
     float hs[32];
     // attention
     float q_s[R][D], kn_s[D], vn_s[D];
-    float wred[4][CPW][R], wsum[4][CPW][R];   // per-wave softmax max / sum per chunk
-    float mch[CPW][R], lch[CPW][R];   // per-chunk max / sum (split partials)
-    float ared[4][CPW][R][D];
+    float wred[4][R], wsum[4][R];   // per-wave softmax max / sum of the chunk
+    float mch[R], lch[R];           // the chunk's max / sum (split partials)
+    float ared[4][R][D];
     SelLds sel;
     PLayerW layers[MAXL];
 };
+static_assert(sizeof(TLds) == 33808, "the launch's LDS request (two workgroups per CU): unchanged since the chunks-per-workgroup template went");
 
-template <int CPW>
-struct Ctx {
-    const PersistParams &p;
-    TLds<CPW> &S;
-    Ctl c;
-    unsigned seq;
+struct Ctx : RoleCtx<TLds> {
     int pos, nl;
-    __device__ uint32_t tag(int ph) const { return ((seq * 1024u + (unsigned)ph) << 1) | 1u; }
+};
+struct Pol {   // persist_roles.h's policy: the talker's polls are always gated and sweep with g_waitc
+    static constexpr bool WPUB = Q3T_TK_WPUB, PUT_FIRST = Q3T_TK_PUT_FIRST, GATE = true;
+    template <int N>
+    static __device__ __forceinline__ void wait(const uint64_t *g, uint32_t tag, uint32_t (&u)[N], Ctl &c) { g_waitc<N>(g, tag, u, c); }
 };
 
-#define PROF(ph, k)                                                                                           \
-    do {                                                                                                      \
-        if (X.p.prof && threadIdx.x == 0 && blockIdx.x < PROF_WG) X.p.prof[((size_t)blockIdx.x * PROF_PH + (ph)) * 4 + (k)] = wall_clock64(); \
-    } while (0)
-
-// x rows 4t..4t+3 of the layer-0 input (k_persist<0,*>'s prologue, same summation order)
-__device__ __forceinline__ float4 layer0_x4(const PersistParams &p) {
-    const int t = threadIdx.x;
-    if (!p.gather) return ldf4(p.x_in + 4 * t);
-    const GatherSum &gs = p.gs;
-    uint2 hv[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) hv[j] = ld8(gs.tabs[j] + (size_t)gs.tok[j] * H + 4 * t);
-    const int fr = gs.frame[0];
-    const float *extra = fr < gs.tr_len[0] ? gs.tr + (size_t)fr * H : gs.pad;
-    const float4 ex = ldf4(extra + 4 * t);
-    auto h4 = [](uint2 u) { return make_float4(h2f(u.x & 0xffff), h2f(u.x >> 16), h2f(u.y & 0xffff), h2f(u.y >> 16)); };
-    float4 x = h4(hv[0]);
-#pragma unroll
-    for (int j = 1; j < 16; ++j) { const float4 b = h4(hv[j]); x = make_float4(x.x + b.x, x.y + b.y, x.z + b.z, x.w + b.w); }
-    return make_float4(x.x + ex.x, x.y + ex.y, x.z + ex.z, x.w + ex.w);
-}
-// one element of the same (the O workgroups' residual rows): identical per-element summation order
-__device__ __forceinline__ float layer0_x1(const PersistParams &p, int e) {
-    if (!p.gather) return p.x_in[e];
-    const GatherSum &gs = p.gs;
-    uint16_t hv[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) hv[j] = gs.tabs[j][(size_t)gs.tok[j] * H + e];
-    const int fr = gs.frame[0];
-    const float *extra = fr < gs.tr_len[0] ? gs.tr + (size_t)fr * H : gs.pad;
-    const float ex = extra[e];
-    float x = h2f(hv[0]);
-#pragma unroll
-    for (int j = 1; j < 16; ++j) x = x + h2f(hv[j]);
-    return x + ex;
-}
-
 // ------------------------------------------------------------------ QKV rows (+ codec head after the last layer)
-template <int CPW>
-__device__ __forceinline__ void tk_qkv(Ctx<CPW> &X) {
+__device__ __forceinline__ void tk_qkv(Ctx &X) {
     const PersistParams &p = X.p;
-    TLds<CPW> &S = X.S;
-    const int i = blockIdx.x - QW, t = threadIdx.x, l16 = t & 15, grp = t >> 4, nl = X.nl;
+    TLds &S = X.S;
+    const int i = blockIdx.x - QW, t = threadIdx.x, grp = t >> 4, nl = X.nl;
     uint4 wq[4][8];
     float4 nw;
-    auto issue_qkv = [&](int l) {
-        const uint16_t *W = S.layers[l].qkv;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            // Q3T_TK_WPUB: wave w owns rows 16w .. 16w + 15 (row 16w + 4j + lane / 16) and publishes them itself
-            const int row = Q3T_TK_WPUB ? 16 * (t >> 6) + 4 * j + (grp & 3) : 16 * j + grp;
-            const uint16_t *r = W + (size_t)(64 * i + row) * H + l16 * 8;
-#pragma unroll
-            for (int tt = 0; tt < 8; ++tt) wq[j][tt] = ld16(r + tt * 128);
-        }
-        nw = ldf4(S.layers[l].attn_norm + 4 * t);
-    };
-    issue_qkv(0);
+    qkv_issue<Pol>(S.layers[0].qkv, S.layers[0].attn_norm, i, wq, nw);
     for (int l = 0; l < nl; ++l) {
         const int ph = 5 * l;
         float4 x;
         if (l == 0) {
-            x = layer0_x4(p);
+            x = gather_x4(p);
         } else {
             uint32_t u[4];
             PROF(ph, 0);
-            g_gate(p.gx + 4 * t, X.tag(5 * (l - 1) + 4), X.c);
-            g_waitc<4>(p.gx + 4 * t, X.tag(5 * (l - 1) + 4), u, X.c);
+            wait_in<Pol, 4>(X, p.gx + 4 * t, X.tag(5 * (l - 1) + 4), u);
             PROF(ph, 1);
             x = f4_of(u);
         }
-        rms_to_f16(x, nw, p.eps, S.xs, S.dscr, nullptr);
-        __syncthreads();
-        float acc[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            acc[j] = 0.0f;
-#pragma unroll
-            for (int tt = 0; tt < 8; ++tt) acc[j] = dot8(wq[j][tt], *reinterpret_cast<const uint4 *>(S.xs + l16 * 8 + tt * 128), acc[j]);
-        }
-        if constexpr (Q3T_TK_WPUB) {
-            // each wave publishes its 16 rows as one whole line (persist_cp.hip role_qkv): no barrier
-            float pv = 0.0f;
-            const int lane = t & 63;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float v = __shfl(group_sum<16>(acc[j]), 16 * (lane & 3));
-                if ((lane >> 2) == j) pv = v;
-            }
-            if (lane < 16) g_put(p.gqkv + 64 * i + 16 * (t >> 6) + lane, __float_as_uint(pv), X.tag(ph));
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc[j] = group_sum<16>(acc[j]);
-                if (l16 == 0) S.outv[16 * j + grp] = acc[j];
-            }
-            __syncthreads();
-            // one store instruction of wave 0 publishes the 64 rows (4 whole lines): single-lane stores from four waves
-            // into shared lines make the next edge slower
-            if (t < 64) g_put(p.gqkv + 64 * i + t, __float_as_uint(S.outv[t]), X.tag(ph));
-        }
-        PROF(ph, 2);
-        if (Q3T_TK_PUT_FIRST) __syncthreads();
+        qkv_phase<Pol>(X, i, x, wq, nw, ph);
         if (l + 1 < nl) {
-            issue_qkv(l + 1);
+            qkv_issue<Pol>(S.layers[l + 1].qkv, S.layers[l + 1].attn_norm, i, wq, nw);
         } else {   // codec head rows 48i + 16j + grp
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const uint16_t *r = p.head + (size_t)(48 * i + 16 * j + grp) * H + l16 * 8;
-#pragma unroll
-                for (int tt = 0; tt < 8; ++tt) wq[j][tt] = ld16(r + tt * 128);
-            }
+            for (int j = 0; j < 3; ++j) issue_row(p.head, 48 * i + 16 * j + grp, wq[j]);
             nw = ldf4(p.out_norm + 4 * t);
         }
     }
@@ -236,21 +153,7 @@ __device__ __forceinline__ void tk_qkv(Ctx<CPW> &X) {
     PROF(hph, 1);
     rms_to_f16(f4_of(u), nw, p.eps, S.xs, S.dscr, i == 0 ? p.hidden : nullptr);
     __syncthreads();
-    float a0[3], a1[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        a0[j] = 0.0f;
-        a1[j] = 0.0f;
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) a0[j] = dot8(wq[j][tt], *reinterpret_cast<const uint4 *>(S.xs + l16 * 8 + tt * 128), a0[j]);
-#pragma unroll
-        for (int tt = 4; tt < 8; ++tt) a1[j] = dot8(wq[j][tt], *reinterpret_cast<const uint4 *>(S.xs + l16 * 8 + tt * 128), a1[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const float lg = group_sum<16>(a0[j]) + group_sum<16>(a1[j]);
-        if (l16 == 0) S.outv[16 * j + grp] = lg;
-    }
+    head_rows<3>(X, wq);
     __syncthreads();
     if (t < 48) {
         g_put(p.glog + 48 * i + t, __float_as_uint(S.outv[t]), X.tag(hph));
@@ -260,11 +163,10 @@ __device__ __forceinline__ void tk_qkv(Ctx<CPW> &X) {
 }
 
 // ------------------------------------------------------------------ split combine + O-projection K slice (128 rows)
-template <int CPW>
-__device__ __forceinline__ void tk_o(Ctx<CPW> &X) {
+__device__ __forceinline__ void tk_o(Ctx &X) {
     constexpr int CB = 8;   // chunks per poll sweep
     const PersistParams &p = X.p;
-    TLds<CPW> &S = X.S;
+    TLds &S = X.S;
     const int i = blockIdx.x - OW, w = i >> 3, rb = i & 7, t = threadIdx.x, lane = t & 63, wave = t >> 6, l16 = t & 15,
               grp4 = lane >> 4, nl = X.nl, nch = X.pos / CHK + 1;
     uint4 wo[8][4];
@@ -319,12 +221,7 @@ __device__ __forceinline__ void tk_o(Ctx<CPW> &X) {
 #pragma unroll
                         for (int k = 0; k < CB; ++k) ok &= k >= nb || (uint32_t)(va[sel][k] >> 32) == want;
                     if (ok || X.c.abort) break;
-                    if ((++it & 255u) == 0 && (__hip_atomic_load(X.c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
-                                               it >= SPIN_LIMIT)) {
-                        X.c.abort = true;
-                        __hip_atomic_fetch_or(X.c.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        break;
-                    }
+                    if (give_up(X.c, it)) break;
                     __builtin_amdgcn_s_sleep(1);
                 }
                 if (c0 == 0) {   // lane j: chunk j & 31 of group j >> 5.  max over the chunks: order-free (expf(m - max)
@@ -368,39 +265,24 @@ __device__ __forceinline__ void tk_o(Ctx<CPW> &X) {
         __syncthreads();
         // two store instructions (waves 0, 1: whole lines each) publish the slice sums of the 128 rows
         if (t < 128) g_put(p.gop + (size_t)w * H + 128 * rb + t, __float_as_uint(S.outv[t]), X.tag(ph));
-        PROF(ph, 2);
-        if (Q3T_TK_PUT_FIRST) __syncthreads();
+        published<Pol>(X, ph);
         if (l + 1 < nl) issue(l + 1);
     }
 }
 
 // ------------------------------------------------------------------ RMSNorm(ffn_norm) + gate/up + SwiGLU (32 units)
-template <int CPW>
-__device__ __forceinline__ void tk_gu(Ctx<CPW> &X) {
+__device__ __forceinline__ void tk_gu(Ctx &X) {
     const PersistParams &p = X.p;
-    TLds<CPW> &S = X.S;
-    const int i = blockIdx.x - UW, t = threadIdx.x, l16 = t & 15, grp = t >> 4, nl = X.nl;
+    TLds &S = X.S;
+    const int i = blockIdx.x - UW, t = threadIdx.x, nl = X.nl;
     uint4 wg[2][8], wu[2][8];
     float4 nw;
-    auto issue = [&](int l) {
-        const uint16_t *W = S.layers[l].gu;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int unit = 32 * i + 16 * j + grp;
-            const uint16_t *r = W + (size_t)((unit >> 4) * 32 + (unit & 15)) * H + l16 * 8;
-#pragma unroll
-            for (int tt = 0; tt < 8; ++tt) wg[j][tt] = ld16(r + tt * 128);
-#pragma unroll
-            for (int tt = 0; tt < 8; ++tt) wu[j][tt] = ld16(r + 16 * H + tt * 128);
-        }
-        nw = ldf4(S.layers[l].ffn_norm + 4 * t);
-    };
-    issue(0);
+    gu_issue(S.layers[0].gu, S.layers[0].ffn_norm, i, wg, wu, nw);
     for (int l = 0; l < nl; ++l) {
         const int ph = 5 * l + 3;
         float4 xr;   // the residual stream entering the layer
         if (l == 0) {
-            xr = layer0_x4(p);
+            xr = gather_x4(p);
         } else {
             uint32_t u4[4];
             g_waitc<4>(p.gx + 4 * t, X.tag(5 * (l - 1) + 4), u4, X.c);
@@ -418,59 +300,20 @@ __device__ __forceinline__ void tk_gu(Ctx<CPW> &X) {
             const float s = ((__uint_as_float(u[e]) + __uint_as_float(u[4 + e])) + __uint_as_float(u[8 + e])) + __uint_as_float(u[12 + e]);
             x[e] = (e == 0 ? xr.x : e == 1 ? xr.y : e == 2 ? xr.z : xr.w) + s;
         }
-        rms_to_f16(make_float4(x[0], x[1], x[2], x[3]), nw, p.eps, S.xs, S.dscr, nullptr);
-        __syncthreads();
-        float a0[2], a1[2], b0[2], b1[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            a0[j] = a1[j] = b0[j] = b1[j] = 0.0f;
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) {
-                const uint4 xv = *reinterpret_cast<const uint4 *>(S.xs + l16 * 8 + tt * 128);
-                a0[j] = dot8(wg[j][tt], xv, a0[j]);
-                b0[j] = dot8(wu[j][tt], xv, b0[j]);
-            }
-#pragma unroll
-            for (int tt = 4; tt < 8; ++tt) {
-                const uint4 xv = *reinterpret_cast<const uint4 *>(S.xs + l16 * 8 + tt * 128);
-                a1[j] = dot8(wg[j][tt], xv, a1[j]);
-                b1[j] = dot8(wu[j][tt], xv, b1[j]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const float ga = group_sum<16>(a0[j]) + group_sum<16>(a1[j]);
-            const float ub = group_sum<16>(b0[j]) + group_sum<16>(b1[j]);
-            if (l16 == 0) S.hs[16 * j + grp] = silu_f(ga) * ub;
-        }
-        __syncthreads();
-        if (t < 16) g_put(p.gh + 16 * i + t, (uint32_t)f2h(S.hs[2 * t]) | ((uint32_t)f2h(S.hs[2 * t + 1]) << 16), X.tag(ph));
-        PROF(ph, 2);
-        if (Q3T_TK_PUT_FIRST) __syncthreads();
-        if (l + 1 < nl) issue(l + 1);
+        gu_phase<Pol>(X, i, make_float4(x[0], x[1], x[2], x[3]), wg, wu, nw, ph);
+        if (l + 1 < nl) gu_issue(S.layers[l + 1].gu, S.layers[l + 1].ffn_norm, i, wg, wu, nw);
     }
 }
 
-// ------------------------------------------------------------------ down + residual (23-24 rows)
-template <int CPW>
-__device__ __forceinline__ void tk_dn(Ctx<CPW> &X) {
+// ------------------------------------------------------------------ down + residual (18-19 rows)
+__device__ __forceinline__ void tk_dn(Ctx &X) {
     const PersistParams &p = X.p;
-    TLds<CPW> &S = X.S;
-    const int i = blockIdx.x - DW, t = threadIdx.x, lane = t & 63, wave = t >> 6, l16 = t & 15, grp4 = lane >> 4, nl = X.nl;
+    TLds &S = X.S;
+    const int i = blockIdx.x - DW, t = threadIdx.x, nl = X.nl;
     const int lo = i * H / ND, n = (i + 1) * H / ND - lo;
     uint4 wd[5][6];
-    auto issue = [&](int l) {   // row lo + 4j + grp4 (clamped), K slice = wave (k_gemv<1,1,4,PRO_F16,8>)
-        const uint16_t *W = S.layers[l].down;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const uint16_t *r = W + (size_t)(lo + min(4 * j + grp4, n - 1)) * INTER + wave * 768 + l16 * 8;
-#pragma unroll
-            for (int tt = 0; tt < 6; ++tt) wd[j][tt] = ld16(r + tt * 128);
-        }
-    };
-    issue(0);
+    dn_issue(S.layers[0].down, lo, n, wd);
     for (int l = 0; l < nl; ++l) {
-        const int ph = 5 * l + 4;
         if (t < n) {   // x' = x + (((o0 + o1) + o2) + o3) of row lo + t (as the gate/up workgroups)
             float xr;
             if (l == 0) {
@@ -485,53 +328,22 @@ __device__ __forceinline__ void tk_dn(Ctx<CPW> &X) {
             const float s = ((__uint_as_float(uo[0]) + __uint_as_float(uo[1])) + __uint_as_float(uo[2])) + __uint_as_float(uo[3]);
             S.xr[t] = xr + s;
         }
-        uint32_t u[6];
-        PROF(ph, 0);
-        g_gate(p.gh + 6 * t, X.tag(5 * l + 3), X.c);
-        g_waitc<6>(p.gh + 6 * t, X.tag(5 * l + 3), u, X.c);
-        PROF(ph, 1);
-        *reinterpret_cast<uint2 *>(S.xs + 12 * t) = make_uint2(u[0], u[1]);
-        *reinterpret_cast<uint2 *>(S.xs + 12 * t + 4) = make_uint2(u[2], u[3]);
-        *reinterpret_cast<uint2 *>(S.xs + 12 * t + 8) = make_uint2(u[4], u[5]);
-        wave_lds_sync();   // wave w polled exactly the K slice [768 w, 768 w + 768) it multiplies
-        float acc[5];
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            acc[j] = 0.0f;
-#pragma unroll
-            for (int tt = 0; tt < 6; ++tt)
-                acc[j] = dot8(wd[j][tt], *reinterpret_cast<const uint4 *>(S.xs + wave * 768 + l16 * 8 + tt * 128), acc[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            acc[j] = group_sum<16>(acc[j]);
-            if (l16 == 0) S.red[l & 1][wave][4 * j + grp4] = acc[j];
-        }
-        __syncthreads();
-        if (t < n) {
-            const float (&rd)[4][32] = S.red[l & 1];
-            const float s = rd[0][t] + rd[1][t] + rd[2][t] + rd[3][t];
-            g_put(p.gx + lo + t, __float_as_uint(S.xr[t] + s), X.tag(ph));
-        }
-        PROF(ph, 2);
-        if (Q3T_TK_PUT_FIRST) __syncthreads();
-        if (l + 1 < nl) issue(l + 1);
+        dn_phase<Pol>(X, lo, n, l & 1, wd, 5 * l + 4);
+        if (l + 1 < nl) dn_issue(S.layers[l + 1].down, lo, n, wd);
     }
 }
 
-// ------------------------------------------------------------------ attention: kv group g, split s (CPW chunks)
-template <int CPW>
-__device__ __forceinline__ void tk_att(Ctx<CPW> &X) {
-    constexpr int NP = CPW * CHK / 16;   // position passes of 16 (16 lanes x 8 dims per position)
+// ------------------------------------------------------------------ attention: kv group g, split s = chunk s
+__device__ __forceinline__ void tk_att(Ctx &X) {
+    constexpr int NP = CHK / 16;   // position passes of 16 (16 lanes x 8 dims per position)
     const PersistParams &p = X.p;
-    TLds<CPW> &S = X.S;
+    TLds &S = X.S;
     const int a = blockIdx.x - AW, g = a & (NKV - 1), s = a >> 3;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, pg = t >> 4, li = t & 15, nl = X.nl, pos = X.pos;
-    const int nch = pos / CHK + 1, c0 = s * CPW;
-    const int myc = min(max(nch - c0, 0), CPW);   // chunks of this split in use this step
-    if (myc == 0) return;                           // (uniform over the workgroup)
-    const int j0 = c0 * CHK;
-    const bool has_pos = pos / CHK >= c0 && pos / CHK < c0 + CPW;
+    const int nch = pos / CHK + 1;
+    if (s >= nch) return;   // this split's chunk is not in use this step (uniform over the workgroup)
+    const int j0 = s * CHK;
+    const bool has_pos = pos / CHK == s;
     // wave v polls elements lane and lane + 64 of its head (q head 2g, q head 2g+1, k, v of group g): the pair its
     // head norm and NEOX RoPE work on (no LDS staging or barrier before the norm)
     const int gi = (wave == 0 ? g * 256 : wave == 1 ? g * 256 + D : wave == 2 ? NH * D + g * D : (NH + NKV) * D + g * D) + lane;
@@ -636,82 +448,71 @@ __device__ __forceinline__ void tk_att(Ctx<CPW> &X) {
                 sc[pi][h] = ok ? __fmul_rn(sv, kq_scale) : -INFINITY;
             }
         }
-        // per chunk cc (passes 4cc .. 4cc+3): max, then exp / sum, then P.V, each as k_attn's split of 64 positions
+        // max, then exp / sum, then P.V, each as k_attn's split of 64 positions
 #pragma unroll
-        for (int cc = 0; cc < CPW; ++cc)
+        for (int h = 0; h < R; ++h) {
+            float m = sc[0][h];
 #pragma unroll
-            for (int h = 0; h < R; ++h) {
-                float m = sc[4 * cc][h];
-#pragma unroll
-                for (int q = 1; q < 4; ++q) m = fmaxf(m, sc[4 * cc + q][h]);
-                m = rows_max(m);
-                if (lane == 0) S.wred[wave][cc][h] = m;
-            }
+            for (int q = 1; q < NP; ++q) m = fmaxf(m, sc[q][h]);
+            m = rows_max(m);
+            if (lane == 0) S.wred[wave][h] = m;
+        }
         __syncthreads();
-        float M[CPW][R];
+        float M[R];
 #pragma unroll
-        for (int cc = 0; cc < CPW; ++cc)
-#pragma unroll
-            for (int h = 0; h < R; ++h)
-                M[cc][h] = fmaxf(fmaxf(S.wred[0][cc][h], S.wred[1][cc][h]), fmaxf(S.wred[2][cc][h], S.wred[3][cc][h]));
+        for (int h = 0; h < R; ++h) M[h] = fmaxf(fmaxf(S.wred[0][h], S.wred[1][h]), fmaxf(S.wred[2][h], S.wred[3][h]));
         if (t == 0) {
 #pragma unroll
-            for (int cc = 0; cc < CPW; ++cc)
-#pragma unroll
-                for (int h = 0; h < R; ++h) S.mch[cc][h] = M[cc][h];
+            for (int h = 0; h < R; ++h) S.mch[h] = M[h];
         }
         PROF(200 + l, 1);   // (development timeline: scores + max done)
+        float pr[NP][R], ls[R];
 #pragma unroll
-        for (int cc = 0; cc < CPW; ++cc) {
-            float pr[4][R], ls[R];
+        for (int h = 0; h < R; ++h) {
+            ls[h] = 0.0f;
 #pragma unroll
-            for (int h = 0; h < R; ++h) {
-                ls[h] = 0.0f;
+            for (int q = 0; q < NP; ++q) {
+                const bool ok = j0 + q * 16 + pg <= pos;
+                pr[q][h] = ok ? exp_sm(__fsub_rn(sc[q][h], M[h])) : 0.0f;
+                ls[h] += pr[q][h];
+            }
+        }
+        {   // rows_sum of both heads at once: row 0 ends with head 0's (r0 + r1) + (r2 + r3), row 1 with head 1's
+            const float lsum = rows_sum_pair(ls[0], ls[1]);
+            if ((lane & 47) == 0) S.wsum[wave][lane >> 4] = lsum;   // lanes 0, 16
+        }
+        float acc[R][8];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int pi = 4 * cc + q;
-                    const bool ok = j0 + pi * 16 + pg <= pos;
-                    pr[q][h] = ok ? exp_sm(__fsub_rn(sc[pi][h], M[cc][h])) : 0.0f;
-                    ls[h] += pr[q][h];
+        for (int h = 0; h < R; ++h)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[h][e] = 0.0f;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            const int j = j0 + q * 16 + pg;
+            const bool ok = j <= pos;
+            float v8[8];
+            if constexpr (Q3T_TK_HOIST) {
+                const uint32_t ww[4] = {vr[q].x, vr[q].y, vr[q].z, vr[q].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v8[2 * e] = j == pos ? vn8[2 * e] : h2f(ww[e] & 0xffff);
+                    v8[2 * e + 1] = j == pos ? vn8[2 * e + 1] : h2f(ww[e] >> 16);
                 }
+            } else if (j == pos) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v8[e] = S.vn_s[li * 8 + e];
+            } else {
+                const uint32_t ww[4] = {vr[q].x, vr[q].y, vr[q].z, vr[q].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { v8[2 * e] = h2f(ww[e] & 0xffff); v8[2 * e + 1] = h2f(ww[e] >> 16); }
             }
-            {   // rows_sum of both heads at once: row 0 ends with head 0's (r0 + r1) + (r2 + r3), row 1 with head 1's
-                const float lsum = rows_sum_pair(ls[0], ls[1]);
-                if ((lane & 47) == 0) S.wsum[wave][cc][lane >> 4] = lsum;   // lanes 0, 16
-            }
-            float acc[R][8];
 #pragma unroll
             for (int h = 0; h < R; ++h)
 #pragma unroll
-                for (int e = 0; e < 8; ++e) acc[h][e] = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int pi = 4 * cc + q;
-                const int j = j0 + pi * 16 + pg;
-                const bool ok = j <= pos;
-                float v8[8];
-                if constexpr (Q3T_TK_HOIST) {
-                    const uint32_t ww[4] = {vr[pi].x, vr[pi].y, vr[pi].z, vr[pi].w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        v8[2 * e] = j == pos ? vn8[2 * e] : h2f(ww[e] & 0xffff);
-                        v8[2 * e + 1] = j == pos ? vn8[2 * e + 1] : h2f(ww[e] >> 16);
-                    }
-                } else if (j == pos) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v8[e] = S.vn_s[li * 8 + e];
-                } else {
-                    const uint32_t ww[4] = {vr[pi].x, vr[pi].y, vr[pi].z, vr[pi].w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { v8[2 * e] = h2f(ww[e] & 0xffff); v8[2 * e + 1] = h2f(ww[e] >> 16); }
-                }
-#pragma unroll
-                for (int h = 0; h < R; ++h)
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2)   // packed fmas (v_pk_fma_f32), the same roundings
-                        fma2(pr[q][h], ok ? v8[e] : 0.0f, ok ? v8[e + 1] : 0.0f, acc[h][e], acc[h][e + 1]);
-            }
-            // rows_sum of the 16 accumulators as a reduce-scatter (12 row swaps in place of 32): row k ends with values
+                for (int e = 0; e < 8; e += 2)   // packed fmas (v_pk_fma_f32), the same roundings
+                    fma2(pr[q][h], ok ? v8[e] : 0.0f, ok ? v8[e + 1] : 0.0f, acc[h][e], acc[h][e + 1]);
+        }
+        {   // rows_sum of the 16 accumulators as a reduce-scatter (12 row swaps in place of 32): row k ends with values
             // k, 4 + k, 8 + k, 12 + k (value n = 8 h + e), each (r0 + r1) + (r2 + r3) as rows_sum
             float v16[16], c8[8];
 #pragma unroll
@@ -726,33 +527,29 @@ __device__ __forceinline__ void tk_att(Ctx<CPW> &X) {
                 const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(c8[2 * q]), __float_as_uint(c8[2 * q + 1]), false, false);
                 const float av = __uint_as_float((uint32_t)sw[0]) + __uint_as_float((uint32_t)sw[1]);
                 const int n = 4 * q + (lane >> 4);
-                S.ared[wave][cc][n >> 3][li * 8 + (n & 7)] = av;
+                S.ared[wave][n >> 3][li * 8 + (n & 7)] = av;
             }
         }
         __syncthreads();
         PROF(200 + l, 2);   // (development timeline: P.V reduced)
-        uint64_t *gout = p.gattn + (size_t)g * R * (D / 2);
         if (nch == 1) {   // one chunk: k_attn's single-split output
             if (t < R * D / 2) {
                 const int h = t / (D / 2), d = 2 * (t % (D / 2));
-                const float lsum = (S.wsum[0][0][h] + S.wsum[1][0][h]) + (S.wsum[2][0][h] + S.wsum[3][0][h]);
-                const float a0 = (S.ared[0][0][h][d] + S.ared[1][0][h][d]) + (S.ared[2][0][h][d] + S.ared[3][0][h][d]);
-                const float a1 = (S.ared[0][0][h][d + 1] + S.ared[1][0][h][d + 1]) + (S.ared[2][0][h][d + 1] + S.ared[3][0][h][d + 1]);
-                g_put(gout + t, (uint32_t)f2h(a0 / lsum) | ((uint32_t)f2h(a1 / lsum) << 16), X.tag(ph));
+                const float lsum = (S.wsum[0][h] + S.wsum[1][h]) + (S.wsum[2][h] + S.wsum[3][h]);
+                const float a0 = (S.ared[0][h][d] + S.ared[1][h][d]) + (S.ared[2][h][d] + S.ared[3][h][d]);
+                const float a1 = (S.ared[0][h][d + 1] + S.ared[1][h][d + 1]) + (S.ared[2][h][d + 1] + S.ared[3][h][d + 1]);
+                g_put(p.gattn + (size_t)g * R * (D / 2) + t, (uint32_t)f2h(a0 / lsum) | ((uint32_t)f2h(a1 / lsum) << 16), X.tag(ph));
             }
-        } else {   // this split's chunk partials (acc [2][128], m [2], l [2]) in their chunk slots: the O workgroups combine
-            uint64_t *gp = p.gpart + (size_t)g * MAXCH * PSLOT;
-            for (int cc = 0; cc < myc; ++cc) {
-                uint64_t *mine = gp + (size_t)(c0 + cc) * PSLOT;
-                const int h = t / D, d = t % D;
-                const float av = (S.ared[0][cc][h][d] + S.ared[1][cc][h][d]) + (S.ared[2][cc][h][d] + S.ared[3][cc][h][d]);
-                g_put(mine + t, __float_as_uint(av), X.tag(ph));
-                if (t < PSLOT - R * D) {
-                    const int hh = t % R;
-                    const float lsum = (S.wsum[0][cc][hh] + S.wsum[1][cc][hh]) + (S.wsum[2][cc][hh] + S.wsum[3][cc][hh]);
-                    const float v = t < R ? S.mch[cc][hh] : t < 2 * R ? lsum : 0.0f;
-                    g_put(mine + R * D + t, __float_as_uint(v), X.tag(ph));
-                }
+        } else {   // this chunk's partial (acc [2][128], m [2], l [2]) in its chunk slot: the O workgroups combine
+            uint64_t *mine = p.gpart + ((size_t)g * MAXCH + s) * PSLOT;
+            const int h = t / D, d = t % D;
+            const float av = (S.ared[0][h][d] + S.ared[1][h][d]) + (S.ared[2][h][d] + S.ared[3][h][d]);
+            g_put(mine + t, __float_as_uint(av), X.tag(ph));
+            if (t < PSLOT - R * D) {
+                const int hh = t % R;
+                const float lsum = (S.wsum[0][hh] + S.wsum[1][hh]) + (S.wsum[2][hh] + S.wsum[3][hh]);
+                const float v = t < R ? S.mch[hh] : t < 2 * R ? lsum : 0.0f;
+                g_put(mine + R * D + t, __float_as_uint(v), X.tag(ph));
             }
         }
         PROF(ph, 2);
@@ -763,10 +560,9 @@ __device__ __forceinline__ void tk_att(Ctx<CPW> &X) {
 }
 
 // ------------------------------------------------------------------ CB0 selection of the next frame
-template <int CPW>
-__device__ __forceinline__ void tk_sel(Ctx<CPW> &X) {
+__device__ __forceinline__ void tk_sel(Ctx &X) {
     const PersistParams &p = X.p;
-    TLds<CPW> &S = X.S;
+    TLds &S = X.S;
     const int t = threadIdx.x, hph = 5 * X.nl;
     SelPre spre;
     if (p.sel.mode != SEL_NONE) sel_prefetch<SEL_CB0>(p.sel, 0, spre);
@@ -811,12 +607,11 @@ __device__ __forceinline__ void tk_sel(Ctx<CPW> &X) {
     PROF(hph, 2);
 }
 
-template <int CPW>
 __global__ void __launch_bounds__(256, 2) k_tk_roles(const PersistParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    TLds<CPW> &S = *reinterpret_cast<TLds<CPW> *>(smem);
+    TLds &S = *reinterpret_cast<TLds *>(smem);
     const int t = threadIdx.x, w = blockIdx.x;
-    Ctx<CPW> X{p, S, Ctl{p.err, false}, __hip_atomic_load(p.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), p.pos[0], p.n_layers};
+    Ctx X{{p, S, Ctl{p.err, false}, __hip_atomic_load(p.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)}, p.pos[0], p.n_layers};
     if (t < p.n_layers) S.layers[t] = p.L[t];
     __syncthreads();
     const int sel_w = AW + 8 * p.roles_split;
@@ -828,57 +623,44 @@ __global__ void __launch_bounds__(256, 2) k_tk_roles(const PersistParams p) {
     else tk_sel(X);
 }
 
-template <int CPW>
-size_t tk_lds() { return sizeof(TLds<CPW>); }   // <= 80 KB: two workgroups per CU
-
-template <int CPW>
-const void *tk_fn() { return reinterpret_cast<const void *>(&k_tk_roles<CPW>); }
-
-// chunks of 64 positions per attention workgroup for a context, 0 if the role kernel does not cover it
-int tk_cpw(int n_ctx) {
+// one chunk of 64 positions per attention workgroup: does the grid cover the context?
+bool tk_covers(int n_ctx) {
     const int nch = (n_ctx + CHK - 1) / CHK;
-    return nch <= S_MAX && nch <= MAXCH ? 1 : 0;
+    return nch <= S_MAX && nch <= MAXCH;
 }
+const void *const tk_fn = reinterpret_cast<const void *>(&k_tk_roles);
 
 }  // namespace
 
-bool persist_tk_roles_supported(int n_ctx) { return tk_cpw(n_ctx) != 0; }
+bool persist_tk_roles_supported(int n_ctx) { return tk_covers(n_ctx); }
 
 bool persist_tk_roles_resident(int device, int n_ctx) {
     int n_cu = 0, blocks = 0;
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < 256) return false;
-    const int cpw = tk_cpw(n_ctx);
-    if (!cpw) return false;
-    const void *k = tk_fn<1>();
-    const size_t lds = tk_lds<1>();
-    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+    if (!tk_covers(n_ctx)) return false;
+    if (hipFuncSetAttribute(tk_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(TLds)) != hipSuccess) return false;
     // the grid (up to 505 workgroups) must be co-resident: two per CU
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k, 256, lds) == hipSuccess && blocks >= 2;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, tk_fn, 256, sizeof(TLds)) == hipSuccess && blocks >= 2;
 }
 
-template <int CPW>
-static bool tk_launch(PersistParams p, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        Q3T_HIP(hipFuncSetAttribute(tk_fn<CPW>(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tk_lds<CPW>()));
-        attr = true;
-    }
-    const int nch = (p.n_ctx + CHK - 1) / CHK;
-    p.roles_split = (nch + CPW - 1) / CPW;
-    hipLaunchKernelGGL((k_tk_roles<CPW>), dim3(AW + 8 * p.roles_split + 1), dim3(256), tk_lds<CPW>(), s, p);
-    Q3T_HIP(hipGetLastError());
-    return true;
-}
-
-bool persist_tk_roles(const PersistParams &p, hipStream_t s) {
+bool persist_tk_roles(const PersistParams &p0, hipStream_t s) {
+    PersistParams p = p0;
     if (!p.L || p.n_layers <= 0 || p.n_layers > MAXL || !p.head || !p.logits || !p.hidden || !p.pos || !p.rope || !p.kc ||
         !p.vc || !p.gx || (p.gather && !(p.gs.tok && p.gs.tabs && p.gs.frame && p.gs.tr && p.gs.tr_len && p.gs.pad)) ||
         (!p.gather && !p.x_in) || (p.sel.mode != SEL_NONE && (p.sel.mode != SEL_CB0 || p.sel.V != VOC))) {
         set_error("persist_tk_roles: bad parameters");
         return false;
     }
-    if (tk_cpw(p.n_ctx) != 1) { set_error("persist_tk_roles: context too long"); return false; }
-    return tk_launch<1>(p, s);
+    if (!tk_covers(p.n_ctx)) { set_error("persist_tk_roles: context too long"); return false; }
+    static bool attr = false;
+    if (!attr) {
+        Q3T_HIP(hipFuncSetAttribute(tk_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(TLds)));
+        attr = true;
+    }
+    p.roles_split = (p.n_ctx + CHK - 1) / CHK;   // one attention split per chunk of the context
+    hipLaunchKernelGGL(k_tk_roles, dim3(AW + 8 * p.roles_split + 1), dim3(256), sizeof(TLds), s, p);
+    Q3T_HIP(hipGetLastError());
+    return true;
 }
 
 }  // namespace q3t

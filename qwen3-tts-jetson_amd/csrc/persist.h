@@ -45,6 +45,9 @@ struct PersistParams {
     SelectSpec sel;               // SEL_CB0 of the next frame, or SEL_NONE
     // hand-off state (persist_alloc)
     uint64_t *gx = nullptr, *gx2 = nullptr, *gqkv = nullptr, *gattn = nullptr, *gh = nullptr;
+    // a second instance of those five vectors (k_cp_roles only: the hidden-state token of its paired pass, whose chain
+    // runs beside the CB0 token's; every other kernel ignores them)
+    uint64_t *gx_b = nullptr, *gx2_b = nullptr, *gqkv_b = nullptr, *gattn_b = nullptr, *gh_b = nullptr;
     uint64_t *gpart = nullptr;     // [8][32][264] attention split partials (granules)
     uint64_t *gop = nullptr;       // [4][1024] O-projection K-slice partial rows (granules, persist_tk.hip)
     uint64_t *gtok = nullptr;      // [16] code-predictor tokens of the launch (granules)

@@ -672,7 +672,7 @@ __global__ void __launch_bounds__(256) k_persist(const PersistParams p) {
 }
 
 struct StateLayout {
-    size_t gx, gx2, gqkv, gattn, gh, part, gpart, gop, gtok, glog, ctr, total;
+    size_t gx, gx2, gqkv, gattn, gh, part, gpart, gop, gtok, glog, ctr, gx_b, gx2_b, gqkv_b, gattn_b, gh_b, total;
     StateLayout() {
         size_t o = 0;
         auto take = [&](size_t b) { const size_t r = o; o += (b + 255) & ~(size_t)255; return r; };
@@ -687,6 +687,11 @@ struct StateLayout {
         gtok = take(16 * 8);
         glog = take(VOC * 8);
         ctr = take(64 * 4);
+        gx_b = take(H * 8);   // k_cp_roles: the second set of the five edge vectors
+        gx2_b = take(H * 8);
+        gqkv_b = take(QKVN * 8);
+        gattn_b = take(NH * D / 2 * 8);
+        gh_b = take(INTER / 2 * 8);
         total = o;
     }
 };
@@ -753,6 +758,11 @@ void persist_carve(uint8_t *base, PersistParams &p) {
     p.gqkv = reinterpret_cast<uint64_t *>(base + L.gqkv);
     p.gattn = reinterpret_cast<uint64_t *>(base + L.gattn);
     p.gh = reinterpret_cast<uint64_t *>(base + L.gh);
+    p.gx_b = reinterpret_cast<uint64_t *>(base + L.gx_b);
+    p.gx2_b = reinterpret_cast<uint64_t *>(base + L.gx2_b);
+    p.gqkv_b = reinterpret_cast<uint64_t *>(base + L.gqkv_b);
+    p.gattn_b = reinterpret_cast<uint64_t *>(base + L.gattn_b);
+    p.gh_b = reinterpret_cast<uint64_t *>(base + L.gh_b);
     p.part = reinterpret_cast<float *>(base + L.part);
     p.gpart = reinterpret_cast<uint64_t *>(base + L.gpart);
     p.gop = reinterpret_cast<uint64_t *>(base + L.gop);

@@ -26,9 +26,33 @@
 // reads its raw QKV row from the per-token table (Engine::build_cp_qkv_table); pass 0's last layer stops after its
 // K/V append (no head consumes its output).
 //
+// The paired pass (Q3T_CP_PAIR, default 1).  Passes 0 (the hidden-state token) and 1 (the CB0 token) do not consume each
+// other's output: both inputs are in memory before the launch, pass 0 has no head and no selection, and all pass 1
+// needs from pass 0 is, at each layer, its K/V row at position 0 of the attention workgroup's LDS cache.  A role
+// workgroup is idle about four fifths of a pass (it waits through the other four roles), so the two chains run through
+// the same workgroups at once: each role runs its phase for token 0 at layer l and directly after it the same phase for
+// token 1, with the layer's weights (in registers) serving both, and issues the next layer's weights after the second.
+// Phase numbers stay ph_of(pass, l, k), so tags, PROF stamps and the timeline tools keep their meaning.
+//
+//   role        order of phase executions (pass, layer) during the pair
+//   QKV         (0,0); then for l = 1..4: (0,l), (1,l); then lm_head[0] for pass 1   (pass 1's layer 0: the table row)
+//   ATT         for l = 0..4: (0,l), (1,l); then the selection       ((1,0): input traw; (0,4): K/V append only)
+//   O, GU, DN   for l = 0..4: (0,l), (1,l)                            ((0,4) is skipped)
+//
+// This order cannot deadlock: every role runs its items in the order in which their input edges become ready.
+// (1,l,k) needs (1,l,k-1), which the previous role publishes right after (0,l,k-1), and that one this role's (0,l,k)
+// has already consumed; (0,l+1,0) needs (0,l,4), which DN runs before (1,l,4).  Passes 2..15 run as before.
+// The two chains are about one body (1 us) apart, so a producer would publish token 1's granules into a vector whose
+// consumers may still poll for token 0's tag (and then wait until the bounded wait gives up): gx, gx2, gqkv, gattn and
+// gh exist twice (PersistParams::g*_b), pass 0 has the second set and every reader picks its producer's set (Ctx::use).
+// gtok and glog stay single (only passes >= 1 have a head).  LDS: S.red alternates by phase execution, so the two
+// tokens of a layer take different parities; every other tile is reused only after the barrier that already ends each
+// phase execution (published<Pol> with PUT_FIRST, the attention's barriers), exactly as between two layers; the
+// attention writes position 0 and then position 1 of the layer's cache before token 1's scores.
+//
 // The QKV, head-row, gate/up and down bodies are persist_roles.h's, shared with persist_tk.hip; this file keeps the
-// role map, the 16 x 5 loop nest with pass 0's skipped last layer, each phase's input wait (gx / gx2), the O role
-// (a wave K slice + residual), the attention and the selection.
+// role map, the 16 x 5 loop nest with the paired pass and pass 0's skipped last layer, each phase's input wait
+// (gx / gx2), the O role (a wave K slice + residual), the attention and the selection.
 #include "persist.h"
 #include "persist_dev.h"
 #ifdef Q3T_DEV
@@ -66,6 +90,9 @@ namespace q3t { __device__ uint64_t *g_selprof = nullptr; }
 #ifndef Q3T_CP_PREDIV
 #define Q3T_CP_PREDIV 1   // the head workgroups publish the rows divided by T (0: the selecting workgroups divide)
 #endif
+#ifndef Q3T_CP_PAIR   // passes 0 and 1 as one paired pass, interleaved layer by layer (0: one after the other)
+#define Q3T_CP_PAIR 1
+#endif
 #ifndef Q3T_CP_WAIT
 #define Q3T_CP_WAIT g_waitc   // contiguous granules (16-byte loads; development: g_wait_gated)
 #endif
@@ -77,6 +104,7 @@ using namespace prole;
 
 constexpr int VOC = 3072, CPV = 2048;
 constexpr int G = 256, NLC = 5, NPASS = 16, PPH = 5 * NLC + 1, MMS = Q3T_CP_MMS;
+constexpr bool PAIR = Q3T_CP_PAIR;
 constexpr int QW = 0, NQ = 64;      // QKV rows 64 (4 x 16) of 4096; lm_head rows 32 (2 x 16) of 2048
 constexpr int AW = 64, NA = 8;      // attention of kv group w - AW, token selection
 constexpr int OW = 72, NO = 32;     // O-projection rows 32 (8 x 4) of 1024
@@ -104,13 +132,38 @@ struct CLds {
     const uint16_t *tabs[16];
 };
 
-using Ctx = RoleCtx<CLds>;
+// persist_roles.h's role context (RoleCtx) with the launch's parameters by value: use(pass) points the five edge
+// vectors at the set of the token the next phase execution serves, so the shared bodies publish and poll there
+struct Ctx {
+    const PersistParams &k;   // the launch's parameters as passed
+    PersistParams p;
+    CLds &S;
+    Ctl c;
+    unsigned seq;
+    __device__ uint32_t tag(int ph) const { return ((seq * 1024u + (unsigned)ph) << 1) | 1u; }
+    __device__ __forceinline__ void use(int pass) {
+        if constexpr (!PAIR) return;
+        const bool b = pass == 0;   // the hidden-state token has the second set
+        p.gx = b ? k.gx_b : k.gx;
+        p.gx2 = b ? k.gx2_b : k.gx2;
+        p.gqkv = b ? k.gqkv_b : k.gqkv;
+        p.gattn = b ? k.gattn_b : k.gattn;
+        p.gh = b ? k.gh_b : k.gh;
+    }
+};
 struct Pol {   // persist_roles.h's policy
     static constexpr bool WPUB = Q3T_CP_WPUB, PUT_FIRST = Q3T_CP_PUT_FIRST, GATE = Q3T_CP_GATE;
     template <int N>
     static __device__ __forceinline__ void wait(const uint64_t *g, uint32_t tag, uint32_t (&u)[N], Ctl &c) { Q3T_CP_WAIT<N>(g, tag, u, c); }
 };
 
+// the tokens of `pass` at one layer: the paired pass runs token 0 (the hidden state), then token 1 (CB0); every other
+// pass its own token
+#if Q3T_CP_PAIR
+#define CP_TOKENS(pass, ps) for (int ps = (pass) == 1 ? 0 : (pass); ps <= (pass); ++ps)
+#else
+#define CP_TOKENS(pass, ps) if (const int ps = (pass); true)
+#endif
 __device__ __forceinline__ int ph_of(int pass, int l, int k) { return pass * PPH + 5 * l + k; }
 // the layer an O / gate-up / down workgroup runs after (pass, l), whose weights it issues next: pass 0 skips its last
 // layer; -1 after the frame's last phase
@@ -130,20 +183,24 @@ __device__ __forceinline__ void role_qkv(Ctx &X) {
     float4 nw;
     auto issue_qkv = [&](int l) { qkv_issue<Pol>(S.layers[l].qkv, S.layers[l].attn_norm, i, wq, nw); };
     issue_qkv(0);
-    for (int pass = 0; pass < NPASS; ++pass) {
-        for (int l = pass == 0 ? 0 : 1; l < NLC; ++l) {
-            const int ph = ph_of(pass, l, 0);
+    for (int pass = PAIR ? 1 : 0; pass < NPASS; ++pass) {
+        for (int l = 0; l < NLC; ++l)
+        CP_TOKENS(pass, ps) {   // the paired pass: token 0, then token 1
+            if (ps >= 1 && l == 0) continue;   // layer 0 of passes 1..15: the table row, no phase here
+            X.use(ps);
+            const int ph = ph_of(ps, l, 0);
             float4 x;
             if (l == 0) {
                 x = ldf4(p.x_in + 4 * t);   // pass 0: the talker hidden state (written before the launch)
             } else {
                 uint32_t u[4];
                 PROF(ph, 0);
-                wait_in<Pol, 4>(X, p.gx + 4 * t, X.tag(ph_of(pass, l - 1, 4)), u);
+                wait_in<Pol, 4>(X, p.gx + 4 * t, X.tag(ph_of(ps, l - 1, 4)), u);
                 PROF(ph, 1);
                 x = f4_of(u);
             }
             qkv_phase<Pol>(X, i, x, wq, nw, ph);
+            if (ps < pass && l > 0) continue;   // the paired pass: the layer's rows serve the second token too
             if (l + 1 < NLC) {
                 issue_qkv(l + 1);
             } else if (pass >= 1) {   // lm_head[pass - 1]: rows 32i + 16j + grp
@@ -205,18 +262,20 @@ __device__ __forceinline__ void role_att(Ctx &X) {
     float traw[2] = {ldgv<float>(p.qkvtab + (size_t)tok * QKVN + gi), ldgv<float>(p.qkvtab + (size_t)tok * QKVN + gi + 64)};
     const float kq_scale = 1.0f / sqrtf((float)D);
     __syncthreads();
-    for (int pass = 0; pass < NPASS; ++pass) {
-        const int pos = pass;
-        for (int l = 0; l < NLC; ++l) {
-            const int ph = ph_of(pass, l, 1);
+    for (int pass = PAIR ? 1 : 0; pass < NPASS; ++pass) {
+        for (int l = 0; l < NLC; ++l)
+        CP_TOKENS(pass, ps) {   // the paired pass: position 0's row of the
+            X.use(ps);                                                    // layer's cache, then position 1's and its scores
+            const int pos = ps;
+            const int ph = ph_of(ps, l, 1);
             float xr[2];
-            if (pass >= 1 && l == 0) {
+            if (ps >= 1 && l == 0) {
                 xr[0] = traw[0];
                 xr[1] = traw[1];
             } else {
                 uint32_t u[2];
                 PROF(ph, 0);
-                g_wait<2, 64>(p.gqkv + gi, X.tag(ph_of(pass, l, 0)), u, X.c);
+                g_wait<2, 64>(p.gqkv + gi, X.tag(ph_of(ps, l, 0)), u, X.c);
                 PROF(ph, 1);
                 xr[0] = __uint_as_float(u[0]);
                 xr[1] = __uint_as_float(u[1]);
@@ -249,7 +308,7 @@ __device__ __forceinline__ void role_att(Ctx &X) {
                 }
             }
             __syncthreads();
-            if (pass == 0 && l == NLC - 1) continue;   // pass 0's last layer: only its K/V rows are ever read
+            if (ps == 0 && l == NLC - 1) continue;   // pass 0's last layer: only its K/V rows are ever read
             // scores of position pg (16 lanes x 8 dims), softmax over positions 0..pos, P.V (k_attn arithmetic)
             const bool ok = pg <= pos;
             float q8[2][8], k8[8], v8[8];
@@ -400,15 +459,17 @@ __device__ __forceinline__ void role_o(Ctx &X) {
     };
     issue(0);
     int it = 0;   // phase executions: the parity of S.red
-    for (int pass = 0; pass < NPASS; ++pass) {
-        for (int l = 0; l < NLC; ++l) {
-            if (pass == 0 && l == NLC - 1) continue;
+    for (int pass = PAIR ? 1 : 0; pass < NPASS; ++pass) {
+        for (int l = 0; l < NLC; ++l)
+        CP_TOKENS(pass, ps) {   // the paired pass: token 0, then token 1
+            if (ps == 0 && l == NLC - 1) continue;
+            X.use(ps);
             const int par = it++ & 1;
-            const int ph = ph_of(pass, l, 2);
+            const int ph = ph_of(ps, l, 2);
             if (t < 32) {   // the residual rows x_l[32i + t]
                 const int row = 32 * i + t;
                 float xr;
-                if (l == 0 && pass == 0) {
+                if (l == 0 && ps == 0) {
                     xr = p.x_in[row];
                 } else if (l == 0) {   // the table row of the previous pass's token (pass 1: CB0)
                     int tok = p.gs.tok[0];
@@ -422,14 +483,14 @@ __device__ __forceinline__ void role_o(Ctx &X) {
                                 : h2f(S.tabs[pass - 1][(size_t)tok * H + row]);
                 } else {
                     uint32_t u1[1];
-                    g_wait<1>(p.gx + row, X.tag(ph_of(pass, l - 1, 4)), u1, X.c);
+                    g_wait<1>(p.gx + row, X.tag(ph_of(ps, l - 1, 4)), u1, X.c);
                     xr = __uint_as_float(u1[0]);
                 }
                 S.xr[t] = xr;
             }
             uint32_t u[4];
             PROF(ph, 0);
-            wait_in<Pol, 4>(X, p.gattn + 4 * t, X.tag(ph_of(pass, l, 1)), u);
+            wait_in<Pol, 4>(X, p.gattn + 4 * t, X.tag(ph_of(ps, l, 1)), u);
             PROF(ph, 1);
             *reinterpret_cast<uint4 *>(S.xs + 8 * t) = make_uint4(u[0], u[1], u[2], u[3]);
             wave_lds_sync();   // wave w polled exactly the K slice [512 w, 512 w + 512) it multiplies
@@ -453,7 +514,7 @@ __device__ __forceinline__ void role_o(Ctx &X) {
                 g_put(p.gx2 + 32 * i + t, __float_as_uint(S.xr[t] + s), X.tag(ph));
             }
             published<Pol>(X, ph);
-            if (next_layer(pass, l) >= 0) issue(next_layer(pass, l));
+            if (ps == pass && next_layer(pass, l) >= 0) issue(next_layer(pass, l));   // (after the pair's second token)
         }
     }
 }
@@ -466,16 +527,18 @@ __device__ __forceinline__ void role_gu(Ctx &X) {
     uint4 wg[2][8], wu[2][8];
     float4 nw;
     gu_issue(S.layers[0].gu, S.layers[0].ffn_norm, i, wg, wu, nw);
-    for (int pass = 0; pass < NPASS; ++pass) {
-        for (int l = 0; l < NLC; ++l) {
-            if (pass == 0 && l == NLC - 1) continue;
-            const int ph = ph_of(pass, l, 3);
+    for (int pass = PAIR ? 1 : 0; pass < NPASS; ++pass) {
+        for (int l = 0; l < NLC; ++l)
+        CP_TOKENS(pass, ps) {   // the paired pass: token 0, then token 1
+            if (ps == 0 && l == NLC - 1) continue;
+            X.use(ps);
+            const int ph = ph_of(ps, l, 3);
             uint32_t u[4];
             PROF(ph, 0);
-            wait_in<Pol, 4>(X, p.gx2 + 4 * t, X.tag(ph_of(pass, l, 2)), u);
+            wait_in<Pol, 4>(X, p.gx2 + 4 * t, X.tag(ph_of(ps, l, 2)), u);
             PROF(ph, 1);
             gu_phase<Pol>(X, i, f4_of(u), wg, wu, nw, ph);
-            const int nl = next_layer(pass, l);
+            const int nl = ps == pass ? next_layer(pass, l) : -1;   // (after the pair's second token)
             if (nl >= 0) gu_issue(S.layers[nl].gu, S.layers[nl].ffn_norm, i, wg, wu, nw);
         }
     }
@@ -490,16 +553,18 @@ __device__ __forceinline__ void role_dn(Ctx &X) {
     uint4 wd[5][6];
     dn_issue(S.layers[0].down, lo, n, wd);
     int it = 0;   // phase executions: the parity of S.red
-    for (int pass = 0; pass < NPASS; ++pass) {
-        for (int l = 0; l < NLC; ++l) {
-            if (pass == 0 && l == NLC - 1) continue;
+    for (int pass = PAIR ? 1 : 0; pass < NPASS; ++pass) {
+        for (int l = 0; l < NLC; ++l)
+        CP_TOKENS(pass, ps) {   // the paired pass: token 0, then token 1
+            if (ps == 0 && l == NLC - 1) continue;
+            X.use(ps);
             if (t < n) {   // the residual rows x'_l (published a phase earlier)
                 uint32_t u1[1];
-                g_wait<1>(p.gx2 + lo + t, X.tag(ph_of(pass, l, 2)), u1, X.c);
+                g_wait<1>(p.gx2 + lo + t, X.tag(ph_of(ps, l, 2)), u1, X.c);
                 S.xr[t] = __uint_as_float(u1[0]);
             }
-            dn_phase<Pol>(X, lo, n, it++ & 1, wd, ph_of(pass, l, 4));
-            const int nl = next_layer(pass, l);
+            dn_phase<Pol>(X, lo, n, it++ & 1, wd, ph_of(ps, l, 4));
+            const int nl = ps == pass ? next_layer(pass, l) : -1;   // (after the pair's second token)
             if (nl >= 0) dn_issue(S.layers[nl].down, lo, n, wd);
         }
     }
@@ -509,7 +574,7 @@ __global__ void __launch_bounds__(256) k_cp_roles(const PersistParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     CLds &S = *reinterpret_cast<CLds *>(smem);
     const int t = threadIdx.x, w = blockIdx.x;
-    Ctx X{p, S, Ctl{p.err, false}, __hip_atomic_load(p.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)};
+    Ctx X{p, p, S, Ctl{p.err, false}, __hip_atomic_load(p.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)};
 #ifdef Q3T_DEV
     if (w == 0 && t == 0) g_selprof = p.prof;
 #endif

@@ -6,13 +6,15 @@ import sys
 
 import numpy as np
 
-T = np.load(sys.argv[1]).astype(np.int64)
+T = np.load(sys.argv[1]).astype(np.int64)[:256]   # the 256-workgroup kernels (k_tk_roles' rows: persist_tl_tk.py)
 stage = int(sys.argv[2])
 nsplit = int(sys.argv[3]) if len(sys.argv) > 3 else (5 if stage == 0 else 1)
-t0 = T[:, 0, 3][T[:, 0, 3] > 0].min()
+t0 = T[:, 0, 3][T[:, 0, 3] > 0].min() if (T[:, 0, 3] > 0).any() else T[T > 0].min()   # (k_cp_roles: its earliest stamp)
 T = np.where(T > 0, T - t0, -1) * 10e-3   # microseconds (100 MHz clock)
 W = np.arange(256)
 att = W < 8 * nsplit
+if stage == 1 and (T[:, 1, 2] >= 0).any():
+    att = T[:, 1, 2] >= 0   # the workgroups that stamped layer 0's attention (k_cp_roles: 64..71)
 if stage == 0:
     NL, npass, PPH = 28, 1, 141
 else:
@@ -65,7 +67,18 @@ if stage == 0:
     print(f"launch span to last head publish {end:.1f} us; layer step sum {tot:.1f}")
 else:
     ends = [T[:, ps * PPH + 24, 2].max() for ps in range(16)]
-    print(f"per-pass span mean {np.mean(np.diff(ends)):.2f} us; last layer-E publish {ends[-1]:.1f} us")
+    # pass 0 has no layer-4 E phase (its slot stays empty), so the first interval is the span of passes 0 + 1 from the
+    # launch's first stamp: reported on its own, the mean is over passes 2..15
+    print(f"passes 0 + 1: launch start to pass 1's last E publish {ends[1]:.2f} us; "
+          f"per-pass span mean (passes 2..15) {np.mean(np.diff(ends[1:])):.2f} us; last layer-E publish {ends[-1]:.1f} us")
+    # pass 1 behind pass 0, role by role (last publish of the role's workgroups), and each layer's last publishes:
+    # with the paired pass (Q3T_CP_PAIR) the lag is about one body; run one after the other it is pass 0's span
+    last = lambda ps, l, k: T[:, ps * PPH + 5 * l + k, 2].max()
+    print("layer  " + "  ".join(f"{n:>15s}" for n in names) + "   (last publish of pass 0 / pass 1, us)")
+    for l in range(NL):
+        print(f"{l:5d}  " + "  ".join(f"{last(0, l, k):7.2f}/{last(1, l, k):7.2f}" for k in range(5)))
+    lag = [np.mean([last(1, l, k) - last(0, l, k) for l in range(NL - 1) if last(0, l, k) >= 0 and last(1, l, k) >= 0]) for k in range(5)]
+    print("pass 1 behind pass 0 (mean over layers 0..3): " + ", ".join(f"{n} {v:.2f}" for n, v in zip(names, lag)) + " us")
     # head -> next pass: selection + token hand-off + first phase of next pass
     d = []
     for ps in range(1, 15):

@@ -166,6 +166,32 @@ int q3t_vocoder_decode_batch(q3t_ctx *ctx, int32_t n_utt, const int32_t *const *
 /* frames (utterances x frames) per batched vocoder launch sequence; scratch grows to ~3 MB per frame */
 int q3t_vocoder_set_batch_frames(q3t_ctx *ctx, int32_t frames);
 
+/* Streaming FULL decode: frames pushed in pieces of any size; the concatenation of the PCM of the pushes is, bit for
+ * bit, q3t_vocoder_decode(all frames, Q3T_VOCODER_FULL).  After F frames in total the stream has emitted exactly
+ * q3t_vocoder_num_samples(F, Q3T_VOCODER_FULL) samples, and a push returns the difference from the previous total
+ * (there is no flush: the one-shot decode of the same frames ends at the same sample).  The frame-rate part runs on
+ * the new frames only, against state the stream carries (per-layer f32 K/V caches sized at open from max_frames,
+ * ~64 KB per frame with the shipped geometry; open fails when they do not fit); the convolution stack is recomputed
+ * over the last q3t_vocoder_stream_halo frames plus the new ones.  The cost of a push depends on the piece, not on
+ * the history, except for the attention over the cached keys.
+ * Several streams may be open on one context, each with its own state; pushes, q3t_vocoder_decode and
+ * q3t_vocoder_decode_batch on the same context may interleave freely (they share the decoder's scratch and run one
+ * after the other on the context stream, under the device lock q3t_vocoder_decode takes).  A push may be made from a
+ * q3t_generate_stream callback, under the rule stated there for q3t_vocoder_decode.
+ * Q3T_ERR with a message, the stream's state unchanged: n_frames <= 0, more than max_frames frames in total, pcm_cap
+ * smaller than the push's sample count, a context without a vocoder (open).  A push writes
+ * q3t_vocoder_num_samples(frames + n_frames, Q3T_VOCODER_FULL) - q3t_vocoder_stream_samples samples.
+ * q3t_ctx_destroy frees the streams still open on the context; their handles are invalid afterwards.
+ * Q3T_VOC_STREAM_HALO=<frames> (development knob, read at open) overrides the derived halo. */
+typedef struct q3t_voc_stream q3t_voc_stream;
+int q3t_vocoder_stream_open(q3t_ctx *ctx, int32_t max_frames, q3t_voc_stream **out);
+int q3t_vocoder_stream_push(q3t_voc_stream *s, const int32_t *codes /* [n_frames][16] */, int32_t n_frames,
+                            float *pcm, int64_t pcm_cap, int64_t *n_samples);
+int64_t q3t_vocoder_stream_samples(const q3t_voc_stream *s); /* emitted so far */
+int32_t q3t_vocoder_stream_frames(const q3t_voc_stream *s);  /* pushed so far */
+int32_t q3t_vocoder_stream_halo(const q3t_voc_stream *s);    /* frames of left context the convolution stack re-runs */
+void q3t_vocoder_stream_close(q3t_voc_stream *s);
+
 /* ---- speaker encoder (ECAPA-TDNN; the TTS GGUF's spk_enc.* tensors)
  * q3t_speaker_dim: embedding length, 0 when the model has no speaker encoder.
  * q3t_speaker_encode: AudioTokenizerEncoder::encode (src/audio_tokenizer_encoder.h:107-108): samples in [-1, 1] at

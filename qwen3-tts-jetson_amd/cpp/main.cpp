@@ -9,6 +9,8 @@
 //   --device <n>         GPU ordinal
 //   --seed <n>           sampling seed (the counter-based sampler is reproducible per seed)
 //   --vocoder-chunk <n>  0 = whole-utterance vocoder; n > 0 = n-frame chunks streamed during generation
+//   --stream-full <n>    whole-utterance vocoder PCM produced during generation: every n frames pushed into a
+//                        vocoder stream (same WAV as without the flag; ignored with a chunked vocoder)
 //   --batch <n>          --serve decodes up to n queued requests together on the GPU (lock-step slots): requests
 //                        already waiting on stdin when one is read are batched; replies keep request order
 #include <poll.h>
@@ -42,6 +44,7 @@ void print_usage(const char *program) {
     fprintf(stderr, "  --device <n>           GPU ordinal (default: 0)\n");
     fprintf(stderr, "  --seed <n>             Sampling seed (default: 0)\n");
     fprintf(stderr, "  --vocoder-chunk <n>    Vocoder chunk frames, 0 = whole utterance (default: model dir)\n");
+    fprintf(stderr, "  --stream-full <n>      Decode every n generated frames with the streaming whole-utterance vocoder\n");
     fprintf(stderr, "  --batch <n>            Server mode: decode up to n queued requests together (default: 1)\n");
     fprintf(stderr, "  -h, --help             Show this help\n");
     fprintf(stderr, "\n");
@@ -188,7 +191,7 @@ int run_server(qwen3_tts::Qwen3TTS &tts, const std::vector<float> &speaker_embd,
 int main(int argc, char **argv) {
     std::string model_dir, text, output_file = "output.wav", reference_audio, embedding_file;
     bool serve_mode = false;
-    int device = 0, batch = 1, vocoder_chunk = -1;
+    int device = 0, batch = 1, vocoder_chunk = -1, stream_full = 0;
     unsigned long long seed = 0;
     qwen3_tts::tts_params params;
     auto need = [&](int &i, const char *what) -> const char * {
@@ -217,6 +220,7 @@ int main(int argc, char **argv) {
             else if (arg == "--serve") serve_mode = true;
             else if (arg == "--device") { if (!(v = need(i, "device"))) return 1; device = std::stoi(v); }
             else if (arg == "--seed") { if (!(v = need(i, "seed"))) return 1; seed = std::stoull(v); }
+            else if (arg == "--stream-full") { if (!(v = need(i, "stream-full interval"))) return 1; stream_full = std::stoi(v); }
             else if (arg == "--vocoder-chunk") { if (!(v = need(i, "vocoder-chunk value"))) return 1; vocoder_chunk = std::stoi(v); }
             else if (arg == "--batch") { if (!(v = need(i, "batch value"))) return 1; batch = std::max(1, std::stoi(v)); }
             else {
@@ -243,6 +247,7 @@ int main(int argc, char **argv) {
     tts.set_device(device);
     tts.set_seed(seed);
     if (vocoder_chunk >= 0) tts.set_vocoder_chunk(vocoder_chunk);
+    if (stream_full > 0) tts.set_stream_full(stream_full);
     fprintf(stderr, "Loading models from: %s\n", model_dir.c_str());
     if (!tts.load_models(model_dir)) {
         fprintf(stderr, "Error: %s\n", tts.get_error().c_str());

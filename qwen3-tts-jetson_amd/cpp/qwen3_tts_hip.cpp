@@ -283,8 +283,43 @@ bool AudioTokenizerDecoder::load_model(const std::string &model_path) {
 }
 
 void AudioTokenizerDecoder::unload_model() {
+    stream_end();
     if (ctx_) q3t_ctx_destroy(ctx_);
     ctx_ = nullptr;
+}
+
+bool AudioTokenizerDecoder::stream_begin(int32_t max_frames) {
+    if (!ctx_) { error_msg_ = "Model not loaded"; return false; }
+    stream_end();
+    if (q3t_vocoder_stream_open(ctx_, max_frames, &stream_) != Q3T_OK) {
+        stream_ = nullptr;
+        error_msg_ = last_error();
+        return false;
+    }
+    return true;
+}
+
+bool AudioTokenizerDecoder::stream_decode(const int32_t *codes, int32_t n_frames, std::vector<float> &samples) {
+    samples.clear();
+    if (!stream_) { error_msg_ = "no stream open (stream_begin)"; return false; }
+    if (!codes || n_frames <= 0) { error_msg_ = "no codes to decode"; return false; }
+    const int64_t total = q3t_vocoder_num_samples(ctx_, q3t_vocoder_stream_frames(stream_) + n_frames, Q3T_VOCODER_FULL);
+    const int64_t cap = total - q3t_vocoder_stream_samples(stream_);
+    if (total < 0 || cap < 0) { error_msg_ = last_error(); return false; }
+    samples.resize((size_t)cap);
+    int64_t got = 0;
+    if (q3t_vocoder_stream_push(stream_, codes, n_frames, samples.data(), cap, &got) != Q3T_OK) {
+        samples.clear();
+        error_msg_ = last_error();
+        return false;
+    }
+    samples.resize((size_t)got);
+    return true;
+}
+
+void AudioTokenizerDecoder::stream_end() {
+    if (stream_) q3t_vocoder_stream_close(stream_);
+    stream_ = nullptr;
 }
 
 bool AudioTokenizerDecoder::decode(const int32_t *codes, int32_t n_frames, std::vector<float> &samples) {

@@ -42,6 +42,7 @@
 
 struct q3t_ctx;
 struct q3t_tokenizer;
+struct q3t_voc_stream;
 
 namespace qwen3_tts {
 
@@ -163,6 +164,12 @@ public:
     void unload_model();
     // whole-utterance decode, codes [n_frames][16] -> samples in [-1, 1] at 24 kHz (:375-879)
     bool decode(const int32_t *codes, int32_t n_frames, std::vector<float> &samples);
+    // the same decode in pieces (q3t_vocoder_stream_*): after stream_begin, each stream_decode returns the next
+    // samples of the frames given so far; their concatenation is decode() of all frames, bit for bit.  stream_begin
+    // drops a stream still open; samples receives only this call's samples
+    bool stream_begin(int32_t max_frames = 4096);
+    bool stream_decode(const int32_t *codes, int32_t n_frames, std::vector<float> &samples);
+    void stream_end();
 
     const audio_decoder_config &get_config() const { return config_; }
     const std::string &get_error() const { return error_msg_; }
@@ -170,6 +177,7 @@ public:
 
 private:
     q3t_ctx *ctx_ = nullptr;
+    q3t_voc_stream *stream_ = nullptr;
     int device_ = 0;
     audio_decoder_config config_;
     std::string error_msg_;

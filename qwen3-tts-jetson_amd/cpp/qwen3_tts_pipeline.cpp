@@ -103,6 +103,7 @@ constexpr int32_t kSampleRate = 24000;
 
 struct StreamState {
     q3t_ctx *ctx = nullptr;
+    q3t_voc_stream *voc = nullptr;   // set: full_stream_cb pushes into it
     int32_t chunk = 0;
     std::vector<float> *audio = nullptr;
     int64_t decode_ms = 0;
@@ -122,6 +123,29 @@ int stream_cb(void *user, int32_t /*utt*/, const int32_t *codes, int32_t n_frame
         return 0;
     }
     s->audio->insert(s->audio->end(), pcm.begin(), pcm.begin() + got);
+    s->decode_ms += now_ms() - t0;
+    return 1;
+}
+
+// generate_stream callback of --stream-full: push each delivery into the vocoder stream and append what it returns
+// (the whole-utterance decode's samples, in order)
+int full_stream_cb(void *user, int32_t /*utt*/, const int32_t *codes, int32_t n_frames, int32_t /*n_cb*/) {
+    auto *s = static_cast<StreamState *>(user);
+    if (n_frames <= 0) return 1;
+    const int64_t t0 = now_ms();
+    const int64_t total = q3t_vocoder_num_samples(s->ctx, q3t_vocoder_stream_frames(s->voc) + n_frames, Q3T_VOCODER_FULL);
+    const int64_t cap = total - q3t_vocoder_stream_samples(s->voc);
+    const size_t at = s->audio->size();
+    s->audio->resize(at + (size_t)std::max<int64_t>(cap, 0));
+    int64_t got = 0;
+    if (total < 0 || cap < 0 ||
+        q3t_vocoder_stream_push(s->voc, codes, n_frames, s->audio->data() + at, cap, &got) != Q3T_OK) {
+        s->audio->resize(at);
+        s->error = true;
+        s->error_msg = q3t_error();
+        return 0;
+    }
+    s->audio->resize(at + (size_t)got);
     s->decode_ms += now_ms() - t0;
     return 1;
 }
@@ -313,21 +337,38 @@ tts_result Qwen3TTS::synthesize_internal(const std::string &text, const float *s
     st.ctx = ctx_;
     st.chunk = vocoder_chunk_;
     st.audio = &result.audio;
+    const bool stream_full = stream_full_ > 0 && vocoder_chunk_ <= 0 && max_len > 0;
+    if (stream_full && q3t_vocoder_stream_open(ctx_, max_len, &st.voc) != Q3T_OK) {
+        result.error_msg = "Failed to open the vocoder stream: " + q3t_error();
+        return result;
+    }
     int rc;
     if (max_len == 0) rc = Q3T_OK;
     else if (vocoder_chunk_ > 0)
         rc = q3t_generate_stream(ctx_, 1, tok_ptr, &n_tok, speaker_embedding ? spk : nullptr, &p, codes.data(),
                                  &n_frames, stream_cb, &st, 40);
+    else if (stream_full)
+        rc = q3t_generate_stream(ctx_, 1, tok_ptr, &n_tok, speaker_embedding ? spk : nullptr, &p, codes.data(),
+                                 &n_frames, full_stream_cb, &st, stream_full_);
     else
         rc = q3t_generate(ctx_, 1, tok_ptr, &n_tok, speaker_embedding ? spk : nullptr, &p, codes.data(), &n_frames);
+    if (st.voc && rc == Q3T_OK && !st.error && q3t_vocoder_stream_frames(st.voc) != n_frames) {
+        st.error = true;
+        st.error_msg = "the callback saw " + std::to_string(q3t_vocoder_stream_frames(st.voc)) + " of " +
+                       std::to_string(n_frames) + " generated frames";
+    }
+    if (st.voc) q3t_vocoder_stream_close(st.voc);
     if (rc != Q3T_OK) { result.error_msg = "Failed to generate speech codes: " + q3t_error(); return result; }
-    if (st.error) { result.error_msg = "TRT vocoder decode failed: " + st.error_msg; return result; }
+    if (st.error) {
+        result.error_msg = (stream_full ? "Vocoder stream decode failed: " : "TRT vocoder decode failed: ") + st.error_msg;
+        return result;
+    }
     result.t_generate_ms = now_ms() - t_gen;
     mem("synth/after-generate");
     if (params.print_progress) fprintf(stderr, "Speech codes generated: %d frames x %d codebooks\n", n_frames, 16);
     if (n_frames == 0) { result.error_msg = "No speech codes generated"; return result; }
     const int64_t t_dec = now_ms();
-    if (vocoder_chunk_ <= 0) {
+    if (vocoder_chunk_ <= 0 && !stream_full) {
         const int64_t n = q3t_vocoder_num_samples(ctx_, n_frames, Q3T_VOCODER_FULL);
         result.audio.resize((size_t)std::max<int64_t>(n, 0));
         int64_t got = 0;

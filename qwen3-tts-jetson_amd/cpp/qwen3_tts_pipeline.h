@@ -65,6 +65,11 @@ public:
     // 0: whole-utterance vocoder after generation; n > 0: n-frame chunks streamed from the frame callback
     void set_vocoder_chunk(int32_t frames) { vocoder_chunk_ = frames; }
     int32_t vocoder_chunk() const { return vocoder_chunk_; }
+    // n > 0 (and no chunked vocoder): synthesize() generates through the frame callback every n frames and pushes
+    // each delivery into a vocoder stream (q3t_vocoder_stream_*): the whole-utterance vocoder's PCM, bit for bit,
+    // produced while the frames are generated.  0 (default): whole-utterance vocoder after generation
+    void set_stream_full(int32_t interval) { stream_full_ = interval; }
+    int32_t stream_full() const { return stream_full_; }
     // n utterances decoded together on one GPU (lock-step slots); speaker_embeddings empty or one per text (an empty
     // vector = no speaker row); results[i] as synthesize_with_embedding's
     std::vector<tts_result> synthesize_batch(const std::vector<std::string> &texts,
@@ -82,6 +87,7 @@ private:
     uint64_t seed_ = 0;
     int32_t slots_ = 0, n_ctx_ = 0, hidden_ = 1024;
     int32_t vocoder_chunk_ = 0;
+    int32_t stream_full_ = 0;
     bool models_loaded_ = false;
     std::string error_msg_;
     std::string tts_model_path_;

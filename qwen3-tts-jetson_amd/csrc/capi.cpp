@@ -325,6 +325,53 @@ int q3t_vocoder_set_batch_frames(q3t_ctx *ctx, int32_t frames) {
     GUARD_END
 }
 
+// a stream handle is the decoder's own stream state (it carries its owner and the context's device)
+namespace {
+q3t::Vocoder::Stream *vst(q3t_voc_stream *s) { return reinterpret_cast<q3t::Vocoder::Stream *>(s); }
+const q3t::Vocoder::Stream *cvst(const q3t_voc_stream *s) { return reinterpret_cast<const q3t::Vocoder::Stream *>(s); }
+}  // namespace
+
+int q3t_vocoder_stream_open(q3t_ctx *ctx, int32_t max_frames, q3t_voc_stream **out) {
+    GUARD_BEGIN
+    if (out) *out = nullptr;
+    CHECK_CTX(ctx);
+    if (!out) { q3t::set_error("null argument"); return Q3T_ERR; }
+    q3t::Vocoder *v = ctx->engine.vocoder();
+    if (!v || !v->loaded()) { q3t::set_error("vocoder not loaded (no tokenizer GGUF given)"); return Q3T_ERR; }
+    q3t::DeviceLock lk(false, ctx->engine.device());   // never beside a persistent grid (devlock.h)
+    q3t::Vocoder::Stream *st = v->stream_open(max_frames);
+    if (!st) return Q3T_ERR;
+    st->device = ctx->engine.device();
+    *out = reinterpret_cast<q3t_voc_stream *>(st);
+    return Q3T_OK;
+    GUARD_END
+}
+
+int q3t_vocoder_stream_push(q3t_voc_stream *s, const int32_t *codes, int32_t n_frames, float *pcm, int64_t pcm_cap,
+                            int64_t *n_samples) {
+    GUARD_BEGIN
+    if (n_samples) *n_samples = 0;
+    if (!s) { q3t::set_error("null vocoder stream"); return Q3T_ERR; }
+    q3t::Vocoder::Stream *st = vst(s);
+    q3t::DeviceLock lk(false, st->device);   // never beside a persistent grid (devlock.h)
+    return st->owner->stream_push(st, codes, n_frames, pcm, pcm_cap, n_samples) ? Q3T_OK : Q3T_ERR;
+    GUARD_END
+}
+
+int64_t q3t_vocoder_stream_samples(const q3t_voc_stream *s) { return s ? cvst(s)->samples : -1; }
+int32_t q3t_vocoder_stream_frames(const q3t_voc_stream *s) { return s ? cvst(s)->frames : -1; }
+int32_t q3t_vocoder_stream_halo(const q3t_voc_stream *s) { return s ? cvst(s)->halo : -1; }
+
+void q3t_vocoder_stream_close(q3t_voc_stream *s) {
+    if (!s) return;
+    try {
+        q3t::Vocoder::Stream *st = vst(s);
+        q3t::DeviceLock lk(false, st->device);
+        st->owner->stream_close(st);
+    } catch (...) {
+    }
+}
+
 int q3t_ctx_create_speaker(const char *tts_gguf, int device, q3t_ctx **out) {
     GUARD_BEGIN
     if (!out || !tts_gguf) { q3t::set_error("null argument"); return Q3T_ERR; }

@@ -11,6 +11,7 @@
 namespace q3t {
 
 Vocoder::~Vocoder() {
+    while (!streams_.empty()) stream_close(streams_.back());
     for (void *p : allocs_) hipFree(p);
     for (void *p : scratch_) hipFree(p);
 }
@@ -247,6 +248,32 @@ int64_t Vocoder::full_len(int F) const {
     for (int d = 0; d < 4; ++d) { const int s = dec_[d].rate, K = dec_[d].ct.k; T = (T - 1) * s + K - 2 * (K - s); }
     return T;
 }
+// Frames of left context the convolution stack needs to reproduce the samples of a push (DESIGN 2c "Vocoder
+// stream").  full_len is affine in F, rate * F - lead: a push at frame boundary P starts `lead` samples before that
+// boundary.  L is how far before the boundary, in steps of the current stage, the stage's output is still read; walk
+// the stack from the PCM back to the frame rows: a causal conv (k, dilation d) reads (k-1)*d steps back; a transposed
+// conv of stride s whose output t, after trimming `trim` on the left, gathers inputs ceil((t + trim - K + 1) / s) ..
+// floor((t + trim) / s) maps L steps back to floor((L + K - 1 - trim) / s) input steps back (with trim = K - s that is
+// ceil(L / s): the second input step a K = 2s kernel reads lies ahead of t, not behind it).
+int Vocoder::stream_halo() const {
+    if (!loaded_) return 0;
+    const int64_t rate = full_len(2) - full_len(1), lead = rate - full_len(1);
+    int64_t L = std::max<int64_t>(lead, 0);
+    L += dec6_.k - 1;
+    for (int d = 3; d >= 0; --d) {
+        const Dec &D = dec_[d];
+        for (int ri = 2; ri >= 0; --ri) L += (int64_t)(D.res[ri].c1.k - 1) * D.res[ri].dil + (D.res[ri].c2.k - 1);
+        const int s = D.rate, K = D.ct.k, trim = K - s;
+        L = (L + K - 1 - trim) / s;
+    }
+    L += dec0_.k - 1;
+    for (int u = 1; u >= 0; --u) {
+        L += up_[u].dw_k - 1;
+        L = (L + up_[u].ct.k - 1) / 2;   // stride 2, no trimming
+    }
+    return (int)L;
+}
+
 double Vocoder::decode_flops(int F) const {
     if (F <= 0 || !loaded_) return 0.0;
     const double f = F, VH = hidden_, LAT = latent_;
@@ -451,9 +478,20 @@ static GemvParams row_gemv() {
 // one decode of nb_ utterances of F frames: row-wise stages (RVQ, projections, norms, 1-tap convs) run over all
 // nb_*F rows, sequence stages (causal convs, transposed convs, attention) carry the utterance as grid z
 bool Vocoder::decode_rows(const int32_t *codes_dev, int F, float *pcm_dev, int64_t *n_out, hipStream_t s) {
+    return frame_rows(codes_dev, F, s, nullptr) && conv_stack(F, pcm_dev, n_out, s);
+}
+
+// Frame-rate half.  st null: the whole utterances of a one-shot decode.  st set (nb_ = 1): the F new frames of a stream
+// at positions P..P+F-1 -- pre_conv sees the RVQ rows of the previous two frames in front of the new ones, the
+// attention runs against the stream's K/V caches, and output_proj's rows land after the stream's halo rows in buf_[1],
+// which then holds the window the convolution stack runs on.  Every launch is the one-shot path's on fewer rows.
+bool Vocoder::frame_rows(const int32_t *codes_dev, int F, hipStream_t s, Stream *st) {
     const int VH = hidden_, LAT = latent_;
     const int FR = F * nb_;   // frame rows of the batch
     float *A = buf_[0], *B = buf_[1], *C = buf_[2];
+    const int P = st ? st->frames : 0;
+    const int tail = st ? std::min(2, P) : 0;            // carried RVQ rows in front of the new ones
+    const int hrows = st ? std::min(st->halo, P) : 0;    // carried output_proj rows in front of the new ones
     // 1) RVQ: latent = W_first . cb_first[c0] + sum_k W_rest . cb_rest_k[c_{k+1}]   (:650-703)
     if (!codes_cols(codes_dev, cols_, FR, 16, s)) return false;
     GemvParams g = row_gemv();
@@ -463,13 +501,20 @@ bool Vocoder::decode_rows(const int32_t *codes_dev, int F, float *pcm_dev, int64
         g.resid = k == 0 ? nullptr : B; g.ldr = VH; g.out_f32 = B;
         if (!gemv(g, s)) return false;
     }
-    g.W = vq_first_out_; g.x = cb_first_; g.x_idx = cols_; g.resid = nullptr; g.aux = B; g.lda = VH; g.out_f32 = A;
+    g.W = vq_first_out_; g.x = cb_first_; g.x_idx = cols_; g.resid = nullptr; g.aux = B; g.lda = VH;
+    g.out_f32 = A + (size_t)tail * VH;
     if (!gemv(g, s)) return false;
+    if (st) {
+        if (tail) Q3T_HIP(hipMemcpyAsync(A, st->rvq_tail, (size_t)tail * VH * 4, hipMemcpyDeviceToDevice, s));
+        const int keep = std::min(2, P + F);   // the next push's tail: the last rows of [tail + F]
+        Q3T_HIP(hipMemcpyAsync(st->rvq_tail, A + (size_t)(tail + F - keep) * VH, (size_t)keep * VH * 4,
+                               hipMemcpyDeviceToDevice, s));
+    }
     // 2) causal pre-conv k3 (left pad 2) -> [F][LAT]   (:705-718)
-    if (!run_conv(pre_conv_, A, F, 2, 1, nullptr, C, nullptr, 0, s)) return false;
+    if (!run_conv(pre_conv_, A, tail + F, 2, 1, nullptr, C, nullptr, 0, s)) return false;
     // 3) input_proj + bias -> x [F][VH]
     GemvParams ip = row_gemv();
-    ip.W = in_proj_; ip.N = VH; ip.K = LAT; ip.B = FR; ip.pro = PRO_F32; ip.x = C; ip.ldx = LAT;
+    ip.W = in_proj_; ip.N = VH; ip.K = LAT; ip.B = FR; ip.pro = PRO_F32; ip.x = C + (size_t)tail * LAT; ip.ldx = LAT;
     ip.bias = in_proj_b_; ip.out_f32 = A; ip.ldo = VH;
     if (!gemv(ip, s)) return false;
     float *x = A;
@@ -493,7 +538,12 @@ bool Vocoder::decode_rows(const int32_t *codes_dev, int F, float *pcm_dev, int64
             q.eps = 1e-5f; q.out_f32 = qkv; q.ldo = 3 * LAT;
             if (!gemv(q, s)) return false;
         }
-        if (!attn_prefill(qkv, rope_, att, F, n_heads_, head_dim_, s, nb_)) return false;
+        if (st) {
+            const size_t lo = (size_t)(&L - layers_.data()) * st->max_frames * LAT;   // this layer's cache
+            if (!voc_kv_append(qkv, st->rope, st->kc + lo, st->vc + lo, P, F, n_heads_, head_dim_, s) ||
+                !voc_attn_cached(qkv, st->kc + lo, st->vc + lo, att, P, F, n_heads_, head_dim_, s))
+                return false;
+        } else if (!attn_prefill(qkv, rope_, att, F, n_heads_, head_dim_, s, nb_)) return false;
         GemvParams o = row_gemv();
         o.W = L.o; o.N = VH; o.K = LAT; o.B = FR; o.pro = PRO_F16; o.x = att; o.ldx = LAT;
         o.scale = L.attn_scale; o.resid = x; o.ldr = VH; o.out_f32 = x; o.ldo = VH;
@@ -510,8 +560,22 @@ bool Vocoder::decode_rows(const int32_t *codes_dev, int F, float *pcm_dev, int64
     // final RMSNorm + output_proj + bias -> [F][LAT]   (:740-744)
     GemvParams op = row_gemv();
     op.W = out_proj_; op.N = LAT; op.K = VH; op.B = FR; op.pro = PRO_RMS; op.x = x; op.ldx = VH; op.nw = pre_norm_;
-    op.eps = 1e-5f; op.bias = out_proj_b_; op.out_f32 = B; op.ldo = LAT;
+    op.eps = 1e-5f; op.bias = out_proj_b_; op.out_f32 = B + (size_t)hrows * LAT; op.ldo = LAT;
     if (!gemv(op, s)) return false;
+    if (st) {
+        if (hrows) Q3T_HIP(hipMemcpyAsync(B, st->halo_rows, (size_t)hrows * LAT * 4, hipMemcpyDeviceToDevice, s));
+        const int keep = std::min(st->halo, P + F);   // the next push's halo: the last rows of [hrows + F]
+        if (keep)
+            Q3T_HIP(hipMemcpyAsync(st->halo_rows, B + (size_t)(hrows + F - keep) * LAT, (size_t)keep * LAT * 4,
+                                   hipMemcpyDeviceToDevice, s));
+    }
+    return true;
+}
+
+// Convolution half: the nb_ sequences of F frame rows [F][LAT] in buf_[1] -> PCM
+bool Vocoder::conv_stack(int F, float *pcm_dev, int64_t *n_out, hipStream_t s) {
+    const int LAT = latent_;
+    float *A = buf_[0], *B = buf_[1], *C = buf_[2];
     float *cur = B;
     float *f0 = A, *f1 = C;
     int64_t T = F;
@@ -671,6 +735,106 @@ bool Vocoder::decode_batch(int n_utt, const int32_t *const *codes, const int *n_
         Q3T_HIP(hipStreamSynchronize(stream_));
         i += nb;
     }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ streaming decode
+Vocoder::Stream *Vocoder::stream_open(int max_frames, int halo) {
+    if (!loaded_) { set_error("vocoder not loaded"); return nullptr; }
+    if (max_frames <= 0) { set_error("vocoder stream: max_frames must be > 0"); return nullptr; }
+    if (halo < 0) {
+        halo = stream_halo();
+        if (const char *e = std::getenv("Q3T_VOC_STREAM_HALO")) halo = std::atoi(e);
+    }
+    // a push starts `lead` samples before its first frame's boundary: the window must reach at least that far back
+    const int64_t rate = full_len(2) - full_len(1), lead = rate - full_len(1);
+    halo = std::max<int>(halo, lead > 0 ? (int)((lead + rate - 1) / rate) : 0);
+    halo = std::min(halo, max_frames);
+    const size_t L = layers_.size(), LAT = latent_;
+    const size_t kv = L * (size_t)max_frames * LAT * 4;
+    Stream *st = new Stream();
+    st->owner = this;
+    st->max_frames = max_frames;
+    st->halo = halo;
+    auto alloc = [&](size_t bytes) -> float * {
+        void *p = nullptr;
+        return hipMalloc(&p, std::max<size_t>(bytes, 16)) == hipSuccess ? (float *)p : nullptr;
+    };
+    st->kc = alloc(kv);
+    st->vc = alloc(kv);
+    st->rope = alloc((size_t)max_frames * head_dim_ * 4);
+    st->rvq_tail = alloc((size_t)2 * hidden_ * 4);
+    st->halo_rows = alloc((size_t)halo * LAT * 4);
+    if (!st->kc || !st->vc || !st->rope || !st->rvq_tail || !st->halo_rows) {
+        (void)hipGetLastError();
+        stream_close(st);
+        set_error("vocoder stream: cannot allocate the state of " + std::to_string(max_frames) + " frames (" +
+                  std::to_string((2 * kv) >> 20) + " MB of K/V cache)");
+        return nullptr;
+    }
+    // RoPE cos/sin by absolute position, the recurrence of ensure() (ggml_rope_cache_init)
+    std::vector<float> rope((size_t)max_frames * head_dim_);
+    const float theta_scale = powf(10000.0f, -2.0f / (float)head_dim_);
+    for (int p = 0; p < max_frames; ++p) {
+        float theta = (float)p;
+        for (int i0 = 0; i0 < head_dim_; i0 += 2) {
+            rope[(size_t)p * head_dim_ + i0] = cosf(theta);
+            rope[(size_t)p * head_dim_ + i0 + 1] = sinf(theta);
+            theta *= theta_scale;
+        }
+    }
+    if (hipMemcpy(st->rope, rope.data(), rope.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        stream_close(st);
+        set_error("vocoder stream: rope upload failed");
+        return nullptr;
+    }
+    streams_.push_back(st);
+    return st;
+}
+
+void Vocoder::stream_close(Stream *st) {
+    if (!st) return;
+    streams_.erase(std::remove(streams_.begin(), streams_.end(), st), streams_.end());
+    if (stream_) hipStreamSynchronize(stream_);   // a push in flight on the decoder's stream reads the state
+    for (float *p : {st->kc, st->vc, st->rope, st->rvq_tail, st->halo_rows})
+        if (p) hipFree(p);
+    delete st;
+}
+
+bool Vocoder::stream_push(Stream *st, const int32_t *codes, int n, float *pcm, int64_t pcm_cap, int64_t *n_out) {
+    if (n_out) *n_out = 0;
+    if (!st || std::find(streams_.begin(), streams_.end(), st) == streams_.end()) { set_error("vocoder stream: not an open stream"); return false; }
+    if (n <= 0) { set_error("vocoder stream: n_frames must be > 0"); return false; }
+    if (!codes || !pcm) { set_error("null argument"); return false; }
+    const int P = st->frames;
+    if ((int64_t)P + n > st->max_frames) {
+        set_error("vocoder stream: push of " + std::to_string(n) + " frames after " + std::to_string(P) +
+                  " exceeds max_frames " + std::to_string(st->max_frames));
+        return false;
+    }
+    const int64_t total = full_len(P + n), count = std::max<int64_t>(total - st->samples, 0);
+    if (pcm_cap < count) {
+        set_error("vocoder stream: pcm_cap " + std::to_string(pcm_cap) + " < " + std::to_string(count) + " samples of this push");
+        return false;
+    }
+    const int hrows = std::min(st->halo, P), W = hrows + n;   // window of the convolution stack, from frame P - hrows
+    if (!ensure(std::max(W, n + 2))) return false;
+    Q3T_HIP(hipMemcpyAsync(codes_, codes, (size_t)n * 16 * 4, hipMemcpyHostToDevice, stream_));
+    nb_ = 1;
+    int64_t nwin = 0;
+    if (!frame_rows(codes_, n, stream_, st)) return false;
+    // from here on the stream's state is that of P + n frames
+    st->frames = P + n;
+    st->samples = total;
+    if (!conv_stack(W, pcm_, &nwin, stream_)) return false;
+    // the window's decode is the full decode shifted by (P - hrows) * rate samples: keep what follows the samples
+    // already emitted
+    const int64_t rate = full_len(2) - full_len(1);
+    const int64_t off = (total - count) - (int64_t)(P - hrows) * rate;
+    if (off < 0 || off + count != nwin) { set_error("vocoder stream: window bookkeeping"); return false; }
+    if (count) Q3T_HIP(hipMemcpyAsync(pcm, pcm_ + off, (size_t)count * 4, hipMemcpyDeviceToHost, stream_));
+    Q3T_HIP(hipStreamSynchronize(stream_));
+    if (n_out) *n_out = count;
     return true;
 }
 

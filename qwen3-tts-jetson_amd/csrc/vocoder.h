@@ -38,6 +38,32 @@ public:
     // and the causal attention (QK^T + PV over the lower triangle), from the loaded shapes
     double decode_flops(int n_frames) const;   // codebooks divided by *.usage at load (0 for converter output)
 
+    // ---- streaming FULL decode: frames pushed in pieces of any size; the concatenated PCM of the pushes is, bit for
+    // bit, decode(all frames, mode 0).  The frame-rate part (RVQ .. output_proj) runs on the new rows only, against
+    // carried state; the convolution stack is recomputed over a window of `halo` earlier frames plus the new ones and
+    // the halo's samples are dropped (DESIGN 2c "Vocoder stream").  Several streams may be open; each owns its state,
+    // all share the decoder's scratch and serialise on its stream.
+    struct Stream {
+        Vocoder *owner = nullptr;
+        int device = 0;          // of the owning context (the C ABI's device lock)
+        int max_frames = 0, halo = 0;
+        int frames = 0;          // frames pushed so far (P)
+        int64_t samples = 0;     // samples emitted so far = n_samples(frames, 0)
+        float *kc = nullptr;     // [layers][max_frames][latent] f32 rotated keys
+        float *vc = nullptr;     // [layers][max_frames][latent] f32 values
+        float *rope = nullptr;   // [max_frames][head_dim] cos/sin by absolute position
+        float *rvq_tail = nullptr;   // [2][hidden] RVQ rows of the last min(2, frames) frames, oldest first (pre_conv k3)
+        float *halo_rows = nullptr;  // [halo][latent] output_proj rows of the last min(halo, frames) frames, oldest first
+    };
+    // look-back of the convolution stack in frames, derived from the loaded shapes (next to full_len)
+    int stream_halo() const;
+    // halo < 0: stream_halo(), or Q3T_VOC_STREAM_HALO when set (development knob); null + error when it does not fit
+    Stream *stream_open(int max_frames, int halo = -1);
+    // n_frames new frames of codes_host [n_frames][16] -> the next n_samples(P + n, 0) - n_samples(P, 0) samples.
+    // Bad arguments (n_frames <= 0, more than max_frames in total, pcm_cap too small) fail before any state changes
+    bool stream_push(Stream *st, const int32_t *codes_host, int n_frames, float *pcm_host, int64_t pcm_cap, int64_t *n_out);
+    void stream_close(Stream *st);
+
 private:
     struct Conv { uint16_t *w = nullptr; float *b = nullptr; int k = 0, ic = 0, oc = 0; };   // w: [k][oc][ic]
     struct Snake { float *a = nullptr, *ib = nullptr; int n = 0; };                          // exp(alpha), exp(-beta)
@@ -67,6 +93,11 @@ private:
     bool convT16(const Conv &c, const uint16_t *xh, int T, int stride, int trim, float *y, int T_out, uint16_t *y16,
                  const Snake *next, hipStream_t s);
     bool decode_rows(const int32_t *codes_dev, int F, float *pcm_dev, int64_t *n_out, hipStream_t s);
+    // decode_rows' two halves.  frame_rows: RVQ .. output_proj of F frame rows per utterance into buf_[1] (a stream's
+    // rows: against its state, written after the rows of its halo); conv_stack: upsample blocks .. output conv of the
+    // T-frame sequences in buf_[1]
+    bool frame_rows(const int32_t *codes_dev, int F, hipStream_t s, Stream *st);
+    bool conv_stack(int F, float *pcm_dev, int64_t *n_out, hipStream_t s);
 
     bool loaded_ = false;
     hipStream_t stream_ = nullptr;
@@ -94,6 +125,7 @@ private:
     int32_t *codes_ = nullptr;
     int *cols_ = nullptr;
     float *pcm_ = nullptr, *rope_ = nullptr;
+    std::vector<Stream *> streams_;   // open streams (freed with the decoder)
 };
 
 }  // namespace q3t

@@ -94,6 +94,15 @@ bool conv_out1(const uint16_t *xh, const uint16_t *w, const float *bias, float *
 bool dwconv(const float *x, const uint16_t *w, const float *b, float *y, int T, int C, int K, hipStream_t s, int nb = 1);
 // RoPE is applied to qkv's q and k columns in place; nb utterances of F frames each, causal within each
 bool attn_prefill(float *qkv, const float *rope, uint16_t *out, int F, int nH, int D, hipStream_t s, int nb = 1);
+// a vocoder stream's attention (Vocoder::stream_push): the n new frames at absolute positions P..P+n-1 against per-layer
+// f32 caches kc / vc [max_frames][nH*D] of rotated keys and of values, rope [max_frames][D] indexed by position.
+// voc_kv_append: attn_prefill's RoPE launch on the new rows -- q rotated in place in qkv [n][3*nH*D], rotated k and v
+// written to cache rows P..P+n-1 (the caller guarantees P + n <= max_frames; rows before P are not touched).
+// voc_attn_cached: out [n][nH*D] f16, bit-identical to rows P..P+n-1 of attn_prefill over the P + n frames; cache rows
+// at or past P + n are never read.
+bool voc_kv_append(float *qkv, const float *rope, float *kc, float *vc, int P, int n, int nH, int D, hipStream_t s);
+bool voc_attn_cached(const float *qkv, const float *kc, const float *vc, uint16_t *out, int P, int n, int nH, int D,
+                     hipStream_t s);
 bool codes_cols(const int32_t *codes, int *cols, int F, int ncb, hipStream_t s);
 
 }  // namespace q3t

@@ -1107,6 +1107,152 @@ bool attn_prefill(float *qkv, const float *rope, uint16_t *out, int F, int nH, i
     return true;
 }
 
+// ======================================================================================= streaming attention
+// The pre-transformer attention of a vocoder stream (Vocoder::stream_push): the n new frames sit at absolute positions
+// P..P+n-1, the keys and values of every frame so far in a per-layer f32 cache [max_frames][nH*64].
+// k_voc_kv_append is k_rope_qk on the new rows (q rotated in place; k rotated into the cache, v copied into it; the
+// same expressions, the rope table indexed by absolute position).
+__global__ void k_voc_kv_append(float *qkv, const float *rope, float *kc, float *vc, int P, int n, int nH) {
+    constexpr int D = 64;
+    const int idx = blockIdx.x * 256 + threadIdx.x;   // (row, q/k/v, head, pair)
+    const int total = n * 3 * nH * 32;
+    if (idx >= total) return;
+    const int i = idx & 31, hh = (idx >> 5) % (3 * nH), r = idx / (96 * nH);
+    float *x = qkv + (size_t)r * 3 * nH * D + hh * D;   // hh < nH: q head, < 2 nH: k head, else v head
+    const size_t pos = (size_t)P + r;
+    const float x0 = x[i], x1 = x[i + 32];
+    if (hh >= 2 * nH) {
+        float *dst = vc + pos * nH * D + (hh - 2 * nH) * D;
+        dst[i] = x0;
+        dst[i + 32] = x1;
+        return;
+    }
+    const float c = rope[pos * D + 2 * i], sn = rope[pos * D + 2 * i + 1];
+    float *dst = hh < nH ? x : kc + pos * nH * D + (hh - nH) * D;
+    // k_rope_qk's x0 * c - x1 * sn and x0 * sn + x1 * c as the compiler contracts them there (one product rounded,
+    // the other fused into the sum), written out: left to contraction, this kernel's different surroundings gave two
+    // rounded products and a sum, one ulp away.  tests/test_gpu_voc_stream_ops.py compares the two kernels' bits.
+    dst[i] = __builtin_fmaf(x0, c, -(x1 * sn));
+    dst[i + 32] = __builtin_fmaf(x0, sn, x1 * c);
+}
+
+// k_attn_prefill with the keys and values read from the cache: a second copy of its body rather than a shared
+// __device__ function, so that k_attn_prefill's own code is untouched.  Per query the arithmetic is k_attn_prefill's
+// for a sequence of Ft = P + n frames: query tiles stay aligned to absolute multiples of 32 (the first tile starts at
+// P rounded down, its queries before P are computed and not stored), key chunks of 64 from absolute key 0, the same
+// lane assignment, online-softmax update and P.V order, f16 output.  Cache rows at or past Ft are never loaded (rows
+// clamped to Ft - 1 and zeroed at the LDS store, as k_attn_prefill does past F).
+// qkv: the n new rows [n][3*nH*64] (q already rotated); out [n][nH*64] f16.
+__global__ void __launch_bounds__(512) k_voc_attn_cached(const float *qkv, const float *kc, const float *vc, uint16_t *out,
+                                                         int P, int n, int nH) {
+    constexpr int D = 64, QT = 32, KT = 64, KP = D + 4, LQ = 16;
+    __shared__ __attribute__((aligned(16))) float ks[KT * KP];
+    __shared__ __attribute__((aligned(16))) float vs[KT * KP];
+    __shared__ float ps[QT][KT + 1];
+    const int F = P + n;
+    const int h = blockIdx.y, q0 = (P / QT + blockIdx.x) * QT;
+    const int tid = threadIdx.x, qi = tid / LQ, g = tid % LQ;
+    const int LD = 3 * nH * D, LC = nH * D;
+    const int qpos = q0 + qi;
+    float q[D];
+    {
+        const float *src = qkv + (size_t)(max(min(qpos, F - 1), P) - P) * LD + h * D;
+#pragma unroll
+        for (int d = 0; d < D; d += 4) {
+            const float4 v = *reinterpret_cast<const float4 *>(src + d);
+            q[d] = v.x; q[d + 1] = v.y; q[d + 2] = v.z; q[d + 3] = v.w;
+        }
+    }
+    float m = -INFINITY, l = 0.0f, acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const float scale = 0.125f;   // 1 / sqrt(64)
+    const int kend = min(F, q0 + QT);
+    float4 kr4[2], vr4[2];
+    auto kv_load = [&](int k0) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int e = (u * 512 + tid) * 4, kk = e / D, d = e % D, pos = min(k0 + kk, F - 1);
+            kr4[u] = *reinterpret_cast<const float4 *>(kc + (size_t)pos * LC + h * D + d);
+            vr4[u] = *reinterpret_cast<const float4 *>(vc + (size_t)pos * LC + h * D + d);
+        }
+    };
+    kv_load(0);
+    for (int k0 = 0; k0 < kend; k0 += KT) {
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int e = (u * 512 + tid) * 4, kk = e / D, d = e % D;
+            const bool in = k0 + kk < F;
+            *reinterpret_cast<float4 *>(ks + kk * KP + d) = in ? kr4[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4 *>(vs + kk * KP + d) = in ? vr4[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        __syncthreads();
+        kv_load(min(k0 + KT, kend - 1));   // the next chunk (past the last: the last rows again, never stored)
+        float sc[4], mt = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int kk = g + LQ * i, kpos = k0 + kk;
+            const float *kr = ks + kk * KP;
+            float dsum = 0.0f;
+#pragma unroll
+            for (int d = 0; d < D; d += 4) {
+                const float4 kv = *reinterpret_cast<const float4 *>(kr + d);
+                dsum += q[d] * kv.x + q[d + 1] * kv.y + q[d + 2] * kv.z + q[d + 3] * kv.w;
+            }
+            sc[i] = (kpos <= qpos && kpos < F) ? dsum * scale : -INFINITY;
+            mt = fmaxf(mt, sc[i]);
+        }
+#pragma unroll
+        for (int o = 1; o < LQ; o <<= 1) mt = fmaxf(mt, __shfl_xor(mt, o));
+        const float mn = fmaxf(m, mt);
+        const float corr = m == -INFINITY ? 0.0f : expf(m - mn);
+        float ls = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float pv = sc[i] == -INFINITY ? 0.0f : expf(sc[i] - mn);
+            ps[qi][g + LQ * i] = pv;
+            ls += pv;
+        }
+#pragma unroll
+        for (int o = 1; o < LQ; o <<= 1) ls += __shfl_xor(ls, o);
+        l = l * corr + ls;
+        m = mn;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] *= corr;
+        __syncthreads();
+        const int kn = min(KT, kend - k0);
+        for (int kk = 0; kk < kn; ++kk) {
+            const float pv = ps[qi][kk];
+            const float4 a = *reinterpret_cast<const float4 *>(vs + kk * KP + g * 4);
+            acc[0] += pv * a.x; acc[1] += pv * a.y; acc[2] += pv * a.z; acc[3] += pv * a.w;
+        }
+    }
+    if (qpos >= P && qpos < F) {
+        const float inv = 1.0f / l;
+        uint2 o;
+        o.x = (uint32_t)f2h(acc[0] * inv) | ((uint32_t)f2h(acc[1] * inv) << 16);
+        o.y = (uint32_t)f2h(acc[2] * inv) | ((uint32_t)f2h(acc[3] * inv) << 16);
+        *reinterpret_cast<uint2 *>(out + (size_t)(qpos - P) * nH * D + h * D + g * 4) = o;
+    }
+}
+bool voc_kv_append(float *qkv, const float *rope, float *kc, float *vc, int P, int n, int nH, int D, hipStream_t s) {
+    if (D != 64) { set_error("voc_kv_append: head_dim must be 64"); return false; }
+    if (P < 0 || nH <= 0) { set_error("voc_kv_append: bad position or head count"); return false; }
+    if (n <= 0) return true;
+    hipLaunchKernelGGL(k_voc_kv_append, dim3((n * 3 * nH * 32 + 255) / 256), dim3(256), 0, s, qkv, rope, kc, vc, P, n, nH);
+    Q3T_HIP(hipGetLastError());
+    return true;
+}
+bool voc_attn_cached(const float *qkv, const float *kc, const float *vc, uint16_t *out, int P, int n, int nH, int D,
+                     hipStream_t s) {
+    if (D != 64) { set_error("voc_attn_cached: head_dim must be 64"); return false; }
+    if (P < 0 || nH <= 0) { set_error("voc_attn_cached: bad position or head count"); return false; }
+    if (n <= 0) return true;
+    const int tiles = (P + n + 31) / 32 - P / 32;
+    hipLaunchKernelGGL(k_voc_attn_cached, dim3(tiles, nH), dim3(512), 0, s, qkv, kc, vc, out, P, n, nH);
+    Q3T_HIP(hipGetLastError());
+    return true;
+}
+
 // codes [F][ncb] -> per-codebook index columns [ncb][F]
 __global__ void k_codes_cols(const int32_t *codes, int *cols, int F, int ncb) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

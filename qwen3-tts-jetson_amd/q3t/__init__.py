@@ -6,6 +6,7 @@ q3t_last_error() when the C ABI reports failure (the reference's bool + get_erro
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -80,6 +81,16 @@ _lib.q3t_vocoder_decode_chunked.argtypes = [_P, _ip, C.c_int32, C.c_int32, C.c_i
 _lib.q3t_vocoder_decode_batch.argtypes = [_P, C.c_int32, C.POINTER(C.c_void_p), _ip, _I, C.c_int32,
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
 _lib.q3t_vocoder_set_batch_frames.argtypes = [_P, C.c_int32]
+_lib.q3t_vocoder_stream_open.argtypes = [_P, C.c_int32, C.POINTER(_P)]
+_lib.q3t_vocoder_stream_push.argtypes = [_P, _P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]
+_lib.q3t_vocoder_stream_samples.restype = C.c_int64
+_lib.q3t_vocoder_stream_samples.argtypes = [_P]
+_lib.q3t_vocoder_stream_frames.restype = C.c_int32
+_lib.q3t_vocoder_stream_frames.argtypes = [_P]
+_lib.q3t_vocoder_stream_halo.restype = C.c_int32
+_lib.q3t_vocoder_stream_halo.argtypes = [_P]
+_lib.q3t_vocoder_stream_close.restype = None
+_lib.q3t_vocoder_stream_close.argtypes = [_P]
 _lib.q3t_speaker_dim.argtypes = [_P]
 _lib.q3t_ctx_create_speaker.argtypes = [C.c_char_p, _I, C.POINTER(_P)]
 _lib.q3t_speaker_encode.argtypes = [_P, _fp, C.c_int32, _fp]
@@ -101,7 +112,9 @@ _lib.q3t_prefill_embd.argtypes = [_P, _ip, _I, _P, _I, _fp, C.POINTER(C.c_int32)
 EXPORTS = ["q3t_last_error", "q3t_default_params", "q3t_ctx_create", "q3t_ctx_destroy", "q3t_get_config",
            "q3t_generate", "q3t_generate_stream", "q3t_generate_queue", "q3t_comm_unique_id", "q3t_ctx_create_shared",
            "q3t_plan_weight_layout", "q3t_ctx_create_replica", "q3t_comm_allreduce_max", "q3t_set_mfma_min_batch", "q3t_synchronize", "q3t_last_timing", "q3t_time_stage", "q3t_persist_status", "q3t_persist_kernels", "q3t_vocoder_num_samples", "q3t_vocoder_flops", "q3t_vocoder_decode",
-           "q3t_vocoder_decode_chunked", "q3t_vocoder_decode_batch", "q3t_vocoder_set_batch_frames", "q3t_speaker_dim", "q3t_ctx_create_speaker", "q3t_speaker_encode", "q3t_speaker_mel",
+           "q3t_vocoder_decode_chunked", "q3t_vocoder_decode_batch", "q3t_vocoder_set_batch_frames",
+           "q3t_vocoder_stream_open", "q3t_vocoder_stream_push", "q3t_vocoder_stream_samples",
+           "q3t_vocoder_stream_frames", "q3t_vocoder_stream_halo", "q3t_vocoder_stream_close", "q3t_speaker_dim", "q3t_ctx_create_speaker", "q3t_speaker_encode", "q3t_speaker_mel",
            "q3t_tokenizer_load", "q3t_tokenizer_free", "q3t_tokenizer_info", "q3t_tokenizer_encode",
            "q3t_tokenizer_decode", "q3t_talker_forward", "q3t_talker_prefill",
            "q3t_codepred_frame", "q3t_cb0_select", "q3t_project_text", "q3t_prefill_embd", "gpu_fp32_to_fp16",
@@ -195,6 +208,64 @@ class Tokenizer:
         return buf.raw[:nb.value]
 
 
+class VocoderStream:
+    """A streaming FULL vocoder decode (q3t_vocoder_stream_*): push() frames in pieces of any size; the concatenated
+    PCM equals Engine.vocoder(all codes) bit for bit.  Closed with the engine at the latest."""
+
+    def __init__(self, engine, max_frames=4096):
+        self.engine = engine
+        h = _P()
+        _check(_lib.q3t_vocoder_stream_open(engine.h, int(max_frames), C.byref(h)))
+        self.h = h
+        engine._streams.add(self)
+
+    def _handle(self):
+        if not getattr(self, "h", None) or not self.engine.h:
+            raise Q3TError("vocoder stream is closed")
+        return self.h
+
+    def push(self, codes):
+        """codes [n][16] int32 -> the next samples (float32)"""
+        codes = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
+        h, n = self._handle(), codes.shape[0]
+        cap = max(self.engine.vocoder_num_samples(self.frames + n, VOCODER_FULL) - self.samples, 0) if n > 0 else 0
+        pcm = np.zeros(max(cap, 1), np.float32)
+        ns = C.c_int64(0)
+        _check(_lib.q3t_vocoder_stream_push(h, _addr(codes), n, _addr(pcm), cap, C.byref(ns)))
+        return pcm[:ns.value]
+
+    @property
+    def frames(self):
+        return _lib.q3t_vocoder_stream_frames(self._handle())
+
+    @property
+    def samples(self):
+        return _lib.q3t_vocoder_stream_samples(self._handle())
+
+    @property
+    def halo(self):
+        return _lib.q3t_vocoder_stream_halo(self._handle())
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self.engine.h:   # a destroyed context has already freed its streams
+                _lib.q3t_vocoder_stream_close(self.h)
+            self.h = None
+            self.engine._streams.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """One device context (TTSTransformer + code predictor + vocoder resident in HBM)."""
 
@@ -206,6 +277,7 @@ class Engine:
                                        int(device), int(max_slots), int(max_ctx), C.byref(h)))
             _handle = h
         self.h = _handle
+        self._streams = weakref.WeakSet()   # open VocoderStreams (the context frees them when it is destroyed)
         c = Config()
         _check(_lib.q3t_get_config(self.h, C.byref(c)))
         self.cfg = {n: getattr(c, n) for n, _ in Config._fields_}
@@ -240,6 +312,8 @@ class Engine:
 
     def close(self):
         if getattr(self, "h", None):
+            for st in list(getattr(self, "_streams", [])):
+                st.close()
             _lib.q3t_ctx_destroy(self.h)
             self.h = None
 
@@ -388,6 +462,10 @@ class Engine:
         ns = (C.c_int64 * max(n, 1))()
         _check(_lib.q3t_vocoder_decode_batch(self.h, n, cp, nf, int(mode), int(chunk_frames), pp, ns))
         return [pcms[i][:ns[i]] for i in range(n)]
+
+    def vocoder_stream(self, max_frames=4096):
+        """a VocoderStream on this context: .push(codes) -> float32 PCM, .frames, .samples, .halo, .close()"""
+        return VocoderStream(self, max_frames)
 
     def vocoder_set_batch_frames(self, frames):
         _check(_lib.q3t_vocoder_set_batch_frames(self.h, int(frames)))

@@ -444,16 +444,10 @@ bool Engine::alloc_state() {
     slot_iota_ = dalloc<int>(S);
     trailing_ = dalloc<float>((size_t)S * max_trailing_ * H);
     tts_pad_ = dalloc<float>((size_t)S * H);
-    prefill_ = dalloc<float>((size_t)S * 10 * H);
     codes_max_len_ = max_ctx_;
     codes_ = dalloc<int32_t>((size_t)S * codes_max_len_ * 16);
-    proj_cap_ = S * (max_trailing_ + 16);
-    proj_idx_ = dalloc<int>(proj_cap_);
-    proj_h_ = dalloc<uint16_t>((size_t)proj_cap_ * c_.text_dim);
-    proj_out_ = dalloc<float>((size_t)proj_cap_ * H);
-    recipe_cap_ = S * (max_trailing_ + 16);
-    recipe_ = dalloc<RowRecipe>(recipe_cap_);
-    if (!x_ || !kc_ || !vc_ || !recipe_ || !proj_out_) { set_error("device allocation failed"); return false; }
+    if (!alloc_prompt_scratch(main_ps_, cp_in1_)) return false;
+    if (!x_ || !kc_ || !vc_) { set_error("device allocation failed"); return false; }
     std::vector<int> cpp((size_t)16 * S);
     for (int p = 0; p < 16; ++p) for (int s = 0; s < S; ++s) cpp[(size_t)p * S + s] = p;
     Q3T_HIP(hipMemcpyAsync(cp_pos_, cpp.data(), cpp.size() * 4, hipMemcpyHostToDevice, stream_));
@@ -1290,20 +1284,28 @@ bool Engine::graph_for(std::map<int, hipGraphExec_t> &cache, int S, bool (Engine
     return graph_for_key(cache, S, S, fn);
 }
 
-bool Engine::graph_for_key(std::map<int, hipGraphExec_t> &cache, int key, int S, bool (Engine::*fn)(int, hipStream_t)) {
-    if (cache.count(key)) return true;
+// what `enqueue` launches on stream s, as an executable graph
+template <class F>
+hipGraphExec_t Engine::capture(hipStream_t s, F &&enqueue) {
     hipGraph_t graph = nullptr;
-    Q3T_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-    const bool ok = (this->*fn)(S, stream_);
-    hipError_t e = hipStreamEndCapture(stream_, &graph);
-    if (!ok) { if (graph) hipGraphDestroy(graph); return false; }
-    if (e != hipSuccess) { set_error(std::string("graph capture: ") + hipGetErrorString(e)); return false; }
+    hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) { set_error(std::string("graph capture: ") + hipGetErrorString(e)); return nullptr; }
+    const bool ok = enqueue();
+    e = hipStreamEndCapture(s, &graph);
+    if (!ok) { if (graph) hipGraphDestroy(graph); return nullptr; }
+    if (e != hipSuccess) { set_error(std::string("graph capture: ") + hipGetErrorString(e)); return nullptr; }
     hipGraphExec_t exec = nullptr;
     e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     hipGraphDestroy(graph);
-    if (e != hipSuccess) { set_error(std::string("graph instantiate: ") + hipGetErrorString(e)); return false; }
-    cache[key] = exec;
-    return true;
+    if (e != hipSuccess) { set_error(std::string("graph instantiate: ") + hipGetErrorString(e)); return nullptr; }
+    return exec;
+}
+
+bool Engine::graph_for_key(std::map<int, hipGraphExec_t> &cache, int key, int S, bool (Engine::*fn)(int, hipStream_t)) {
+    if (cache.count(key)) return true;
+    hipGraphExec_t exec = capture(stream_, [&] { return (this->*fn)(S, stream_); });
+    if (exec) cache[key] = exec;
+    return exec != nullptr;
 }
 
 bool Engine::set_slot_state(int S, const std::vector<int> &pos, const std::vector<int> &frame) {
@@ -1378,16 +1380,8 @@ bool Engine::prefill(int n_utt, int plen, const float *src, int S_main, hipStrea
                              hipMemcpyDeviceToDevice, s));
     const int key = (S_main * 1024 + n_utt) * 16 + plen;
     if (!g_prefill_.count(key)) {
-        hipGraph_t graph = nullptr;
-        Q3T_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const bool ok = enqueue_prefill_rows(key, s);
-        hipError_t e = hipStreamEndCapture(s, &graph);
-        if (!ok) { if (graph) hipGraphDestroy(graph); return false; }
-        if (e != hipSuccess) { set_error(std::string("graph capture: ") + hipGetErrorString(e)); return false; }
-        hipGraphExec_t exec = nullptr;
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (e != hipSuccess) { set_error(std::string("graph instantiate: ") + hipGetErrorString(e)); return false; }
+        hipGraphExec_t exec = capture(s, [&] { return enqueue_prefill_rows(key, s); });
+        if (!exec) return false;
         g_prefill_[key] = exec;
     }
     Q3T_HIP(hipGraphLaunch(g_prefill_[key], s));
@@ -1395,33 +1389,42 @@ bool Engine::prefill(int n_utt, int plen, const float *src, int S_main, hipStrea
 }
 
 // ------------------------------------------------------------------------------------------ prefill pieces
-bool Engine::enqueue_text_projection(int n_rows, hipStream_t s) {
-    return enqueue_text_projection(n_rows, s, proj_idx_, proj_h_, proj_out_);
+bool Engine::alloc_prompt_scratch(PromptScratch &ps, float *spk) {
+    const int S = max_slots_, H = c_.hidden;
+    ps.cap = S * (max_trailing_ + 16);
+    ps.idx = dalloc<int>(ps.cap);
+    ps.h = dalloc<uint16_t>((size_t)ps.cap * c_.text_dim);
+    ps.out = dalloc<float>((size_t)ps.cap * H);
+    ps.recipe = dalloc<RowRecipe>(ps.cap);
+    ps.rows = dalloc<float>((size_t)S * 10 * H);
+    ps.spk = spk ? spk : dalloc<float>((size_t)S * H);
+    if (!ps.idx || !ps.h || !ps.out || !ps.recipe || !ps.rows || !ps.spk) { set_error("device allocation failed"); return false; }
+    return true;
 }
 
-bool Engine::enqueue_text_projection(int n_rows, hipStream_t s, const int *idx, uint16_t *hbuf, float *out) {
+bool Engine::enqueue_text_projection(int n_rows, hipStream_t s, const PromptScratch &ps) {
     // text_embd row gather -> fc1 + b -> SiLU -> fc2 + b   (tts_transformer.cpp:1050-1055)
     GemvParams a;
     a.W = fc1_; a.N = c_.text_dim; a.K = c_.text_dim; a.B = n_rows;
-    a.pro = PRO_F16; a.x = text_embd_; a.ldx = c_.text_dim; a.x_idx = idx;
-    a.bias = fc1_b_; a.act = ACT_SILU; a.out_f16 = hbuf; a.ldo = c_.text_dim;
+    a.pro = PRO_F16; a.x = text_embd_; a.ldx = c_.text_dim; a.x_idx = ps.idx;
+    a.bias = fc1_b_; a.act = ACT_SILU; a.out_f16 = ps.h; a.ldo = c_.text_dim;
     if (!gemv(a, s)) return false;
     GemvParams b;
     b.W = fc2_; b.N = c_.hidden; b.K = c_.text_dim; b.B = n_rows;
-    b.pro = PRO_F16; b.x = hbuf; b.ldx = c_.text_dim;
-    b.bias = fc2_b_; b.out_f32 = out; b.ldo = c_.hidden;
+    b.pro = PRO_F16; b.x = ps.h; b.ldx = c_.text_dim;
+    b.bias = fc2_b_; b.out_f32 = ps.out; b.ldo = c_.hidden;
     return gemv(b, s);
 }
 
 bool Engine::project_text(int n, const int32_t *toks, float *out) {
     if (n <= 0) return true;
-    if (n > proj_cap_) { set_error("too many text rows"); return false; }
+    if (n > main_ps_.cap) { set_error("too many text rows"); return false; }
     DeviceLock lk(false, device_);
     for (int i = 0; i < n; ++i)
         if (toks[i] < 0 || toks[i] >= c_.text_vocab) { set_error("text token out of range"); return false; }
-    Q3T_HIP(hipMemcpyAsync(proj_idx_, toks, n * 4, hipMemcpyHostToDevice, stream_));
-    if (!enqueue_text_projection(n, stream_)) return false;
-    Q3T_HIP(hipMemcpyAsync(out, proj_out_, (size_t)n * c_.hidden * 4, hipMemcpyDeviceToHost, stream_));
+    Q3T_HIP(hipMemcpyAsync(main_ps_.idx, toks, n * 4, hipMemcpyHostToDevice, stream_));
+    if (!enqueue_text_projection(n, stream_, main_ps_)) return false;
+    Q3T_HIP(hipMemcpyAsync(out, main_ps_.out, (size_t)n * c_.hidden * 4, hipMemcpyDeviceToHost, stream_));
     Q3T_HIP(hipStreamSynchronize(stream_));
     return true;
 }
@@ -1452,54 +1455,77 @@ static bool plan_rows(const Config &c, int n_utt, const int32_t *const *tokens, 
     return true;
 }
 
+// rows of a prompt: 3 text rows, then one per entry of the codec input [think | nothink, think_bos, (language),
+// think_eos, (speaker), pad, bos]
+int Engine::prompt_len(int language_id, bool has_spk) {
+    return 3 + (language_id < 0 ? 3 : 4) + (has_spk ? 1 : 0) + 2;
+}
+
+bool Engine::assemble_prompts(PromptScratch &ps, hipStream_t s, const std::vector<PromptEntry> &in, int language_id,
+                              int *plen_out, std::vector<int> &trailing_len) {
+    const int H = c_.hidden, n = (int)in.size();
+    if (language_id >= c_.codec_vocab) { set_error("language id out of range"); return false; }
+    std::vector<const int32_t *> tk(n);
+    std::vector<int> nt(n), &idx = ps.idx_host;
+    for (int j = 0; j < n; ++j) { tk[j] = in[j].tokens; nt[j] = in[j].n_tokens; }
+    std::vector<SlotPlan> plan;
+    if (!plan_rows(c_, n, tk.data(), nt.data(), max_trailing_, idx, plan)) return false;
+    if ((int)idx.size() > ps.cap) { set_error("too many text rows"); return false; }
+    // ---- text projection for every entry, one batched pass
+    Q3T_HIP(hipMemcpyAsync(ps.idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, s));
+    if (!enqueue_text_projection((int)idx.size(), s, ps)) return false;
+    // ---- prompt / trailing / pad rows
+    const int plen = prompt_len(language_id, n > 0 && in[0].speaker);
+    std::vector<RowRecipe> &rec = ps.recipe_host;
+    rec.clear();
+    auto crow = [&](int id) { return RowTerm{codec_embd_ + (size_t)id * H, 1}; };
+    trailing_len.resize(n);
+    for (int j = 0; j < n; ++j) {
+        const SlotPlan &p = plan[j];
+        const int k = in[j].slot;
+        float *spk_dev = ps.spk + (size_t)k * H;
+        if (in[j].speaker) Q3T_HIP(hipMemcpyAsync(spk_dev, in[j].speaker, H * 4, hipMemcpyHostToDevice, s));
+        const float *P = ps.out + (size_t)p.rb * H;
+        auto prow = [&](int i) { return RowTerm{P + (size_t)i * H, 0}; };
+        auto row = [&](float *dst, RowTerm a, RowTerm b = {nullptr, 0}) { rec.push_back(RowRecipe{dst, {a, b, {nullptr, 0}}}); };
+        std::vector<RowTerm> cin;
+        if (language_id < 0) cin = {crow(c_.nothink), crow(c_.think_bos), crow(c_.think_eos)};
+        else cin = {crow(c_.think), crow(c_.think_bos), crow(language_id), crow(c_.think_eos)};
+        if (in[j].speaker) cin.push_back(RowTerm{spk_dev, 0});
+        cin.push_back(crow(c_.codec_pad));
+        cin.push_back(crow(c_.codec_bos));
+        const int ol = (int)cin.size() - 1;
+        if (3 + ol + 1 != plen) { set_error("prompt assembly: prefill length mismatch"); return false; }
+        float *out = ps.rows + (size_t)in[j].row * 10 * H;
+        for (int r = 0; r < 3; ++r) row(out + (size_t)r * H, prow(3 + r));
+        for (int t = 0; t < ol; ++t) row(out + (size_t)(3 + t) * H, t == ol - 1 ? prow(0) : prow(2), cin[t]);
+        row(out + (size_t)(plen - 1) * H, prow(6), cin.back());
+        float *tr = trailing_ + (size_t)k * max_trailing_ * H;
+        for (int i = 0; i < p.tcount; ++i) row(tr + (size_t)i * H, prow(7 + i));
+        row(tr + (size_t)p.tcount * H, prow(1));
+        row(tts_pad_ + (size_t)k * H, prow(2));
+        trailing_len[j] = p.tcount + 1;
+    }
+    if ((int)rec.size() > ps.cap) { set_error("recipe overflow"); return false; }
+    Q3T_HIP(hipMemcpyAsync(ps.recipe, rec.data(), rec.size() * sizeof(RowRecipe), hipMemcpyHostToDevice, s));
+    *plen_out = plen;
+    return rows_recipe(ps.recipe, (int)rec.size(), H, s);
+}
+
 bool Engine::prefill_embd(const int32_t *toks, int n, const float *spk, int language_id, float *prefill, int *prefill_len,
                           float *trailing, int *trailing_len, float *tts_pad) {
     // host entry for the parity tests: run the same device assembly as generate() on slot 0
     DeviceLock lk(false, device_);
-    const int32_t *tk[1] = {toks};
-    std::vector<int> idx;
-    std::vector<SlotPlan> plan;
-    if (!plan_rows(c_, 1, tk, &n, max_trailing_, idx, plan)) return false;
-    GenParams gp = gp_;
-    gp.language_id = language_id;
-    (void)gp;
     const int H = c_.hidden;
-    Q3T_HIP(hipMemcpyAsync(proj_idx_, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, stream_));
-    if (!enqueue_text_projection((int)idx.size(), stream_)) return false;
-    float *spk_dev = nullptr;
-    if (spk) {
-        spk_dev = cp_in1_;   // scratch
-        Q3T_HIP(hipMemcpyAsync(spk_dev, spk, H * 4, hipMemcpyHostToDevice, stream_));
-    }
-    // recipe (same as generate)
-    std::vector<RowRecipe> rec;
-    const SlotPlan &p = plan[0];
-    const float *P = proj_out_ + (size_t)p.rb * H;
-    auto prow = [&](int i) { return RowTerm{P + (size_t)i * H, 0}; };
-    auto crow = [&](int id) { return RowTerm{codec_embd_ + (size_t)id * H, 1}; };
-    std::vector<RowTerm> cin;
-    if (language_id < 0) { cin = {crow(c_.nothink), crow(c_.think_bos), crow(c_.think_eos)}; }
-    else { cin = {crow(c_.think), crow(c_.think_bos), crow(language_id), crow(c_.think_eos)}; }
-    if (language_id >= c_.codec_vocab) { set_error("language id out of range"); return false; }
-    if (spk) cin.push_back(RowTerm{spk_dev, 0});
-    cin.push_back(crow(c_.codec_pad));
-    cin.push_back(crow(c_.codec_bos));
-    const int ol = (int)cin.size() - 1, plen = 3 + ol + 1;
-    float *out = prefill_;
-    for (int r = 0; r < 3; ++r) rec.push_back(RowRecipe{out + (size_t)r * H, {prow(3 + r), {nullptr, 0}, {nullptr, 0}}});
-    for (int t = 0; t < ol; ++t) rec.push_back(RowRecipe{out + (size_t)(3 + t) * H, {t == ol - 1 ? prow(0) : prow(2), cin[t], {nullptr, 0}}});
-    rec.push_back(RowRecipe{out + (size_t)(plen - 1) * H, {prow(6), cin.back(), {nullptr, 0}}});
-    for (int i = 0; i < p.tcount; ++i) rec.push_back(RowRecipe{trailing_ + (size_t)i * H, {prow(7 + i), {nullptr, 0}, {nullptr, 0}}});
-    rec.push_back(RowRecipe{trailing_ + (size_t)p.tcount * H, {prow(1), {nullptr, 0}, {nullptr, 0}}});
-    rec.push_back(RowRecipe{tts_pad_, {prow(2), {nullptr, 0}, {nullptr, 0}}});
-    Q3T_HIP(hipMemcpyAsync(recipe_, rec.data(), rec.size() * sizeof(RowRecipe), hipMemcpyHostToDevice, stream_));
-    if (!rows_recipe(recipe_, (int)rec.size(), H, stream_)) return false;
-    Q3T_HIP(hipMemcpyAsync(prefill, prefill_, (size_t)plen * H * 4, hipMemcpyDeviceToHost, stream_));
-    Q3T_HIP(hipMemcpyAsync(trailing, trailing_, (size_t)(p.tcount + 1) * H * 4, hipMemcpyDeviceToHost, stream_));
+    int plen = 0;
+    std::vector<int> tl;
+    if (!assemble_prompts(main_ps_, stream_, {PromptEntry{toks, n, spk, 0, 0}}, language_id, &plen, tl)) return false;
+    Q3T_HIP(hipMemcpyAsync(prefill, main_ps_.rows, (size_t)plen * H * 4, hipMemcpyDeviceToHost, stream_));
+    Q3T_HIP(hipMemcpyAsync(trailing, trailing_, (size_t)tl[0] * H * 4, hipMemcpyDeviceToHost, stream_));
     Q3T_HIP(hipMemcpyAsync(tts_pad, tts_pad_, (size_t)H * 4, hipMemcpyDeviceToHost, stream_));
     Q3T_HIP(hipStreamSynchronize(stream_));
     *prefill_len = plen;
-    *trailing_len = p.tcount + 1;
+    *trailing_len = tl[0];
     return true;
 }
 
@@ -1526,7 +1552,7 @@ bool Engine::generate(int n_utt, const int32_t *const *tokens, const int *n_toke
                       const GenParams &gp, int32_t *codes, int *n_frames, FrameCb on_frames, void *user, int interval) {
     if (n_utt <= 0) return true;
     if (n_utt > max_slots_) { set_error("n_utt exceeds max_slots"); return false; }
-    // only single-slot runs launch the persistent kernels: batched contexts on one device run concurrently
+    // a run that launches a persistent grid holds the device alone (persist_exclusive); the others share it
     DeviceLock lk(persist_exclusive(n_utt), device_);
     StreamState st;
     st.delivered.assign(n_utt, 0);
@@ -1541,6 +1567,145 @@ bool Engine::generate(int n_utt, const int32_t *const *tokens, const int *n_toke
     return generate_once(n_utt, tokens, n_tokens, speaker, gp, codes, n_frames, on_frames, user, interval, st, &fault);
 }
 
+namespace {
+// a HIP event for the length of a scope
+struct Event {
+    hipEvent_t ev = nullptr;
+    explicit Event(unsigned flags = hipEventDefault) { hipEventCreateWithFlags(&ev, flags); }
+    ~Event() { if (ev) hipEventDestroy(ev); }
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    operator hipEvent_t() const { return ev; }   // null if the creation failed: the first use reports it
+};
+// runs f on every exit of the scope
+template <class F>
+struct ScopeExit {
+    F f;
+    explicit ScopeExit(F fn) : f(std::move(fn)) {}
+    ~ScopeExit() { f(); }
+    ScopeExit(const ScopeExit &) = delete;
+    ScopeExit &operator=(const ScopeExit &) = delete;
+};
+}  // namespace
+
+bool Engine::check_gen_args(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
+                            const GenParams &gp, int *plen) {
+    if (gp.language_id >= c_.codec_vocab) { set_error("language id out of range"); return false; }
+    const bool has_spk = speaker && speaker[0];
+    for (int u = 0; u < n_utt; ++u)
+        if ((speaker && speaker[u]) != has_spk) { set_error("speaker embedding must be given for all or none of the utterances"); return false; }
+    std::vector<int> idx;   // every prompt is validated before anything runs
+    std::vector<SlotPlan> plan;
+    if (!plan_rows(c_, n_utt, tokens, n_tokens, max_trailing_, idx, plan)) return false;
+    *plen = prompt_len(gp.language_id, has_spk);
+    if (*plen + gp.max_len + 8 > max_ctx_) { set_error("max_len exceeds the context reserved at ctx creation"); return false; }
+    return true;
+}
+
+void Engine::set_gen_params(const GenParams &gp) {
+    if (!(gp.temperature == gp_.temperature && gp.top_k == gp_.top_k && gp.rep_penalty == gp_.rep_penalty)) {
+        for (auto &kv : g_frame_) hipGraphExecDestroy(kv.second);
+        g_frame_.clear();
+    }
+    gp_ = gp;
+}
+
+// streaming (frame callback) of generate(): chunk [start, start+interval) of every slot is copied to pinned memory
+// behind the frame that completes it and delivered one chunk late, so the GPU keeps running the queued frames
+// meanwhile.  The pinned chunks are the context's (chunk_pool_), reused across calls.
+class Engine::ChunkStreamer {
+public:
+    ChunkStreamer(Engine &e, int S, int max_len, FrameCb cb, void *user, int interval, StreamState &st, bool *fault)
+        : e_(e), S_(S), max_len_(max_len), interval_(interval), cb_(cb), user_(user), st_(st), fault_(fault), n_live_(S) {}
+    bool active() const { return cb_ && interval_ > 0; }
+    // utterances the callback has not stopped (a fallback re-run regenerates utterances stopped earlier too: their
+    // frames are returned)
+    int n_live() const { return n_live_; }
+    // frame f was launched: if it completes a chunk, queue the chunk's copy behind it and deliver the chunk before
+    bool after_frame(int f) {
+        if (!active() || (f + 1) % interval_ != 0) return true;
+        Chunk c;
+        if (!pool_.empty()) { c = pool_.back(); pool_.pop_back(); }
+        else if (!take_chunk(c)) return false;
+        c.start = f + 1 - interval_;
+        for (int s = 0; s < S_; ++s)
+            Q3T_HIP(hipMemcpyAsync(c.codes + (size_t)s * interval_ * NCB, e_.codes_ + ((size_t)s * e_.codes_max_len_ + c.start) * NCB,
+                                   (size_t)interval_ * NCB * 4, hipMemcpyDeviceToHost, e_.stream_));
+        Q3T_HIP(hipMemcpyAsync(c.done, e_.done_, S_ * 4, hipMemcpyDeviceToHost, e_.stream_));
+        Q3T_HIP(hipEventRecord(c.ev, e_.stream_));
+        pend_.push_back(c);
+        if (pend_.size() == 1) return true;
+        Chunk front = pend_.front();
+        pend_.erase(pend_.begin());
+        pool_.push_back(front);
+        if (deliver(front)) return true;
+        hipStreamSynchronize(e_.stream_);
+        return false;
+    }
+    // after the last frame (codes: the caller's [S][max_len][16], n_frames: each utterance's length): the chunks still
+    // pending, then the remainder of every utterance (tts_transformer.cpp:2563-2570)
+    bool flush(const int32_t *codes, int *n_frames) {
+        if (!active()) return true;
+        for (Chunk &c : pend_)
+            if (!deliver(c)) return false;
+        for (int s = 0; s < S_; ++s) {
+            if (st_.stop_at[s] >= 0) { n_frames[s] = std::min(n_frames[s], st_.stop_at[s]); continue; }
+            if (n_frames[s] > st_.delivered[s])
+                cb_(user_, s, codes + ((size_t)s * max_len_ + st_.delivered[s]) * NCB, n_frames[s] - st_.delivered[s], NCB);
+        }
+        return true;
+    }
+
+private:
+    static constexpr int NCB = 16;
+    struct Chunk { int start; int32_t *codes; int *done; hipEvent_t ev; };
+    bool take_chunk(Chunk &c) {   // the next pinned chunk of the context's pool, grown to this call's chunk size
+        const size_t chunk_bytes = ((size_t)S_ * interval_ * NCB + S_) * 4;
+        if (next_chunk_ == e_.chunk_pool_.size()) e_.chunk_pool_.push_back(PinnedChunk{});
+        PinnedChunk &pc = e_.chunk_pool_[next_chunk_++];
+        if (pc.cap < chunk_bytes) {
+            if (pc.codes) hipHostFree(pc.codes);
+            pc.codes = nullptr;
+            pc.cap = 0;
+            Q3T_HIP(hipHostMalloc(&pc.codes, chunk_bytes, hipHostMallocDefault));
+            pc.cap = chunk_bytes;
+        }
+        if (!pc.ev) Q3T_HIP(hipEventCreateWithFlags(&pc.ev, hipEventDisableTiming));
+        c.codes = pc.codes;
+        c.done = pc.codes + (size_t)S_ * interval_ * NCB;
+        c.ev = pc.ev;
+        return true;
+    }
+    // a chunk is handed to the caller only once the persistent kernels behind it are known to be fault-free
+    bool deliver(Chunk &c) {
+        Q3T_HIP(hipEventSynchronize(c.ev));
+        if (e_.persist_error()) { *fault_ = true; return false; }
+        for (int s = 0; s < S_; ++s) {
+            if (st_.stop_at[s] >= 0) continue;
+            const int nf = c.done[s] >= 0 ? c.done[s] : max_len_;
+            if (nf < c.start + interval_) continue;   // partial chunks go to the final flush, as in the reference
+            if (c.start + interval_ <= st_.delivered[s]) continue;   // delivered before a fallback re-run
+            st_.delivered[s] = c.start + interval_;
+            if (!cb_(user_, s, c.codes + (size_t)s * interval_ * NCB, interval_, NCB)) {
+                const int d = st_.stop_at[s] = c.start + interval_;
+                Q3T_HIP(hipMemcpyAsync(e_.done_ + s, &d, 4, hipMemcpyHostToDevice, e_.stream_));
+                Q3T_HIP(hipStreamSynchronize(e_.stream_));   // &d is a stack value
+                --n_live_;
+            }
+        }
+        return true;
+    }
+    Engine &e_;
+    const int S_, max_len_, interval_;
+    const FrameCb cb_;
+    void *const user_;
+    StreamState &st_;
+    bool *const fault_;
+    int n_live_;
+    size_t next_chunk_ = 0;           // chunk_pool_[0, next_chunk_) are in use by this call
+    std::vector<Chunk> pend_, pool_;  // copies in flight, oldest first; chunks delivered and free for reuse
+};
+
 bool Engine::generate_once(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                            const GenParams &gp, int32_t *codes, int *n_frames, FrameCb on_frames, void *user,
                            int interval, StreamState &st, bool *fault) {
@@ -1548,61 +1713,18 @@ bool Engine::generate_once(int n_utt, const int32_t *const *tokens, const int *n
     const int S = n_utt, H = c_.hidden, NCB = 16;
     for (int s = 0; s < S; ++s) n_frames[s] = 0;
     if (gp.max_len <= 0) return true;
-    if (gp.language_id >= c_.codec_vocab) { set_error("language id out of range"); return false; }
-    std::vector<int> idx;
-    std::vector<SlotPlan> plan;
-    if (!plan_rows(c_, S, tokens, n_tokens, max_trailing_, idx, plan)) return false;
-    const bool has_spk = speaker && speaker[0];
-    for (int s = 0; s < S; ++s)
-        if ((speaker && speaker[s]) != has_spk) { set_error("speaker embedding must be given for all or none of the utterances"); return false; }
-    const int n_pre = gp.language_id < 0 ? 3 : 4;
-    const int plen = 3 + (n_pre + (has_spk ? 1 : 0) + 2 - 1) + 1;
-    if (plen + gp.max_len + 8 > max_ctx_) { set_error("max_len exceeds the context reserved at ctx creation"); return false; }
-    if (!(gp.temperature == gp_.temperature && gp.top_k == gp_.top_k && gp.rep_penalty == gp_.rep_penalty)) {
-        for (auto &kv : g_frame_) hipGraphExecDestroy(kv.second);
-        g_frame_.clear();
-    }
-    gp_ = gp;
+    int plen = 0;
+    if (!check_gen_args(S, tokens, n_tokens, speaker, gp, &plen)) return false;
+    set_gen_params(gp);
     if (!set_seed(gp.seed, stream_)) return false;
     if (!ensure_prefill()) return false;
-    hipEvent_t e0, e1, e2;
-    hipEventCreate(&e0); hipEventCreate(&e1); hipEventCreate(&e2);
+    Event e0, e1, e2;
     Q3T_HIP(hipEventRecord(e0, stream_));
-    // ---- text projection for every slot, one batched pass
-    Q3T_HIP(hipMemcpyAsync(proj_idx_, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, stream_));
-    if (!enqueue_text_projection((int)idx.size(), stream_)) return false;
-    // ---- prefill / trailing / pad rows
-    float *spk_dev = cp_in1_;   // scratch [S][H]
-    if (has_spk)
-        for (int s = 0; s < S; ++s) Q3T_HIP(hipMemcpyAsync(spk_dev + (size_t)s * H, speaker[s], H * 4, hipMemcpyHostToDevice, stream_));
-    std::vector<RowRecipe> rec;
-    std::vector<int> tl(S), ntok(S), force(S, gp.force_frames), pos0(S, 0), frame0(S, 0), done0(S, -1);
-    for (int s = 0; s < S; ++s) {
-        const SlotPlan &p = plan[s];
-        const float *P = proj_out_ + (size_t)p.rb * H;
-        auto prow = [&](int i) { return RowTerm{P + (size_t)i * H, 0}; };
-        auto crow = [&](int id) { return RowTerm{codec_embd_ + (size_t)id * H, 1}; };
-        std::vector<RowTerm> cin;
-        if (gp.language_id < 0) cin = {crow(c_.nothink), crow(c_.think_bos), crow(c_.think_eos)};
-        else cin = {crow(c_.think), crow(c_.think_bos), crow(gp.language_id), crow(c_.think_eos)};
-        if (has_spk) cin.push_back(RowTerm{spk_dev + (size_t)s * H, 0});
-        cin.push_back(crow(c_.codec_pad));
-        cin.push_back(crow(c_.codec_bos));
-        const int ol = (int)cin.size() - 1;
-        float *out = prefill_ + (size_t)s * 10 * H;
-        for (int r = 0; r < 3; ++r) rec.push_back(RowRecipe{out + (size_t)r * H, {prow(3 + r), {nullptr, 0}, {nullptr, 0}}});
-        for (int t = 0; t < ol; ++t) rec.push_back(RowRecipe{out + (size_t)(3 + t) * H, {t == ol - 1 ? prow(0) : prow(2), cin[t], {nullptr, 0}}});
-        rec.push_back(RowRecipe{out + (size_t)(plen - 1) * H, {prow(6), cin.back(), {nullptr, 0}}});
-        float *tr = trailing_ + (size_t)s * max_trailing_ * H;
-        for (int i = 0; i < p.tcount; ++i) rec.push_back(RowRecipe{tr + (size_t)i * H, {prow(7 + i), {nullptr, 0}, {nullptr, 0}}});
-        rec.push_back(RowRecipe{tr + (size_t)p.tcount * H, {prow(1), {nullptr, 0}, {nullptr, 0}}});
-        rec.push_back(RowRecipe{tts_pad_ + (size_t)s * H, {prow(2), {nullptr, 0}, {nullptr, 0}}});
-        tl[s] = p.tcount + 1;
-        ntok[s] = p.n;
-    }
-    if ((int)rec.size() > recipe_cap_) { set_error("recipe overflow"); return false; }
-    Q3T_HIP(hipMemcpyAsync(recipe_, rec.data(), rec.size() * sizeof(RowRecipe), hipMemcpyHostToDevice, stream_));
-    if (!rows_recipe(recipe_, (int)rec.size(), H, stream_)) return false;
+    // ---- prompt, trailing and pad rows of every slot
+    std::vector<PromptEntry> in(S);
+    for (int s = 0; s < S; ++s) in[s] = PromptEntry{tokens[s], n_tokens[s], speaker ? speaker[s] : nullptr, s, s};
+    std::vector<int> tl, ntok(n_tokens, n_tokens + S), force(S, gp.force_frames), posv(S, plen), frame0(S, 0), done0(S, -1);
+    if (!assemble_prompts(main_ps_, stream_, in, gp.language_id, &plen, tl)) return false;
     Q3T_HIP(hipMemcpyAsync(trailing_len_, tl.data(), S * 4, hipMemcpyHostToDevice, stream_));
     Q3T_HIP(hipMemcpyAsync(n_tokens_, ntok.data(), S * 4, hipMemcpyHostToDevice, stream_));
     Q3T_HIP(hipMemcpyAsync(force_, force.data(), S * 4, hipMemcpyHostToDevice, stream_));
@@ -1611,13 +1733,11 @@ bool Engine::generate_once(int n_utt, const int32_t *const *tokens, const int *n
     Q3T_HIP(hipMemsetAsync(codes_, 0, (size_t)S * codes_max_len_ * NCB * 4, stream_));
     // ---- prefill: one causal pass over the plen rows of every slot; the last row's hidden state / logits per slot
     Q3T_HIP(hipMemcpyAsync(pf_slot_, slot_iota_, S * 4, hipMemcpyDeviceToDevice, stream_));
-    if (!prefill(S, plen, prefill_, policy_slots_ > 0 ? policy_slots_ : S, stream_)) return false;
+    if (!prefill(S, plen, main_ps_.rows, policy_slots_ > 0 ? policy_slots_ : S, stream_)) return false;
     Q3T_HIP(hipMemcpy2DAsync(hidden_, H * 4, pf_hid_ + (size_t)(plen - 1) * H, (size_t)plen * H * 4, H * 4, S,
                              hipMemcpyDeviceToDevice, stream_));
     Q3T_HIP(hipMemcpy2DAsync(logits_, (size_t)c_.codec_vocab * 4, pf_logits_ + (size_t)(plen - 1) * c_.codec_vocab,
                              (size_t)plen * c_.codec_vocab * 4, (size_t)c_.codec_vocab * 4, S, hipMemcpyDeviceToDevice, stream_));
-    std::vector<int> posv(S);
-    for (int s = 0; s < S; ++s) posv[s] = plen;
     if (!set_slot_state(S, posv, frame0)) return false;
     if (fused_select_ && !select_tokens(select_spec(SEL_CB0, gp_, 0, 0), logits_, S, stream_)) return false;
 #ifdef Q3T_DEV
@@ -1631,85 +1751,13 @@ bool Engine::generate_once(int n_utt, const int32_t *const *tokens, const int *n
     if (!graph_for(g_frame_, S, &Engine::enqueue_frame)) return false;
     if (!ensure_pinned((size_t)S * 4)) return false;
     int *done_h = static_cast<int *>(pin_);
-    // streaming (frame callback): chunk [start, start+interval) of every slot copied to pinned memory behind the
-    // frame that completes it; delivered one chunk late so the GPU keeps running the queued frames meanwhile.  The
-    // pinned chunks are the context's (chunk_pool_), reused across calls.
-    const bool stream_cb = on_frames && interval > 0;
-    struct Chunk { int start; int32_t *codes; int *done; hipEvent_t ev; };
-    const size_t chunk_bytes = ((size_t)S * std::max(interval, 1) * NCB + S) * 4;
-    size_t next_chunk = 0;   // chunk_pool_[0, next_chunk) are in use by this call
-    std::vector<Chunk> pend;
-    std::vector<Chunk> pool;
-    auto take_chunk = [&](Chunk &c) -> bool {
-        if (next_chunk == chunk_pool_.size()) chunk_pool_.push_back(PinnedChunk{});
-        PinnedChunk &pc = chunk_pool_[next_chunk++];
-        if (pc.cap < chunk_bytes) {
-            if (pc.codes) hipHostFree(pc.codes);
-            pc.codes = nullptr;
-            pc.cap = 0;
-            Q3T_HIP(hipHostMalloc(&pc.codes, chunk_bytes, hipHostMallocDefault));
-            pc.cap = chunk_bytes;
-        }
-        if (!pc.ev) Q3T_HIP(hipEventCreateWithFlags(&pc.ev, hipEventDisableTiming));
-        c.codes = pc.codes;
-        c.done = pc.codes + (size_t)S * interval * NCB;
-        c.ev = pc.ev;
-        return true;
-    };
-    std::vector<int> &delivered = st.delivered, &stop_at = st.stop_at;
-    int n_live = S;   // a fallback re-run regenerates utterances stopped earlier too (their frames are returned)
-    auto release = [&]() {
-        pend.clear();
-        pool.clear();
-        hipEventDestroy(e0); hipEventDestroy(e1); hipEventDestroy(e2);
-    };
-    // a chunk is handed to the caller only once the persistent kernels behind it are known to be fault-free
-    auto deliver = [&](Chunk &c) -> bool {
-        Q3T_HIP(hipEventSynchronize(c.ev));
-        if (persist_error()) { *fault = true; return false; }
-        for (int s = 0; s < S; ++s) {
-            if (stop_at[s] >= 0) continue;
-            const int nf = c.done[s] >= 0 ? c.done[s] : gp.max_len;
-            if (nf < c.start + interval) continue;   // partial chunks go to the final flush, as in the reference
-            if (c.start + interval <= delivered[s]) continue;   // delivered before a fallback re-run
-            delivered[s] = c.start + interval;
-            if (!on_frames(user, s, c.codes + (size_t)s * interval * NCB, interval, NCB)) {
-                stop_at[s] = c.start + interval;
-                const int d = stop_at[s];
-                Q3T_HIP(hipMemcpyAsync(done_ + s, &d, 4, hipMemcpyHostToDevice, stream_));
-                Q3T_HIP(hipStreamSynchronize(stream_));   // &d is a stack value
-                --n_live;
-            }
-        }
-        return true;
-    };
+    ChunkStreamer streamer(*this, S, gp.max_len, on_frames, user, interval, st, fault);
     bool all_done = false;
-    for (int f = 0; f < gp.max_len && !all_done && n_live > 0; ++f) {
+    for (int f = 0; f < gp.max_len && !all_done && streamer.n_live() > 0; ++f) {
         if (!persist_fault_hook(S, (persist_ ? 1 : 0) + (persist_cp_ ? 1 : 0))) return false;
         Q3T_HIP(hipGraphLaunch(g_frame_[S], stream_));
         if (dbg) { fprintf(stderr, "[q3t] frame %d launched\n", f); fflush(stderr); }
-        if (stream_cb && (f + 1) % interval == 0) {
-            Chunk c;
-            if (!pool.empty()) { c = pool.back(); pool.pop_back(); }
-            else if (!take_chunk(c)) { release(); return false; }
-            c.start = f + 1 - interval;
-            for (int s = 0; s < S; ++s)
-                Q3T_HIP(hipMemcpyAsync(c.codes + (size_t)s * interval * NCB, codes_ + ((size_t)s * codes_max_len_ + c.start) * NCB,
-                                       (size_t)interval * NCB * 4, hipMemcpyDeviceToHost, stream_));
-            Q3T_HIP(hipMemcpyAsync(c.done, done_, S * 4, hipMemcpyDeviceToHost, stream_));
-            Q3T_HIP(hipEventRecord(c.ev, stream_));
-            pend.push_back(c);
-            if (pend.size() > 1) {
-                Chunk front = pend.front();
-                pend.erase(pend.begin());
-                pool.push_back(front);
-                if (!deliver(front)) {
-                    Q3T_HIP(hipStreamSynchronize(stream_));
-                    release();
-                    return false;
-                }
-            }
-        }
+        if (!streamer.after_frame(f)) return false;
         if ((f + 1) % poll_every_ == 0 && f + 1 < gp.max_len) {
             Q3T_HIP(hipMemcpyAsync(done_h, done_, S * 4, hipMemcpyDeviceToHost, stream_));
             Q3T_HIP(hipStreamSynchronize(stream_));
@@ -1730,28 +1778,15 @@ bool Engine::generate_once(int n_utt, const int32_t *const *tokens, const int *n
     if (persist_error()) {
         set_error("persistent kernel: an in-launch hand-off timed out");
         *fault = true;
-        release();
         return false;
     }
     for (int s = 0; s < S; ++s) n_frames[s] = done_h[s] >= 0 ? std::min(done_h[s], gp.max_len) : gp.max_len;
-    if (stream_cb) {
-        std::vector<Chunk> last;
-        last.swap(pend);
-        for (Chunk &c : last) pool.push_back(c);
-        for (Chunk &c : last)
-            if (!deliver(c)) { release(); return false; }
-        for (int s = 0; s < S; ++s) {
-            if (stop_at[s] >= 0) { n_frames[s] = std::min(n_frames[s], stop_at[s]); continue; }
-            if (n_frames[s] > delivered[s])   // final flush (tts_transformer.cpp:2563-2570)
-                on_frames(user, s, codes + ((size_t)s * gp.max_len + delivered[s]) * NCB, n_frames[s] - delivered[s], NCB);
-        }
-    }
+    if (!streamer.flush(codes, n_frames)) return false;
     float ms1 = 0, ms2 = 0;
     hipEventElapsedTime(&ms1, e0, e1);
     hipEventElapsedTime(&ms2, e1, e2);
     last_prefill_ms = ms1;
     last_frames_ms = ms2;
-    release();
     return true;
 }
 
@@ -1769,18 +1804,10 @@ bool Engine::alloc_admission() {
     if (astream_) return true;
     const int S = max_slots_, H = c_.hidden;
     if (!ensure_prefill()) return false;
-    aprefill_ = dalloc<float>((size_t)S * 10 * H);
     ahidden_ = dalloc<float>((size_t)S * H);
     alogits_ = dalloc<float>((size_t)S * c_.codec_vocab);
-    aproj_cap_ = S * (max_trailing_ + 16);
-    aproj_idx_ = dalloc<int>(aproj_cap_);
-    aproj_h_ = dalloc<uint16_t>((size_t)aproj_cap_ * c_.text_dim);
-    aproj_out_ = dalloc<float>((size_t)aproj_cap_ * H);
-    arecipe_ = dalloc<RowRecipe>(aproj_cap_);
-    if (!aprefill_ || !ahidden_ || !alogits_ || !aproj_idx_ || !aproj_h_ || !aproj_out_ || !arecipe_) {
-        set_error("device allocation failed");
-        return false;
-    }
+    if (!alloc_prompt_scratch(adm_ps_, nullptr)) return false;
+    if (!ahidden_ || !alogits_) { set_error("device allocation failed"); return false; }
     // every buffer was zeroed on stream_ and drained by dalloc before the admission stream exists
     Q3T_HIP(hipStreamCreateWithFlags(&astream_, hipStreamNonBlocking));
     return true;
@@ -1793,51 +1820,17 @@ bool Engine::admit_batch(const std::vector<int> &tgt, const std::vector<int> &ut
                          const int *n_tokens, const float *const *speaker, const GenParams &gp, int plen, hipStream_t as,
                          int *tgt_h, std::vector<int> &trailing_len) {
     const int H = c_.hidden, a = (int)tgt.size();
-    std::vector<const int32_t *> tk(a);
-    std::vector<int> nt(a);
-    for (int j = 0; j < a; ++j) { tk[j] = tokens[utt[j]]; nt[j] = n_tokens[utt[j]]; }
-    std::vector<int> idx;
-    std::vector<SlotPlan> plan;
-    if (!plan_rows(c_, a, tk.data(), nt.data(), max_trailing_, idx, plan)) return false;
-    if ((int)idx.size() > aproj_cap_) { set_error("too many text rows"); return false; }
-    Q3T_HIP(hipMemcpyAsync(aproj_idx_, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, as));
-    if (!enqueue_text_projection((int)idx.size(), as, aproj_idx_, aproj_h_, aproj_out_)) return false;
-    std::vector<RowRecipe> rec;
-    auto crow = [&](int id) { return RowTerm{codec_embd_ + (size_t)id * H, 1}; };
-    for (int j = 0; j < a; ++j) {
-        const int k = tgt[j];
-        const float *spk = speaker ? speaker[utt[j]] : nullptr;
-        float *spk_dev = cp_in1_ + (size_t)k * H;
-        if (spk) Q3T_HIP(hipMemcpyAsync(spk_dev, spk, H * 4, hipMemcpyHostToDevice, as));
-        const SlotPlan &p = plan[j];
-        const float *P = aproj_out_ + (size_t)p.rb * H;
-        auto prow = [&](int i) { return RowTerm{P + (size_t)i * H, 0}; };
-        std::vector<RowTerm> cin;
-        if (gp.language_id < 0) cin = {crow(c_.nothink), crow(c_.think_bos), crow(c_.think_eos)};
-        else cin = {crow(c_.think), crow(c_.think_bos), crow(gp.language_id), crow(c_.think_eos)};
-        if (spk) cin.push_back(RowTerm{spk_dev, 0});
-        cin.push_back(crow(c_.codec_pad));
-        cin.push_back(crow(c_.codec_bos));
-        const int ol = (int)cin.size() - 1;
-        if (3 + ol + 1 != plen) { set_error("admit_batch: prefill length mismatch"); return false; }
-        float *out = aprefill_ + (size_t)j * 10 * H;
-        for (int r = 0; r < 3; ++r) rec.push_back(RowRecipe{out + (size_t)r * H, {prow(3 + r), {nullptr, 0}, {nullptr, 0}}});
-        for (int t = 0; t < ol; ++t) rec.push_back(RowRecipe{out + (size_t)(3 + t) * H, {t == ol - 1 ? prow(0) : prow(2), cin[t], {nullptr, 0}}});
-        rec.push_back(RowRecipe{out + (size_t)(plen - 1) * H, {prow(6), cin.back(), {nullptr, 0}}});
-        float *tr = trailing_ + (size_t)k * max_trailing_ * H;
-        for (int i = 0; i < p.tcount; ++i) rec.push_back(RowRecipe{tr + (size_t)i * H, {prow(7 + i), {nullptr, 0}, {nullptr, 0}}});
-        rec.push_back(RowRecipe{tr + (size_t)p.tcount * H, {prow(1), {nullptr, 0}, {nullptr, 0}}});
-        rec.push_back(RowRecipe{tts_pad_ + (size_t)k * H, {prow(2), {nullptr, 0}, {nullptr, 0}}});
-        trailing_len[j] = p.tcount + 1;
-    }
-    if ((int)rec.size() > aproj_cap_) { set_error("recipe overflow"); return false; }
-    Q3T_HIP(hipMemcpyAsync(arecipe_, rec.data(), rec.size() * sizeof(RowRecipe), hipMemcpyHostToDevice, as));
-    if (!rows_recipe(arecipe_, (int)rec.size(), H, as)) return false;
+    std::vector<PromptEntry> in(a);
+    for (int j = 0; j < a; ++j)
+        in[j] = PromptEntry{tokens[utt[j]], n_tokens[utt[j]], speaker ? speaker[utt[j]] : nullptr, tgt[j], j};
+    int got = 0;
+    if (!assemble_prompts(adm_ps_, as, in, gp.language_id, &got, trailing_len)) return false;
+    if (got != plen) { set_error("admit_batch: prefill length mismatch"); return false; }
     // the causal prefill of the batch with the running batch's kernels (S_main = q_slots_), K/V straight into the
     // target slots' rows [0, plen)
     for (int j = 0; j < a; ++j) tgt_h[j] = tgt[j];
     Q3T_HIP(hipMemcpyAsync(pf_slot_, tgt_h, a * 4, hipMemcpyHostToDevice, as));
-    if (!prefill(a, plen, aprefill_, q_slots_, as)) return false;
+    if (!prefill(a, plen, adm_ps_.rows, q_slots_, as)) return false;
     const int V = c_.codec_vocab;
     for (int j = 0; j < a; ++j) {
         const size_t r = (size_t)j * plen + plen - 1;
@@ -1880,28 +1873,14 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
     if (max_active <= 0 || max_active > S) max_active = S;
     for (int u = 0; u < n_utt; ++u) n_frames[u] = 0;
     if (gp.max_len <= 0) return true;
-    if (gp.language_id >= c_.codec_vocab) { set_error("language id out of range"); return false; }
-    const bool has_spk = speaker && speaker[0];
-    for (int u = 0; u < n_utt; ++u)
-        if ((speaker && speaker[u]) != has_spk) { set_error("speaker embedding must be given for all or none of the utterances"); return false; }
-    {   // validate every prompt before anything runs
-        std::vector<int> idx;
-        std::vector<SlotPlan> plan;
-        if (!plan_rows(c_, n_utt, tokens, n_tokens, max_trailing_, idx, plan)) return false;
-    }
-    const int n_pre = gp.language_id < 0 ? 3 : 4;
-    const int plen = 3 + (n_pre + (has_spk ? 1 : 0) + 2 - 1) + 1;
-    if (plen + gp.max_len + 8 > max_ctx_) { set_error("max_len exceeds the context reserved at ctx creation"); return false; }
+    int plen = 0;
+    if (!check_gen_args(n_utt, tokens, n_tokens, speaker, gp, &plen)) return false;
     if (gp.max_len > codes_max_len_) { set_error("max_len exceeds the code buffer"); return false; }
     if (!alloc_admission()) return false;
     q_slots_ = S;
     // the single-slot context runs persistent kernels, which need the whole device: admissions go on the main stream
     hipStream_t as = (S == 1 && persist_enabled()) ? stream_ : astream_;
-    if (!(gp.temperature == gp_.temperature && gp.top_k == gp_.top_k && gp.rep_penalty == gp_.rep_penalty)) {
-        for (auto &kv : g_frame_) hipGraphExecDestroy(kv.second);
-        g_frame_.clear();
-    }
-    gp_ = gp;
+    set_gen_params(gp);
     if (!set_seed(gp.seed, stream_)) return false;
     // the finished utterances' codes, copied to the caller once at the end (device scratch kept by the context)
     if (!ensure_qout((size_t)n_utt * gp.max_len * NCB * 4)) return false;
@@ -1911,20 +1890,18 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
     int *pin = static_cast<int *>(pin_);
     int *done_h = pin + (size_t)S * 8, *tgt_h = pin + (size_t)S * 9, *park = pin + (size_t)S * 10;
     *park = 0;
-    hipEvent_t aev = nullptr, pev = nullptr;
-    auto cleanup = [&]() {
+    Event aev(hipEventDisableTiming), pev(hipEventDisableTiming);
+    // every exit drains both streams and leaves the context as generate() expects it: kernels chosen by the call's
+    // own slot count, sampling keyed by slot index
+    ScopeExit restore([&] {
         hipStreamSynchronize(as);
         hipStreamSynchronize(stream_);
-        if (aev) hipEventDestroy(aev);
-        if (pev) hipEventDestroy(pev);
         policy_slots_ = 0;
-        std::vector<uint64_t> ident(max_slots_);   // generate() keys sampling by slot index again
+        std::vector<uint64_t> ident(max_slots_);
         for (int k = 0; k < max_slots_; ++k) ident[k] = (uint64_t)k;
         hipMemcpyAsync(utt_, ident.data(), max_slots_ * 8, hipMemcpyHostToDevice, stream_);
         hipStreamSynchronize(stream_);
-    };
-    Q3T_HIP(hipEventCreateWithFlags(&aev, hipEventDisableTiming));
-    Q3T_HIP(hipEventCreateWithFlags(&pev, hipEventDisableTiming));
+    });
     // every slot starts parked: done = 0 (no selection, no advance), position plen (above the rows a prefill writes),
     // valid code ids for the gathers it still runs through, no trailing text
     {
@@ -1945,8 +1922,7 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         for (int k = 0; k < S && next + (int)tgt.size() < n_utt && n_busy + (int)tgt.size() < max_active; ++k)
             if (state[k] == FREE) { tgt.push_back(k); utt.push_back(next + (int)tgt.size() - 1); }
         if (tgt.empty()) return true;
-        batch_tl.assign(tgt.size(), 0);
-        if (!admit_batch(tgt, utt, tokens, n_tokens, has_spk ? speaker : nullptr, gp, plen, as, tgt_h, batch_tl)) return false;
+        if (!admit_batch(tgt, utt, tokens, n_tokens, speaker, gp, plen, as, tgt_h, batch_tl)) return false;
         Q3T_HIP(hipEventRecord(aev, as));
         for (size_t j = 0; j < tgt.size(); ++j) {
             state[tgt[j]] = PENDING;
@@ -1969,7 +1945,7 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         batch_tgt.clear();
         return true;
     };
-    if (!admit() || !activate()) { cleanup(); return false; }
+    if (!admit() || !activate()) return false;
     // frame graph over slots [0, S_eff): S_eff = the highest busy slot + 1, rounded up to 8, never below the smallest
     // batch that keeps the S-slot kernel family (matrix cores from 4 slots, k_attn_seq from 16), whose per-token
     // arithmetic the graph reproduces (policy_slots_ = S): a draining queue stops paying for parked slots
@@ -1988,15 +1964,15 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         int n_active = 0;
         for (int k = 0; k < S; ++k) n_active += state[k] == ACTIVE;
         if (n_active == 0) {   // only an admission in flight: wait for it instead of running empty frames
-            if (batch_tgt.empty() && !admit()) { cleanup(); return false; }
+            if (batch_tgt.empty() && !admit()) return false;
             Q3T_HIP(hipEventSynchronize(aev));
-            if (!activate()) { cleanup(); return false; }
+            if (!activate()) return false;
             polled = false;
             continue;
         }
         hipGraphExec_t fg = nullptr;
-        if (!frame_graph(&fg)) { cleanup(); return false; }
-        if (!persist_fault_hook(S, (persist_ ? 1 : 0) + (persist_cp_ ? 1 : 0))) { cleanup(); return false; }
+        if (!frame_graph(&fg)) return false;
+        if (!persist_fault_hook(S, (persist_ ? 1 : 0) + (persist_cp_ ? 1 : 0))) return false;
         Q3T_HIP(hipGraphLaunch(fg, stream_));
         ++f;
         if (polled) {
@@ -2018,21 +1994,19 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
                 ++n_fin;
             }
         }
-        if (!batch_tgt.empty() && (as == stream_ || hipEventQuery(aev) == hipSuccess) && !activate()) { cleanup(); return false; }
-        if (batch_tgt.empty() && next < n_utt && !admit()) { cleanup(); return false; }
-        if (as == stream_ && !batch_tgt.empty() && !activate()) { cleanup(); return false; }
+        if (!batch_tgt.empty() && (as == stream_ || hipEventQuery(aev) == hipSuccess) && !activate()) return false;
+        if (batch_tgt.empty() && next < n_utt && !admit()) return false;
+        if (as == stream_ && !batch_tgt.empty() && !activate()) return false;
         Q3T_HIP(hipMemcpyAsync(done_h, done_, S * 4, hipMemcpyDeviceToHost, stream_));
         Q3T_HIP(hipEventRecord(pev, stream_));
         polled = true;
-        if (f > (n_utt + 1) * (gp.max_len + plen + 2)) { cleanup(); set_error("generate_queue: no progress"); return false; }
+        if (f > (n_utt + 1) * (gp.max_len + plen + 2)) { set_error("generate_queue: no progress"); return false; }
     }
     for (int u = 0; u < n_utt; ++u)
         Q3T_HIP(hipMemcpyAsync(codes + (size_t)u * gp.max_len * NCB, out_dev + (size_t)u * gp.max_len * NCB,
                                (size_t)gp.max_len * NCB * 4, hipMemcpyDeviceToHost, stream_));
     Q3T_HIP(hipStreamSynchronize(stream_));
-    const bool fault = persist_error();
-    cleanup();
-    if (fault) { set_error("persistent kernel: an in-launch hand-off timed out"); *faulted = true; return false; }
+    if (persist_error()) { set_error("persistent kernel: an in-launch hand-off timed out"); *faulted = true; return false; }
     return true;
 }
 
@@ -2062,8 +2036,7 @@ bool Engine::time_stage(int stage, int S, int pos, int iters, double *ms) {
     Q3T_HIP(hipGraphLaunch(g, stream_));   // warm
     // one event pair around EACH replay, on the stream the kernels run on: the mean is the replay's own duration (for
     // the persistent stages, the one kernel's), without the host-side gap between two graph launches
-    std::vector<hipEvent_t> ev(2 * (size_t)iters, nullptr);
-    for (hipEvent_t &e : ev) Q3T_HIP(hipEventCreate(&e));
+    std::vector<Event> ev(2 * (size_t)iters);
     for (int i = 0; i < iters; ++i) {
         Q3T_HIP(hipEventRecord(ev[2 * i], stream_));
         Q3T_HIP(hipGraphLaunch(g, stream_));
@@ -2076,7 +2049,6 @@ bool Engine::time_stage(int stage, int S, int pos, int iters, double *ms) {
         hipEventElapsedTime(&t, ev[2 * i], ev[2 * i + 1]);
         sum += t;
     }
-    for (hipEvent_t e : ev) hipEventDestroy(e);
     *ms = sum / iters;
     if (persist_error()) {   // time the launch-per-op fallback instead of a faulted persistent launch
         if (!persist_recover()) return false;
@@ -2093,10 +2065,10 @@ bool Engine::talker_prefill(int n_utt, int n_rows, const float *embd, int family
     const int H = c_.hidden, V = c_.codec_vocab;
     DeviceLock lk(false, device_);
     if (!ensure_prefill()) return false;
-    Q3T_HIP(hipMemcpy2DAsync(prefill_, (size_t)10 * H * 4, embd, (size_t)n_rows * H * 4, (size_t)n_rows * H * 4, n_utt,
+    Q3T_HIP(hipMemcpy2DAsync(main_ps_.rows, (size_t)10 * H * 4, embd, (size_t)n_rows * H * 4, (size_t)n_rows * H * 4, n_utt,
                              hipMemcpyHostToDevice, stream_));
     Q3T_HIP(hipMemcpyAsync(pf_slot_, slot_iota_, n_utt * 4, hipMemcpyDeviceToDevice, stream_));
-    if (!prefill(n_utt, n_rows, prefill_, family_slots > 0 ? family_slots : n_utt, stream_)) return false;
+    if (!prefill(n_utt, n_rows, main_ps_.rows, family_slots > 0 ? family_slots : n_utt, stream_)) return false;
     if (hidden) Q3T_HIP(hipMemcpyAsync(hidden, pf_hid_, (size_t)n_utt * n_rows * H * 4, hipMemcpyDeviceToHost, stream_));
     if (logits)
         Q3T_HIP(hipMemcpy2DAsync(logits, (size_t)V * 4, pf_logits_ + (size_t)(n_rows - 1) * V, (size_t)n_rows * V * 4,
@@ -2133,10 +2105,8 @@ bool Engine::codepred_frame(int S, const float *hidden, const int *cb0, float te
     DeviceLock lk(persist_exclusive(S), device_);
     GenParams gp = gp_;
     gp.temperature = temperature; gp.top_k = top_k; gp.seed = seed;
-    gp_ = gp;
+    set_gen_params(gp);
     if (!set_seed(seed, stream_)) return false;
-    for (auto &kv : g_frame_) hipGraphExecDestroy(kv.second);
-    g_frame_.clear();
     Q3T_HIP(hipMemcpyAsync(hidden_, hidden, (size_t)S * H * 4, hipMemcpyHostToDevice, stream_));
     std::vector<int> tk0((size_t)S * 16, 0);
     for (int s = 0; s < S; ++s) tk0[(size_t)s * 16] = cb0[s];

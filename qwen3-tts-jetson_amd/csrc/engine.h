@@ -47,6 +47,27 @@ class Vocoder;
 class SpeakerEncoder;
 struct PLayerW;
 
+// scratch of one prompt assembly in flight (Engine::assemble_prompts): one set per stream that assembles prompts
+struct PromptScratch {
+    int cap = 0;                   // rows of idx / h / out / recipe
+    int *idx = nullptr;            // text token id per projection row
+    uint16_t *h = nullptr;         // fc1 output (f16)
+    float *out = nullptr;          // projected text rows
+    RowRecipe *recipe = nullptr;
+    float *rows = nullptr;         // prompt rows [max_slots][10][H]
+    float *spk = nullptr;          // speaker rows [max_slots][H], by target slot
+    std::vector<int> idx_host;     // the (pageable) sources of the idx / recipe uploads: they outlive the copies
+    std::vector<RowRecipe> recipe_host;
+};
+// one utterance of an assembly: its speaker row (or null), the slot whose trailing / pad rows it fills, and the
+// index of its prompt rows in PromptScratch::rows
+struct PromptEntry {
+    const int32_t *tokens;
+    int n_tokens;
+    const float *speaker;
+    int slot, row;
+};
+
 // Path-selection knobs, read once from the environment when a context is created (the reference's own pattern:
 // QWEN3_TTS_LOW_MEM, src/qwen3_tts.cpp:125-129).  All default to the fastest path; the alternatives exist so that
 // the tests can compare paths that must agree (persistent vs launch-per-op, sequential vs split attention).
@@ -148,8 +169,8 @@ public:
     int persist_kernels() const {   // q3t_persist_kernels
         return (persist_ ? (tk_roles_ ? 1 : 2) : 0) | (persist_cp_ ? (cp_roles_ && cp_qkvtab_ ? 4 : 8) : 0) | (cpb_ ? 16 : 0) | (tkb_ ? 32 : 0);
     }
-    // runs with S slots launch a persistent grid (the 1-slot kernels, or the batched code-predictor frame): they hold the
-    // device lock exclusively (devlock.h)
+    // runs with S slots launch a persistent grid (the 1-slot kernels, or the batched code-predictor frame / talker
+    // step): they hold the device lock exclusively (devlock.h)
     bool persist_exclusive(int S) const { return ((persist_ || persist_cp_) && S == 1) || ((cpb_ || tkb_) && S > 1); }
     bool persist_fell_back() const { return persist_fallback_; }
 #ifdef Q3T_DEV
@@ -175,6 +196,7 @@ private:
     struct StreamState {   // per utterance, kept across a fallback re-run so no chunk is delivered twice
         std::vector<int> delivered, stop_at;
     };
+    class ChunkStreamer;   // the frame callback's chunk copies and deliveries (engine.cpp)
     bool generate_once(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                        const GenParams &gp, int32_t *codes, int *n_frames, FrameCb on_frames, void *user, int interval,
                        StreamState &st, bool *fault);
@@ -193,7 +215,18 @@ private:
     SelectSpec select_spec(int mode, const GenParams &gp, int frame_offset, int step) const;
     bool enqueue_cp_frame(int S, hipStream_t s, float *logits_host = nullptr, bool talker_next = false);
     bool enqueue_frame(int S, hipStream_t s);
-    bool enqueue_text_projection(int n_rows, hipStream_t s);
+    bool enqueue_text_projection(int n_rows, hipStream_t s, const PromptScratch &ps);
+    // the prompt rows (PromptScratch::rows), trailing-text rows and pad row of every entry, assembled on stream s;
+    // plen: the prompt length in rows (prompt_len), trailing_len: per entry
+    bool assemble_prompts(PromptScratch &ps, hipStream_t s, const std::vector<PromptEntry> &in, int language_id,
+                          int *plen, std::vector<int> &trailing_len);
+    static int prompt_len(int language_id, bool has_spk);
+    bool alloc_prompt_scratch(PromptScratch &ps, float *spk);
+    // the checks shared by generate() and generate_queue(); plen: the prompt length
+    bool check_gen_args(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
+                        const GenParams &gp, int *plen);
+    void set_gen_params(const GenParams &gp);   // gp_ = gp; drops the frame graphs that baked other sampling values
+    template <class F> hipGraphExec_t capture(hipStream_t s, F &&enqueue);   // null with the error set
     bool graph_for(std::map<int, hipGraphExec_t> &cache, int S, bool (Engine::*fn)(int, hipStream_t));
     bool graph_for_key(std::map<int, hipGraphExec_t> &cache, int key, int S, bool (Engine::*fn)(int, hipStream_t));
     int policy_slots_ = 0;         // > 0: the batched stacks choose kernels as for this many slots (queue graphs)
@@ -213,14 +246,9 @@ private:
                      const int *n_tokens, const float *const *speaker, const GenParams &gp, int plen, hipStream_t as,
                      int *tgt_h, std::vector<int> &trailing_len);
     bool activate_slot(int slot, uint64_t utt, int trailing_len, int n_tok, const GenParams &gp, int plen, int *state_h);
-    bool enqueue_text_projection(int n_rows, hipStream_t s, const int *idx, uint16_t *hbuf, float *out);
     hipStream_t astream_ = nullptr;
-    float *aprefill_ = nullptr, *ahidden_ = nullptr, *alogits_ = nullptr, *aproj_out_ = nullptr;
-    uint16_t *aproj_h_ = nullptr;
-    int *aproj_idx_ = nullptr;
-    RowRecipe *arecipe_ = nullptr;
-    int aproj_cap_ = 0;
-    int q_slots_ = 0;              // slot count of the running queue (the batch the admissions reproduce)
+    float *ahidden_ = nullptr, *alogits_ = nullptr;
+    int q_slots_ = 0;            // slot count of the running queue (the batch the admissions reproduce)
 
     Config c_;
     Config cpc_;                         // the code predictor's layer geometry (c_ with the cp_* values)
@@ -263,16 +291,13 @@ private:
     uint64_t *seed_dev_ = nullptr;   // the sampling seed read by the captured selections (SelectSpec::seed_dev)
     uint64_t seed_host_ = 0;
     bool set_seed(uint64_t seed, hipStream_t s);
-    float *trailing_ = nullptr, *tts_pad_ = nullptr, *prefill_ = nullptr;
+    float *trailing_ = nullptr, *tts_pad_ = nullptr;
     int32_t *codes_ = nullptr;
     int codes_max_len_ = 0;
-    // text projection scratch
-    int *proj_idx_ = nullptr;
-    uint16_t *proj_h_ = nullptr;
-    float *proj_out_ = nullptr;
-    int proj_cap_ = 0;
-    RowRecipe *recipe_ = nullptr;
-    int recipe_cap_ = 0;
+    // prompt assembly scratch: the main stream's (its speaker rows are cp_in1_, which the main stream's frames reuse
+    // after the prompt is assembled) and the admission stream's (alloc_admission: speaker rows of its own, the frame
+    // loop of a model with mtp_proj writes cp_in1_ while an admission runs)
+    PromptScratch main_ps_, adm_ps_;
     GenParams gp_;   // parameters baked into the captured frame graph
     Options opt_;
     int poll_every_ = 16;

@@ -25,7 +25,7 @@
 #include <cstdlib>
 
 #ifndef Q3T_GEMV_NT
-#define Q3T_GEMV_NT 0   // 1: non-temporal weight loads (the compiler then waits vmcnt(0) for every earlier load)
+#define Q3T_GEMV_NT 0   // 1: non-temporal weight loads (ld_nt16: global_load_dwordx4 nt, waits as ld_w's; not measured on the per-op path)
 #endif
 
 namespace q3t {

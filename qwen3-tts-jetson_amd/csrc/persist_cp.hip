@@ -155,6 +155,8 @@ struct Pol {   // persist_roles.h's policy
     static constexpr bool WPUB = Q3T_CP_WPUB, PUT_FIRST = Q3T_CP_PUT_FIRST, GATE = Q3T_CP_GATE;
     template <int N>
     static __device__ __forceinline__ void wait(const uint64_t *g, uint32_t tag, uint32_t (&u)[N], Ctl &c) { Q3T_CP_WAIT<N>(g, tag, u, c); }
+    // default policy: every row is read again by each of the 16 passes, from the Infinity Cache
+    static __device__ __forceinline__ uint4 ldw(const uint16_t *w) { return ld16(w); }
 };
 
 // the tokens of `pass` at one layer: the paired pass runs token 0 (the hidden state), then token 1 (CB0); every other
@@ -205,7 +207,7 @@ __device__ __forceinline__ void role_qkv(Ctx &X) {
                 issue_qkv(l + 1);
             } else if (pass >= 1) {   // lm_head[pass - 1]: rows 32i + 16j + grp
 #pragma unroll
-                for (int j = 0; j < 2; ++j) issue_row(S.heads[pass - 1], 32 * i + 16 * j + grp, wq[j]);
+                for (int j = 0; j < 2; ++j) issue_row<Pol>(S.heads[pass - 1], 32 * i + 16 * j + grp, wq[j]);
                 nw = ldf4(p.out_norm + 4 * t);
             } else {
                 issue_qkv(1);   // pass 0 has no head; layer 0 of the next passes comes from the table
@@ -526,7 +528,7 @@ __device__ __forceinline__ void role_gu(Ctx &X) {
     const int i = blockIdx.x - UW, t = threadIdx.x;
     uint4 wg[2][8], wu[2][8];
     float4 nw;
-    gu_issue(S.layers[0].gu, S.layers[0].ffn_norm, i, wg, wu, nw);
+    gu_issue<Pol>(S.layers[0].gu, S.layers[0].ffn_norm, i, wg, wu, nw);
     for (int pass = PAIR ? 1 : 0; pass < NPASS; ++pass) {
         for (int l = 0; l < NLC; ++l)
         CP_TOKENS(pass, ps) {   // the paired pass: token 0, then token 1
@@ -539,7 +541,7 @@ __device__ __forceinline__ void role_gu(Ctx &X) {
             PROF(ph, 1);
             gu_phase<Pol>(X, i, f4_of(u), wg, wu, nw, ph);
             const int nl = ps == pass ? next_layer(pass, l) : -1;   // (after the pair's second token)
-            if (nl >= 0) gu_issue(S.layers[nl].gu, S.layers[nl].ffn_norm, i, wg, wu, nw);
+            if (nl >= 0) gu_issue<Pol>(S.layers[nl].gu, S.layers[nl].ffn_norm, i, wg, wu, nw);
         }
     }
 }
@@ -551,7 +553,7 @@ __device__ __forceinline__ void role_dn(Ctx &X) {
     const int i = blockIdx.x - DW, t = threadIdx.x;
     const int lo = i * H / ND, n = (i + 1) * H / ND - lo;
     uint4 wd[5][6];
-    dn_issue(S.layers[0].down, lo, n, wd);
+    dn_issue<Pol>(S.layers[0].down, lo, n, wd);
     int it = 0;   // phase executions: the parity of S.red
     for (int pass = PAIR ? 1 : 0; pass < NPASS; ++pass) {
         for (int l = 0; l < NLC; ++l)
@@ -565,7 +567,7 @@ __device__ __forceinline__ void role_dn(Ctx &X) {
             }
             dn_phase<Pol>(X, lo, n, it++ & 1, wd, ph_of(ps, l, 4));
             const int nl = ps == pass ? next_layer(pass, l) : -1;   // (after the pair's second token)
-            if (nl >= 0) dn_issue(S.layers[nl].down, lo, n, wd);
+            if (nl >= 0) dn_issue<Pol>(S.layers[nl].down, lo, n, wd);
         }
     }
 }

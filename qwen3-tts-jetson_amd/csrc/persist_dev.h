@@ -6,7 +6,7 @@
 // RMSNorm prologue and the talker step's embedding gather.
 // This header comes before its includers' `#pragma clang fp contract(off)` (select.h, which follows it, is compiled
 // with the default), so it sets no file-scope pragma: the gather's sums carry the pragma in their own bodies, and
-// rms_to_f16 has no multiply that feeds an add.
+// rms_to_f16 has no multiply that feeds an add (its products, which feed f16 conversions, are held apart by opaque()).
 #pragma once
 #include "persist.h"
 
@@ -257,7 +257,11 @@ __device__ __forceinline__ void rms_to_f16(float4 x, float4 w, float eps, uint16
     double ss = (double)(x.x * x.x) + (double)(x.y * x.y) + (double)(x.z * x.z) + (double)(x.w * x.w);
     ss = block_sum_d(ss, dscr);
     const float scale = 1.0f / sqrtf((float)(ss / 1024) + eps);
-    const float y0 = (x.x * scale) * w.x, y1 = (x.y * scale) * w.y, y2 = (x.z * scale) * w.z, y3 = (x.w * scale) * w.w;
+    // opaque: the product is rounded to f32 before its f16 conversion, as the per-op prologue's.  Left to instruction
+    // selection, the scalar multiply and the conversion become ONE v_fma_mixlo_f16, which rounds once, whatever the
+    // contraction pragma says (only the SLP vectoriser's packed multiply used to keep them apart)
+    const float y0 = opaque((x.x * scale) * w.x), y1 = opaque((x.y * scale) * w.y), y2 = opaque((x.z * scale) * w.z),
+                y3 = opaque((x.w * scale) * w.w);
     if (side) *reinterpret_cast<float4 *>(side + 4 * t) = make_float4(y0, y1, y2, y3);
     uint2 h;
     h.x = (uint32_t)f2h(y0) | ((uint32_t)f2h(y1) << 16);

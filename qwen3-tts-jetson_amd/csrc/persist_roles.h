@@ -10,12 +10,17 @@
 //   P::PUT_FIRST  a barrier after a role's publish, so the next weight prefetch enters the CU's memory pipe behind it
 //   P::GATE       polls: lane 0 of each wave gates on the wave's first granule before the sweep
 //   P::wait<N>    the sweep of N contiguous granules (g_waitc)
+//   P::ldw        the 16-byte weight load (ld16; ld_nt16 where every row is read once per launch by one CU)
 // Include this header after the .hip's `#pragma clang fp contract(off)`; the pragma is repeated here because the
 // bodies must round as written.
 #pragma once
 #include "persist_dev.h"
 
 #pragma clang fp contract(off)
+
+#ifndef Q3T_QKV_SCATTER   // WPUB publish, 1: the row sums by reduce-scatter and row swaps (0: 16 adds and four ds_bpermute)
+#define Q3T_QKV_SCATTER 0
+#endif
 
 namespace q3t {
 namespace prole {
@@ -33,11 +38,17 @@ struct RoleCtx {
     __device__ uint32_t tag(int ph) const { return ((seq * 1024u + (unsigned)ph) << 1) | 1u; }
 };
 
-// development timeline (p.prof): wall clock at k = 0 wait start / 1 input arrived / 2 output published / 3 mid-phase
+// development timeline (p.prof): wall clock at k = 0 wait start / 1 input arrived / 2 output published / 3 mid-phase.
+// Only the development and experiment builds (Q3T_DEV) allocate p.prof; in the release library the stamp is no code
+// (each one was a test of p.prof and a branch on the chain, 3-4 per role body).
+#ifdef Q3T_DEV
 #define PROF(ph, k)                                                                                           \
     do {                                                                                                      \
         if (X.p.prof && threadIdx.x == 0 && blockIdx.x < PROF_WG) X.p.prof[((size_t)blockIdx.x * PROF_PH + (ph)) * 4 + (k)] = wall_clock64(); \
     } while (0)
+#else
+#define PROF(ph, k) ((void)0)
+#endif
 
 // a role's input poll: N contiguous granules at g, behind the one-lane gate
 template <class P, int N, class C>
@@ -53,10 +64,11 @@ __device__ __forceinline__ void published(C &X, int ph) {
 }
 
 // 16-lane-group row over K = 1024: lane l16 holds k = l16 * 8 + tt * 128, tt < 8 (two K halves of 4)
+template <class P>
 __device__ __forceinline__ void issue_row(const uint16_t *W, int row, uint4 (&w)[8]) {
     const uint16_t *r = W + (size_t)row * H + (threadIdx.x & 15) * 8;
 #pragma unroll
-    for (int tt = 0; tt < 8; ++tt) w[tt] = ld16(r + tt * 128);
+    for (int tt = 0; tt < 8; ++tt) w[tt] = P::ldw(r + tt * 128);
 }
 
 // ------------------------------------------------------------------ QKV rows 64i .. 64i + 63 (4 x 16)
@@ -65,7 +77,7 @@ __device__ __forceinline__ void qkv_issue(const uint16_t *W, const float *norm, 
     const int t = threadIdx.x, grp = t >> 4;
 #pragma unroll
     for (int j = 0; j < 4; ++j)   // WPUB: wave w owns rows 16w .. 16w + 15 (row 16w + 4j + lane / 16) and publishes them itself
-        issue_row(W, 64 * i + (P::WPUB ? 16 * (t >> 6) + 4 * j + (grp & 3) : 16 * j + grp), wq[j]);
+        issue_row<P>(W, 64 * i + (P::WPUB ? 16 * (t >> 6) + 4 * j + (grp & 3) : 16 * j + grp), wq[j]);
     nw = ldf4(norm + 4 * t);
 }
 // RMSNorm(nw) of x (elements 4t..4t+3) -> the 64 rows -> gqkv, tagged ph
@@ -83,16 +95,25 @@ __device__ __forceinline__ void qkv_phase(C &X, int i, float4 x, const uint4 (&w
         for (int tt = 0; tt < 8; ++tt) acc[j] = dot8(wq[j][tt], *reinterpret_cast<const uint4 *>(S.xs + l16 * 8 + tt * 128), acc[j]);
     }
     if constexpr (P::WPUB) {
-        // each wave publishes its 16 rows as one whole line: lane L < 16 takes row 4j + g (j = L / 4, g = L % 4) from
-        // lane 16 g of the group that reduced it (the l16 == 0 lane, as the LDS form), no barrier
-        float pv = 0.0f;
+        // each wave publishes its 16 rows as one whole line, no barrier
         const int lane = t & 63;
+        if constexpr (Q3T_QKV_SCATTER) {
+            // the four row sums of every 16-lane group as one reduce-scatter (group_sum<16>'s tree per row, 5 adds for
+            // 16), then lane L < 16 takes group L / 4's value at its own lane position over two row swaps: that is row
+            // 4j + L / 4, j = scatter4_index(L), so the same one store writes the line's granules in a permuted order.
+            // Measured and not faster (DESIGN 2a''): off
+            const float pv = rows_gather16(group16_sum_scatter4(acc));
+            if (lane < 16)
+                g_put(X.p.gqkv + 64 * i + 16 * (t >> 6) + 4 * scatter4_index(lane) + (lane >> 2), __float_as_uint(pv), X.tag(ph));
+        } else {   // lane L < 16 takes row 4j + g (j = L / 4, g = L % 4) from lane 16 g of the group that reduced it
+            float pv = 0.0f;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float v = __shfl(group_sum<16>(acc[j]), 16 * (lane & 3));
-            if ((lane >> 2) == j) pv = v;
+            for (int j = 0; j < 4; ++j) {
+                const float v = __shfl(group_sum<16>(acc[j]), 16 * (lane & 3));
+                if ((lane >> 2) == j) pv = v;
+            }
+            if (lane < 16) g_put(X.p.gqkv + 64 * i + 16 * (t >> 6) + lane, __float_as_uint(pv), X.tag(ph));
         }
-        if (lane < 16) g_put(X.p.gqkv + 64 * i + 16 * (t >> 6) + lane, __float_as_uint(pv), X.tag(ph));
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -133,13 +154,14 @@ __device__ __forceinline__ void head_rows(C &X, const uint4 (&wq)[4][8]) {
 
 // ------------------------------------------------------------------ gate/up + SwiGLU units 32i .. 32i + 31 (2 x 16)
 // unit 32i + 16j + grp: gate row, up row 16 below (16-row interleaved blocks)
+template <class P>
 __device__ __forceinline__ void gu_issue(const uint16_t *W, const float *norm, int i, uint4 (&wg)[2][8], uint4 (&wu)[2][8], float4 &nw) {
     const int t = threadIdx.x, grp = t >> 4;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int unit = 32 * i + 16 * j + grp, row = (unit >> 4) * 32 + (unit & 15);
-        issue_row(W, row, wg[j]);
-        issue_row(W, row + 16, wu[j]);
+        issue_row<P>(W, row, wg[j]);
+        issue_row<P>(W, row + 16, wu[j]);
     }
     nw = ldf4(norm + 4 * t);
 }
@@ -180,13 +202,14 @@ __device__ __forceinline__ void gu_phase(C &X, int i, float4 x, const uint4 (&wg
 
 // ------------------------------------------------------------------ down rows lo .. lo + n - 1 (n <= 20, 5 x 4) + residual
 // row lo + 4j + grp4 (clamped: rows past n re-read row lo + n - 1), K slice = wave (k_gemv<1,1,4,PRO_F16,8>)
+template <class P>
 __device__ __forceinline__ void dn_issue(const uint16_t *W, int lo, int n, uint4 (&wd)[5][6]) {
     const int t = threadIdx.x, wave = t >> 6, grp4 = (t & 63) >> 4;
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
         const uint16_t *r = W + (size_t)(lo + min(4 * j + grp4, n - 1)) * INTER + wave * 768 + (t & 15) * 8;
 #pragma unroll
-        for (int tt = 0; tt < 6; ++tt) wd[j][tt] = ld16(r + tt * 128);
+        for (int tt = 0; tt < 6; ++tt) wd[j][tt] = P::ldw(r + tt * 128);
     }
 }
 // h (gh, tagged ph - 1: the gate/up phase of the same layer) -> the rows' four K-slice sums through S.red[par] ->

@@ -66,6 +66,12 @@ constexpr int R = NH / NKV, CHK = 64, PSLOT = 264, MAXCH = 32;   // chunk of pos
 #ifndef Q3T_TK_PUT_FIRST   // a role's publish: the other waves issue the next layer's weight prefetch only after wave 0's
 #define Q3T_TK_PUT_FIRST 0   // store instruction (their loads otherwise queue ahead of it in the CU's memory pipe)
 #endif
+#ifndef Q3T_TK_NT   // weight rows with the non-temporal policy: each is read once per step, by one CU (887 MB a step, which
+#define Q3T_TK_NT 1   // otherwise sweeps the Infinity Cache, the code predictor's weights and the K/V cache with it)
+#endif
+#ifndef Q3T_TK_KV_NT   // the attention's cached K/V rows with the same policy (read once per step, again by the next
+#define Q3T_TK_KV_NT 0   // step): no shorter step and no higher headline beside nt weights (DESIGN 2a''), so off
+#endif
 #ifndef Q3T_TK_PAIR
 #define Q3T_TK_PAIR 1   // development: 0 = O, gate/up, down, QKV; 1 = down, O, gate/up, QKV (the splits beside down)
 #endif
@@ -114,6 +120,7 @@ struct Pol {   // persist_roles.h's policy: the talker's polls are always gated 
     static constexpr bool WPUB = Q3T_TK_WPUB, PUT_FIRST = Q3T_TK_PUT_FIRST, GATE = true;
     template <int N>
     static __device__ __forceinline__ void wait(const uint64_t *g, uint32_t tag, uint32_t (&u)[N], Ctl &c) { g_waitc<N>(g, tag, u, c); }
+    static __device__ __forceinline__ uint4 ldw(const uint16_t *w) { return Q3T_TK_NT ? ld_nt16(w) : ld16(w); }
 };
 
 // ------------------------------------------------------------------ QKV rows (+ codec head after the last layer)
@@ -141,7 +148,7 @@ __device__ __forceinline__ void tk_qkv(Ctx &X) {
             qkv_issue<Pol>(S.layers[l + 1].qkv, S.layers[l + 1].attn_norm, i, wq, nw);
         } else {   // codec head rows 48i + 16j + grp
 #pragma unroll
-            for (int j = 0; j < 3; ++j) issue_row(p.head, 48 * i + 16 * j + grp, wq[j]);
+            for (int j = 0; j < 3; ++j) issue_row<Pol>(p.head, 48 * i + 16 * j + grp, wq[j]);
             nw = ldf4(p.out_norm + 4 * t);
         }
     }
@@ -176,7 +183,7 @@ __device__ __forceinline__ void tk_o(Ctx &X) {
         for (int j = 0; j < 8; ++j) {
             const uint16_t *r = W + (size_t)(128 * rb + 32 * wave + 4 * j + grp4) * (NH * D) + w * 512 + l16 * 8;
 #pragma unroll
-            for (int tt = 0; tt < 4; ++tt) wo[j][tt] = ld16(r + tt * 128);
+            for (int tt = 0; tt < 4; ++tt) wo[j][tt] = Pol::ldw(r + tt * 128);
         }
     };
     // split partials of kv groups 2w (sel 0) and 2w + 1 (sel 1): this thread's output is element t of each group
@@ -277,7 +284,7 @@ __device__ __forceinline__ void tk_gu(Ctx &X) {
     const int i = blockIdx.x - UW, t = threadIdx.x, nl = X.nl;
     uint4 wg[2][8], wu[2][8];
     float4 nw;
-    gu_issue(S.layers[0].gu, S.layers[0].ffn_norm, i, wg, wu, nw);
+    gu_issue<Pol>(S.layers[0].gu, S.layers[0].ffn_norm, i, wg, wu, nw);
     for (int l = 0; l < nl; ++l) {
         const int ph = 5 * l + 3;
         float4 xr;   // the residual stream entering the layer
@@ -301,7 +308,7 @@ __device__ __forceinline__ void tk_gu(Ctx &X) {
             x[e] = (e == 0 ? xr.x : e == 1 ? xr.y : e == 2 ? xr.z : xr.w) + s;
         }
         gu_phase<Pol>(X, i, make_float4(x[0], x[1], x[2], x[3]), wg, wu, nw, ph);
-        if (l + 1 < nl) gu_issue(S.layers[l + 1].gu, S.layers[l + 1].ffn_norm, i, wg, wu, nw);
+        if (l + 1 < nl) gu_issue<Pol>(S.layers[l + 1].gu, S.layers[l + 1].ffn_norm, i, wg, wu, nw);
     }
 }
 
@@ -312,7 +319,7 @@ __device__ __forceinline__ void tk_dn(Ctx &X) {
     const int i = blockIdx.x - DW, t = threadIdx.x, nl = X.nl;
     const int lo = i * H / ND, n = (i + 1) * H / ND - lo;
     uint4 wd[5][6];
-    dn_issue(S.layers[0].down, lo, n, wd);
+    dn_issue<Pol>(S.layers[0].down, lo, n, wd);
     for (int l = 0; l < nl; ++l) {
         if (t < n) {   // x' = x + (((o0 + o1) + o2) + o3) of row lo + t (as the gate/up workgroups)
             float xr;
@@ -329,7 +336,7 @@ __device__ __forceinline__ void tk_dn(Ctx &X) {
             S.xr[t] = xr + s;
         }
         dn_phase<Pol>(X, lo, n, l & 1, wd, 5 * l + 4);
-        if (l + 1 < nl) dn_issue(S.layers[l + 1].down, lo, n, wd);
+        if (l + 1 < nl) dn_issue<Pol>(S.layers[l + 1].down, lo, n, wd);
     }
 }
 
@@ -354,8 +361,8 @@ __device__ __forceinline__ void tk_att(Ctx &X) {
 #pragma unroll
         for (int pi = 0; pi < NP; ++pi) {
             const int j = min(j0 + pi * 16 + pg, pos);
-            kr[pi] = ld16(p.kc + o + (size_t)j * D + li * 8);
-            vr[pi] = ld16(p.vc + o + (size_t)j * D + li * 8);
+            kr[pi] = Q3T_TK_KV_NT ? ld_nt16(p.kc + o + (size_t)j * D + li * 8) : ld16(p.kc + o + (size_t)j * D + li * 8);
+            vr[pi] = Q3T_TK_KV_NT ? ld_nt16(p.vc + o + (size_t)j * D + li * 8) : ld16(p.vc + o + (size_t)j * D + li * 8);
         }
         const float *nwv = wave == 2 ? S.layers[l].kn : S.layers[l].qn;
         hn[0] = nwv[lane];

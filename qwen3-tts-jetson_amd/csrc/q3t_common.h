@@ -93,9 +93,12 @@ __device__ __forceinline__ uint4 ldg16(const void *p) {
     const u32x4_t v = *(gv *)p;
     return make_uint4(v.x, v.y, v.z, v.w);
 }
-// 16-byte streaming load of once-read weights (non-temporal policy, microarch 'nt-weights')
+// 16-byte streaming load of once-read weights (non-temporal policy, microarch 'nt-weights'), through a global pointer
+// like ldg16: global_load_dwordx4 ... nt, scheduled and waited for exactly as the default-policy load (through a
+// generic pointer it was a flat load, whose waits drain every earlier load)
 __device__ __forceinline__ uint4 ld_nt16(const void *ptr) {
-    const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(ptr));
+    typedef const __attribute__((address_space(1))) u32x4_t gv;
+    const u32x4_t v = __builtin_nontemporal_load((gv *)ptr);
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
@@ -111,10 +114,22 @@ template <int CTRL>
 __device__ __forceinline__ unsigned dpp_u(unsigned v) {
     return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
 }
+// dpp_u for a permutation in which every lane reads a valid lane (quad_perm, row_half_mirror, row_mirror).
+// Q3T_DPP_BOUND=1: with bound_ctrl the old value can never show, so the compiler does not initialise the destination
+// (f64 steps cannot fold into their add: each costs two v_mov_b32 of zero on top of the two v_mov_b32_dpp).  The same
+// bits (tests/test_gpu_reduce_ops.py), but no shorter kernel in the A/B (DESIGN 2a''), so it is off.
+#ifndef Q3T_DPP_BOUND
+#define Q3T_DPP_BOUND 0
+#endif
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp_all_u(unsigned v) {
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, Q3T_DPP_BOUND != 0);
+}
 template <int CTRL>
 __device__ __forceinline__ double dpp_d(double v) {
+    static_assert(CTRL == 0xB1 || CTRL == 0x4E || CTRL == 0x141 || CTRL == 0x140, "all lanes valid");
     const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const unsigned lo = dpp_u<CTRL>((unsigned)u), hi = dpp_u<CTRL>((unsigned)(u >> 32));
+    const unsigned lo = dpp_all_u<CTRL>((unsigned)u), hi = dpp_all_u<CTRL>((unsigned)(u >> 32));
     return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_HALF_MIRROR = 0x141, DPP_MIRROR = 0x140;
@@ -149,6 +164,34 @@ __device__ __forceinline__ float group_sum(float v) {   // all-reduce inside ali
     if constexpr (W >= 64) v += xrow32(v);
     return v;
 }
+// group_sum<16> of four values as a reduce-scatter: lane l (position in its 16-lane row) ends with the sum of value
+// scatter4_index(l), by group_sum<16>'s own tree: every step adds the same two operands, a lane only keeps just the
+// values it still owns (2, then 1), so 5 adds take the place of 16.  The owner bits are taken relative to bit 2 of the
+// lane, so that the partners of row_half_mirror (7 - l) and row_mirror (15 - l), which complement bits 0 and 1 together
+// with bit 2, own the same value; the partners of xor 1 and xor 2 own the other half, as a reduce-scatter needs.
+__device__ __forceinline__ int scatter4_index(int l) { return 2 * ((l ^ (l >> 2)) & 1) + (((l >> 1) ^ (l >> 2)) & 1); }
+__device__ __forceinline__ float group16_sum_scatter4(const float (&a)[4]) {
+    const int l = threadIdx.x;
+    const bool e0 = ((l ^ (l >> 2)) & 1) != 0, e1 = (((l >> 1) ^ (l >> 2)) & 1) != 0;
+    const float r0 = (e0 ? a[2] : a[0]) + dpp_f<DPP_XOR1>(e0 ? a[0] : a[2]);
+    const float r1 = (e0 ? a[3] : a[1]) + dpp_f<DPP_XOR1>(e0 ? a[1] : a[3]);
+    float q = (e1 ? r1 : r0) + dpp_f<DPP_XOR2>(e1 ? r0 : r1);
+    q += dpp_f<DPP_HALF_MIRROR>(q);
+    q += dpp_f<DPP_MIRROR>(q);
+    return q;
+}
+// lane L < 16 of the wave: the value of row (L >> 2) at lane position L (two row swaps, no LDS crossbar)
+__device__ __forceinline__ float rows_gather16(float v) {
+    const int l = threadIdx.x;
+    // the swaps stand outside the selects (every lane takes part in them), and their second result is the partner's
+    // value in the even rows (xrow16_u) and in the lower half (xrow32_u): rows 0 and 2, then row 0, are all that is read
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const auto s16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    const unsigned x = (l & 4) ? (unsigned)s16[1] : u;
+    const auto s32 = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+    return __builtin_bit_cast(float, (l & 8) ? (unsigned)s32[1] : x);
+}
+
 template <int W>
 __device__ __forceinline__ float group_max(float v) {
     v = fmaxf(v, dpp_f<DPP_XOR1>(v));

@@ -13,7 +13,6 @@
 
 #include "devlock.h"
 #include <chrono>
-#include <condition_variable>
 #include "speaker.h"
 #include "vocoder.h"
 
@@ -40,10 +39,11 @@ DeviceLock::~DeviceLock() {
 }
 
 namespace {
-bool env_flag(const char *name, bool dflt) {
+int env_int(const char *name, int dflt) {
     const char *e = std::getenv(name);
-    return e ? std::atoi(e) != 0 : dflt;
+    return e ? std::atoi(e) : dflt;
 }
+bool env_flag(const char *name, bool dflt) { return env_int(name, dflt) != 0; }
 }  // namespace
 
 Options Options::from_env() {
@@ -61,6 +61,15 @@ Options Options::from_env() {
     o.fused_select = env_flag("Q3T_FUSED_SELECT", true);
     o.defer_cp_select = env_flag("Q3T_CP_DEFER_SELECT", true);
     o.attn_split = env_flag("Q3T_ATTN_SPLIT", false);
+    // weight prefetch of the batched talker stack: 0 off (default), 1 the norms before QKV and gate/up, 2 also the gate/up
+    // GEMM for the down projection (its 64-token tiles leave a quarter of the CUs free).  Off since round 5: level 2 saved
+    // 0.3 % of the 64-slot step (1.5960 -> 1.5912 ms, two A/B pairs) for 755 MB more fabric reads per step (FETCH 3,111 ->
+    // 3,866 MB: every prefetched line is read twice, once into the Infinity Cache and once by the GEMM)
+    o.mm_prefetch = env_int("Q3T_MM_PREFETCH", 0);
+    // gate/up on 64-token tiles: 192 workgroups of one per CU instead of 384 (two on half the CUs, which set the tail);
+    // the other projections keep 32-token tiles.  64-slot talker step 1.574 -> 1.549 ms (two A/B pairs,
+    // tools/dev/exp_gutt.sh); the tile never changes a row's arithmetic.  Q3T_MM_GU_TT=1 restores 32-token tiles.
+    o.mm_gu_tt = env_int("Q3T_MM_GU_TT", 2);
     if (const char *e = std::getenv("Q3T_PERSIST_FAULT_AT")) o.persist_fault_at = (unsigned)std::max(0, std::atoi(e));
 #ifdef Q3T_DEV
     if (const char *e = std::getenv("Q3T_POLL_EVERY")) o.poll_every = std::max(1, std::atoi(e));
@@ -406,7 +415,6 @@ bool Engine::upload_weights_rest() {
 bool Engine::alloc_state() {
     const int S = max_slots_, H = c_.hidden, D = c_.head_dim;
     const int QKV = std::max(c_.n_heads + 2 * c_.n_kv, c_.cp_heads + 2 * c_.cp_kv) * D;   // talker / code predictor
-    const int max_splits = (max_ctx_ + ATTN_CHUNK - 1) / ATTN_CHUNK;
     max_trailing_ = 512;
     x_ = dalloc<float>((size_t)S * H);
     qkv_ = dalloc<float>((size_t)S * QKV);
@@ -416,17 +424,16 @@ bool Engine::alloc_state() {
     cp_in1_ = dalloc<float>((size_t)S * H);
     cp_logits_ = dalloc<float>((size_t)S * c_.cp_vocab);
     // (the code-predictor stack runs attn_decode on these too: sized for the wider of the two head layouts)
-    part_ = dalloc<float>((size_t)S * std::max(c_.n_heads, c_.cp_heads) * max_splits * (D + 2));
+    part_ = dalloc<float>((size_t)S * std::max(c_.n_heads, c_.cp_heads) * talker_cache().max_splits * (D + 2));
     ticket_ = dalloc<unsigned>((size_t)S * std::max(c_.n_kv, c_.cp_kv));
     sel_ticket_ = dalloc<unsigned>((size_t)S);
     attn_ = dalloc<uint16_t>((size_t)S * std::max(c_.n_heads, c_.cp_heads) * D);
     hmlp_ = dalloc<uint16_t>((size_t)S * std::max(c_.inter, c_.cp_inter));
     xn_ = dalloc<uint16_t>((size_t)S * H);
     parts_ = dalloc<float>((size_t)4 * S * H);
-    const size_t kv_layer = (size_t)S * c_.n_kv * max_ctx_ * D;
+    const size_t kv_layer = talker_cache().kv_layer, cpkv_layer = cp_cache(0).kv_layer;
     kc_ = dalloc<uint16_t>(kv_layer * c_.n_layers);
     vc_ = dalloc<uint16_t>(kv_layer * c_.n_layers);
-    const size_t cpkv_layer = (size_t)S * c_.cp_kv * 16 * D;
     cpkc_ = dalloc<uint16_t>(cpkv_layer * c_.cp_layers);
     cpvc_ = dalloc<uint16_t>(cpkv_layer * c_.cp_layers);
     pos_ = dalloc<int>(S);
@@ -765,7 +772,7 @@ bool Engine::debug_read(int which, void *dst, size_t bytes) {
     }
     if (which == 4 && !pstate_) {   // launch-per-phase attention partial buffer (dev dumps)
         Q3T_HIP(hipStreamSynchronize(stream_));
-        Q3T_HIP(hipMemcpy(dst, part_, std::min<size_t>(bytes, (size_t)max_slots_ * c_.n_heads * ((max_ctx_ + ATTN_CHUNK - 1) / ATTN_CHUNK) * (c_.head_dim + 2) * 4), hipMemcpyDeviceToHost));
+        Q3T_HIP(hipMemcpy(dst, part_, std::min<size_t>(bytes, (size_t)max_slots_ * c_.n_heads * talker_cache().max_splits * (c_.head_dim + 2) * 4), hipMemcpyDeviceToHost));
         return true;
     }
     if (which == 4 && pstate_) {   // persistent-step partial buffer (dev dumps)
@@ -829,6 +836,58 @@ struct StackInput {
     SelectSpec sel;                      // PRO_SEL_G1: selection of the gathered token
     const float *sel_logits = nullptr;
 };
+// one run of a decoder stack: where it computes, the cache it attends over and the per-call choices
+struct StackRun {
+    StackBufs buf;
+    StackCache kv;
+    const StackInput *in0 = nullptr;     // replaces layer 0's activation source (null: buf.x as it stands)
+    // the batch whose kernel choices this run reproduces, 0: its own S (a continuous-batching admission runs ONE slot
+    // and the causal prefill its rows with the kernels and K split of the batch, so the per-token arithmetic is the
+    // batch's)
+    int family = 0;
+    const PrefillAttnParams *pf = nullptr;   // the causal prefill's attention in place of the decode launch
+    bool cp_attn = false;                // matrix-core stack: the code predictor's (k_attn_small, no weight prefetch)
+    bool fused_cp_attn = false;          // vector stack: that attention recomputed inside the O-projection prologue
+    // matrix-core stack: the norm after the last layer (null: none, code-predictor pass 0 has no head), its f32 side
+    // output, and layer 0's raw QKV rows from the per-token table (the tab_* fields) in place of its QKV GEMM
+    const float *final_norm = nullptr;
+    float *final_side = nullptr;
+    AttnParams l0tab;                    // (only its qkv_tab / tab_* fields are read)
+};
+struct MmAttn { int seqk, small; bool l0tab; };   // the matrix-core stack's attention kernel choices
+
+// layer il's attention of either stack body: the decode launch over each slot's new token, or the causal prefill's
+// (r.pf) over layer il's cache and the stack's activations
+static bool stack_attn(const Config &c, const DevLayer &l, size_t il, int S, const StackRun &r, const MmAttn *mm, hipStream_t s) {
+    uint16_t *kc = r.kv.kc + il * r.kv.kv_layer, *vc = r.kv.vc + il * r.kv.kv_layer;
+    if (r.pf) {
+        PrefillAttnParams q = *r.pf;
+        q.qkv = r.buf.qkv; q.qn = l.qn; q.kn = l.kn; q.eps = c.eps; q.rope = r.kv.rope; q.kc = kc; q.vc = vc;
+        q.n_ctx = r.kv.n_ctx; q.nH = c.n_heads; q.nKV = c.n_kv; q.D = c.head_dim; q.out = r.buf.attn;
+        return prefill_attn(q, s);
+    }
+    AttnParams a = mm && mm->l0tab && il == 0 ? r.l0tab : AttnParams();
+    a.qkv = r.buf.qkv; a.qn = l.qn; a.kn = l.kn; a.eps = c.eps; a.rope = r.kv.rope; a.pos = r.kv.pos; a.kc = kc; a.vc = vc;
+    a.n_ctx = r.kv.n_ctx; a.S = S; a.nH = c.n_heads; a.nKV = c.n_kv; a.D = c.head_dim;
+    a.max_splits = r.kv.max_splits;   // chunk 128 measured no faster at 64 slots (1.79 vs 1.77 ms per step)
+    a.part = r.kv.part; a.ticket = r.kv.ticket; a.out = r.buf.attn;
+    if (mm) { a.seqk = mm->seqk; a.small = mm->small; }
+#ifdef Q3T_DEV
+    if (!mm && il == 0 && std::getenv("Q3T_PERSIST_DBG")) a.dbg = r.kv.part;
+#endif
+    return attn_decode(a, s);
+}
+
+// final RMSNorm + head GEMV -> logits.  h names the head: W, N, out_f32, force_mm, and for the vector form (the norm in
+// the GEMV's prologue, over b.x) the norm weight nw, the normalised rows' side_out, family_b and a fused selection.
+// hoisted: the matrix-core stack's last resid_norm already normalised the rows into b.xn (and wrote its side output)
+static bool head_gemv(const Config &c, GemvParams h, const StackBufs &b, bool hoisted, int S, hipStream_t s) {
+    h.K = c.hidden; h.B = S; h.ldx = c.hidden; h.ldo = h.N; h.eps = c.eps;
+    h.pro = hoisted ? PRO_F16 : PRO_RMS;
+    h.x = hoisted ? (const void *)b.xn : b.x;
+    if (hoisted) { h.nw = nullptr; h.side_out = nullptr; h.family_b = 0; h.sel = SelectSpec(); }
+    return gemv(h, s);
+}
 
 // ------------------------------------------------------------------------------------------ batched decoder stack
 // matrix-core path (S >= gemm_mfma_min_batch()): 7 launches per layer so that every projection fills the chip:
@@ -848,55 +907,30 @@ static int splitk_for(int N, int S, int K) {
         if (ok(ks)) return ks;
     return 1;
 }
-// the causal prefill's attention in place of the decode launch: layer `il`'s cache and the stack's activations
-static bool prefill_layer_attn(const PrefillAttnParams &pf, const Config &c, const DevLayer &l, const float *qkv,
-                               const float *rope, uint16_t *kc, uint16_t *vc, int n_ctx, uint16_t *attn, hipStream_t s) {
-    PrefillAttnParams q = pf;
-    q.qkv = qkv; q.qn = l.qn; q.kn = l.kn; q.eps = c.eps; q.rope = rope; q.kc = kc; q.vc = vc;
-    q.n_ctx = n_ctx; q.nH = c.n_heads; q.nKV = c.n_kv; q.D = c.head_dim; q.out = attn;
-    return prefill_attn(q, s);
-}
-
-// weight prefetch of the batched talker stack: 0 off (default), 1 the norms before QKV and gate/up, 2 also the gate/up
-// GEMM for the down projection (its 64-token tiles leave a quarter of the CUs free).  Off since round 5: level 2 saved
-// 0.3 % of the 64-slot step (1.5960 -> 1.5912 ms, two A/B pairs) for 755 MB more fabric reads per step (FETCH 3,111 ->
-// 3,866 MB: every prefetched line is read twice, once into the Infinity Cache and once by the GEMM)
-static const int g_mm_prefetch = [] { const char *e = std::getenv("Q3T_MM_PREFETCH"); return e ? std::atoi(e) : 0; }();
-// gate/up on 64-token tiles: 192 workgroups of one per CU instead of 384 (two on half the CUs, which set the tail);
-// the other projections keep 32-token tiles.  64-slot talker step 1.574 -> 1.549 ms (two A/B pairs,
-// tools/dev/exp_gutt.sh); the tile never changes a row's arithmetic.  Q3T_MM_GU_TT=1 restores 32-token tiles.
-static const int g_mm_gu_tt = [] { const char *e = std::getenv("Q3T_MM_GU_TT"); return e ? std::atoi(e) : 2; }();
-static bool decoder_stack_mm(const Config &c, bool attn_split, const std::vector<DevLayer> &layers, int S, float *x, uint16_t *xn,
-                             float *parts, float *qkv, uint16_t *attn, uint16_t *hmlp, uint16_t *kc, uint16_t *vc,
-                             size_t kv_layer, int n_ctx, int max_splits, const int *pos, const float *rope, float *part,
-                             unsigned *ticket, hipStream_t s, const StackInput *in0, const float *final_norm,
-                             float *final_side, int S_main = 0, bool cp_attn = false, const PrefillAttnParams *pf = nullptr,
-                             const AttnParams *l0tab = nullptr) {
-    // S_main: the batch whose kernel choices this stack reproduces (a continuous-batching admission runs ONE slot
-    // with the S_main-slot kernels, so its per-token arithmetic is the batch's)
-    if (S_main <= 0) S_main = S;
+static bool decoder_stack_mm(const Config &c, const Options &opt, const std::vector<DevLayer> &layers, int S, const StackRun &r,
+                             hipStream_t s) {
+    float *const x = r.buf.x, *const parts = r.buf.parts, *const qkv = r.buf.qkv;
+    uint16_t *const xn = r.buf.xn, *const attn = r.buf.attn, *const hmlp = r.buf.hmlp;
+    const int S_main = r.family > 0 ? r.family : S;
     const bool force = S < gemm_mfma_min_batch();
     const int H = c.hidden, D = c.head_dim, QKV = (c.n_heads + 2 * c.n_kv) * D;
     ResidNorm rn;
     rn.S = S; rn.H = H; rn.eps = c.eps; rn.x = x; rn.xn = xn;
-    if (in0 && in0->prenormed) {
-        // the previous launch (token selection) gathered and normalised layer 0's input
-    } else if (in0 && (in0->pro == PRO_RMS_G1 || in0->pro == PRO_RMS_G16)) {
-        if (!gather_sum(in0->gs, in0->pro == PRO_RMS_G16 ? 16 : 1, S, H, x, H, s)) return false;
-    } else if (in0 && in0->x) {
-        rn.xin = in0->x;   // copied into the residual stream by the norm
-    }
     rn.nw = layers[0].attn_norm;
-    if (!(in0 && in0->prenormed) && !resid_norm(rn, s)) return false;
+    const bool gathered = r.in0 && (r.in0->pro == PRO_RMS_G1 || r.in0->pro == PRO_RMS_G16);
+    if (r.in0 && !gathered) rn.xin = r.in0->x;   // copied into the residual stream by the norm
+    // prenormed: the previous launch (token selection) gathered and normalised layer 0's input
+    if (!(r.in0 && r.in0->prenormed)) {
+        if (gathered && !gather_sum(r.in0->gs, r.in0->pro == PRO_RMS_G16 ? 16 : 1, S, H, x, H, s)) return false;
+        if (!resid_norm(rn, s)) return false;
+    }
     rn.xin = nullptr;
     // the code predictor's <= 16 positions run on k_attn_small, which can read layer 0's raw QKV rows from the per-token
-    // table (l0tab: passes 1..15) instead of a QKV GEMM over xn
-    const bool small = cp_attn && n_ctx <= 16 && D == 128 && c.n_heads == 2 * c.n_kv;
-#ifdef Q3T_NO_SMALL_ATTN
-    const bool use_tab = false;
-#else
-    const bool use_tab = small && l0tab && l0tab->qkv_tab && !pf;
-#endif
+    // table (l0tab: passes 1..15) instead of a QKV GEMM over xn (one wave per (slot, kv head), the 0.6B head layout);
+    // k_attn_seq once there are enough (slot, kv head) pairs to fill the chip
+    const bool small = r.cp_attn && r.kv.n_ctx <= 16 && D == 128 && c.n_heads == 2 * c.n_kv;
+    const bool use_tab = small && r.l0tab.qkv_tab && !r.pf;
+    const MmAttn am{S_main >= 16 && !opt.attn_split, small, use_tab};
     for (size_t il = 0; il < layers.size(); ++il) {
         const DevLayer &l = layers[il];
         GemvParams g;
@@ -904,25 +938,9 @@ static bool decoder_stack_mm(const Config &c, bool attn_split, const std::vector
         g.pro = PRO_F16; g.x = xn; g.ldx = H;
         g.out_f32 = qkv; g.ldo = QKV; g.force_mm = force;
         if (!(il == 0 && use_tab) && !gemv(g, s)) return false;
-        AttnParams a;
-        a.qkv = qkv; a.qn = l.qn; a.kn = l.kn; a.eps = c.eps; a.rope = rope; a.pos = pos;
-        a.kc = kc + il * kv_layer; a.vc = vc + il * kv_layer;
-        a.n_ctx = n_ctx; a.S = S; a.nH = c.n_heads; a.nKV = c.n_kv; a.D = D;
-        a.max_splits = max_splits;   // chunk 128 measured no faster at 64 slots (1.79 vs 1.77 ms per step)
-        a.seqk = S_main >= 16 && !attn_split;   // enough (slot, kv head) pairs to fill the chip
-        // the code predictor's <= 16 positions: one wave per (slot, kv head) (the 0.6B head layout)
-        a.small = small;
-        if (il == 0 && use_tab) {
-            a.qkv_tab = l0tab->qkv_tab; a.tab_tok = l0tab->tab_tok; a.tab_ld = l0tab->tab_ld; a.tab_col = l0tab->tab_col;
-            a.tab_row0 = l0tab->tab_row0;
-        }
-#ifdef Q3T_NO_SMALL_ATTN
-        a.small = 0;   // experiment builds: the code predictor on k_attn_seq / k_attn as before
-#endif
-        a.part = part; a.ticket = ticket; a.out = attn;
-        if (pf ? !prefill_layer_attn(*pf, c, l, qkv, rope, a.kc, a.vc, n_ctx, attn, s) : !attn_decode(a, s)) return false;
+        if (!stack_attn(c, l, il, S, r, &am, s)) return false;
         // code-predictor pass 0 (no head): its last layer's K/V rows, appended above, are all that is ever read
-        if (il + 1 == layers.size() && !final_norm) break;
+        if (il + 1 == layers.size() && !r.final_norm) break;
         GemvParams o;
         o.W = l.o; o.N = H; o.K = c.n_heads * D; o.B = S;
         o.pro = PRO_F16; o.x = attn; o.ldx = c.n_heads * D;
@@ -931,14 +949,14 @@ static bool decoder_stack_mm(const Config &c, bool attn_split, const std::vector
         rn.parts = parts; rn.ksplit = o.ksplit; rn.nw = l.ffn_norm; rn.side = nullptr;
         // the talker's weights stream from HBM each step: the norm before a projection touches that projection's lines
         // (the code predictor's 157 MB stay in the Infinity Cache across its 16 passes anyway)
-        const bool pf_w = !cp_attn && g_mm_prefetch > 0;
+        const bool pf_w = !r.cp_attn && opt.mm_prefetch > 0;
         rn.prefetch = pf_w ? l.gu : nullptr; rn.prefetch_bytes = (size_t)2 * c.inter * H * 2;
         if (!resid_norm(rn, s)) return false;
         GemvParams gu;
         gu.W = l.gu; gu.N = 2 * c.inter; gu.K = H; gu.B = S;
         gu.pro = PRO_F16; gu.x = xn; gu.ldx = H;
-        gu.act = ACT_SWIGLU; gu.out_f16 = hmlp; gu.ldo = c.inter; gu.force_mm = force; gu.mm_tt = g_mm_gu_tt;
-        if (pf_w && g_mm_prefetch > 1) { gu.prefetch = l.down; gu.prefetch_bytes = (size_t)c.inter * H * 2; }
+        gu.act = ACT_SWIGLU; gu.out_f16 = hmlp; gu.ldo = c.inter; gu.force_mm = force; gu.mm_tt = opt.mm_gu_tt;
+        if (pf_w && opt.mm_prefetch > 1) { gu.prefetch = l.down; gu.prefetch_bytes = (size_t)c.inter * H * 2; }
         if (!gemv(gu, s)) return false;
         GemvParams dn;
         dn.W = l.down; dn.N = H; dn.K = c.inter; dn.B = S;
@@ -947,10 +965,10 @@ static bool decoder_stack_mm(const Config &c, bool attn_split, const std::vector
         dn.xcd_slices = true;   // each XCD fetches 1 / ksplit of hmlp (FETCH 1.42x -> 1.06x of the algorithmic bytes)
         if (!gemv(dn, s)) return false;
         const bool last = il + 1 == layers.size();
-        if (last && !final_norm) break;   // code-predictor pass 0: only its K/V caches are read afterwards
+        if (last && !r.final_norm) break;   // code-predictor pass 0: only its K/V caches are read afterwards
         rn.parts = parts; rn.ksplit = dn.ksplit;
-        rn.nw = last ? (final_norm ? final_norm : l.ffn_norm) : layers[il + 1].attn_norm;
-        rn.side = last ? final_side : nullptr;
+        rn.nw = last ? (r.final_norm ? r.final_norm : l.ffn_norm) : layers[il + 1].attn_norm;
+        rn.side = last ? r.final_side : nullptr;
         rn.prefetch = pf_w && !last ? layers[il + 1].qkv : nullptr; rn.prefetch_bytes = (size_t)QKV * H * 2;
         if (!resid_norm(rn, s)) return false;
         rn.prefetch = nullptr;
@@ -961,56 +979,44 @@ static bool decoder_stack_mm(const Config &c, bool attn_split, const std::vector
 // ------------------------------------------------------------------------------------------ one decoder stack
 // 5 launches per layer: [RMSNorm+QKV GEMV] [head-norm+RoPE+KV-append+attention] [O GEMV + residual]
 // [RMSNorm+gate/up GEMV+SwiGLU] [down GEMV + residual]   (tts_transformer.cpp:1410-1494)
-// `in0` (optional) replaces layer 0's activation source: a gather prologue or another f32 buffer, with the raw
+// `r.in0` (optional) replaces layer 0's activation source: a gather prologue or another f32 buffer, with the raw
 // rows written to x (the residual stream) by the QKV kernel itself.
 
-static bool decoder_stack(const Config &c, const std::vector<DevLayer> &layers, int S, float *x, float *qkv,
-                          uint16_t *attn, uint16_t *hmlp, uint16_t *kc, uint16_t *vc, size_t kv_layer, int n_ctx,
-                          int max_splits, const int *pos, const float *rope, float *part, unsigned *ticket,
-                          hipStream_t s, const StackInput *in0 = nullptr, bool fused_cp_attn = false,
-                          const PrefillAttnParams *pf = nullptr, int family_b = 0) {
-    // pf: the causal prefill (S = its rows, run with the vector kernels of a family_b-slot step)
-    const int H = c.hidden, D = c.head_dim, QKV = (c.n_heads + 2 * c.n_kv) * D;
+static bool decoder_stack(const Config &c, const std::vector<DevLayer> &layers, int S, const StackRun &r, hipStream_t s) {
+    // r.pf: the causal prefill (S = its rows, run with the vector kernels of a family_b-slot step)
+    float *const x = r.buf.x, *const qkv = r.buf.qkv;
+    uint16_t *const attn = r.buf.attn, *const hmlp = r.buf.hmlp;
+    const int H = c.hidden, D = c.head_dim, QKV = (c.n_heads + 2 * c.n_kv) * D, family_b = r.family;
     // batched (matrix-core) path: gathers become their own launch and the code predictor's attention runs unfused
     const bool mm = (family_b > 0 ? family_b : S) >= gemm_mfma_min_batch();
-    if (mm) fused_cp_attn = false;
+    const bool fused_cp_attn = r.fused_cp_attn && !mm && !r.pf;
     for (size_t il = 0; il < layers.size(); ++il) {
         const DevLayer &l = layers[il];
         GemvParams g;
         g.W = l.qkv; g.N = QKV; g.K = H; g.B = S;
         g.pro = PRO_RMS; g.x = x; g.ldx = H; g.nw = l.attn_norm; g.eps = c.eps;
-        if (il == 0 && in0) {
+        if (il == 0 && r.in0) {
             // the gather as its own launch: batched path (no gather prologue in the GEMM), or rows wider than the
             // GEMV's gather prologue (K > 1024: the 1.7B talker) -- the same summation order either way
-            if ((mm || H > 1024) && (in0->pro == PRO_RMS_G1 || in0->pro == PRO_RMS_G16)) {
-                if (!gather_sum(in0->gs, in0->pro == PRO_RMS_G16 ? 16 : 1, S, H, x, H, s)) return false;
+            if ((mm || H > 1024) && (r.in0->pro == PRO_RMS_G1 || r.in0->pro == PRO_RMS_G16)) {
+                if (!gather_sum(r.in0->gs, r.in0->pro == PRO_RMS_G16 ? 16 : 1, S, H, x, H, s)) return false;
             } else {
-                g.pro = in0->pro; g.x = in0->x; g.gs = in0->gs; g.raw_out = x;
-                g.sel = in0->sel; g.sel_logits = in0->sel_logits;
+                g.pro = r.in0->pro; g.x = r.in0->x; g.gs = r.in0->gs; g.raw_out = x;
+                g.sel = r.in0->sel; g.sel_logits = r.in0->sel_logits;
             }
         }
         g.out_f32 = qkv; g.ldo = QKV; g.family_b = family_b;
         if (!gemv(g, s)) return false;
         GemvParams o;
         o.W = l.o; o.N = H; o.K = c.n_heads * D; o.B = S; o.family_b = family_b;
-        if (pf) {
-            if (!prefill_layer_attn(*pf, c, l, qkv, rope, kc + il * kv_layer, vc + il * kv_layer, n_ctx, attn, s)) return false;
-            o.pro = PRO_F16; o.x = attn; o.ldx = c.n_heads * D;
-        } else if (fused_cp_attn) {
+        if (fused_cp_attn) {
             // code predictor: attention recomputed inside the O-projection prologue (<= 16 positions)
             o.pro = PRO_CPATT;
             o.att.qkv = qkv; o.att.ld = QKV; o.att.qn = l.qn; o.att.kn = l.kn; o.att.eps = c.eps;
-            o.att.rope = rope; o.att.pos = pos; o.att.kc = kc + il * kv_layer; o.att.vc = vc + il * kv_layer;
+            o.att.rope = r.kv.rope; o.att.pos = r.kv.pos;
+            o.att.kc = r.kv.kc + il * r.kv.kv_layer; o.att.vc = r.kv.vc + il * r.kv.kv_layer;
         } else {
-            AttnParams a;
-            a.qkv = qkv; a.qn = l.qn; a.kn = l.kn; a.eps = c.eps; a.rope = rope; a.pos = pos;
-            a.kc = kc + il * kv_layer; a.vc = vc + il * kv_layer;
-            a.n_ctx = n_ctx; a.S = S; a.nH = c.n_heads; a.nKV = c.n_kv; a.D = D;
-            a.max_splits = max_splits; a.part = part; a.ticket = ticket; a.out = attn;
-#ifdef Q3T_DEV
-            if (il == 0 && std::getenv("Q3T_PERSIST_DBG")) a.dbg = part;
-#endif
-            if (!attn_decode(a, s)) return false;
+            if (!stack_attn(c, l, il, S, r, nullptr, s)) return false;
             o.pro = PRO_F16; o.x = attn; o.ldx = c.n_heads * D;
         }
         o.resid = x; o.ldr = H; o.out_f32 = x; o.ldo = H;
@@ -1048,77 +1054,78 @@ SelectSpec Engine::select_spec(int mode, const GenParams &gp, int frame_offset, 
 // frame's 16 codes (PRO_RMS_G16) instead of being read from x_
 // select_next: the codec head's last workgroup also selects CB0 of the NEXT frame (frame_ + 1) in the same launch
 bool Engine::enqueue_talker(int S, hipStream_t s, bool gather_input, bool select_next, bool prenormed, bool *fold_advance) {
-    const int H = c_.hidden;
-    const size_t kv_layer = (size_t)max_slots_ * c_.n_kv * max_ctx_ * c_.head_dim;
-    const int max_splits = (max_ctx_ + ATTN_CHUNK - 1) / ATTN_CHUNK;
-    if (S == 1 && persist_) {
-        PersistParams p;
-        persist_carve(pstate_, p);
-        p.L = pl_dev_; p.n_layers = c_.n_layers; p.eps = c_.eps;
-        p.gather = gather_input ? 1 : 0;
-        p.x_in = x_;
-        p.gs.tok = tokens_; p.gs.tok_ld = 16; p.gs.tabs = tabs16_dev_;
-        p.gs.tr = trailing_; p.gs.tr_len = trailing_len_; p.gs.frame = frame_;
-        p.gs.tr_ld = max_trailing_ * H; p.gs.pad = tts_pad_;
-        p.rope = rope_; p.pos = pos_; p.kc = kc_; p.vc = vc_; p.kv_layer = kv_layer; p.n_ctx = max_ctx_;
-        p.head = codec_head_; p.out_norm = out_norm_; p.hidden = hidden_; p.logits = logits_;
-        if (select_next) p.sel = select_spec(SEL_CB0, gp_, 1, 0);
-        p.prof = pprof_;
-        if (tk_roles_) {
-            if (fold_advance && opt_.fold_advance) {
-                p.adv_pos = pos_; p.adv_frame = frame_; p.adv_done = done_;
-                *fold_advance = true;
-            }
-            return persist_tk_roles(p, s);
-        }
-        return persist_talker_step(p, s);
-    }
-    StackInput in0;
-    if (gather_input) {
-        in0.pro = PRO_RMS_G16;
-        in0.gs.tok = tokens_; in0.gs.tok_ld = 16; in0.gs.tabs = tabs16_dev_;
-        in0.gs.tr = trailing_; in0.gs.tr_len = trailing_len_; in0.gs.frame = frame_;
-        in0.gs.tr_ld = max_trailing_ * H; in0.gs.pad = tts_pad_;
-        in0.prenormed = prenormed;
-    }
-    const bool mm = use_mm(S);   // batched: one selection workgroup per slot after the head
-    if (use_tkb(S)) {   // batched: the whole step as one persistent launch (persist_tkb.hip)
-        if (gather_input && !prenormed && !gather_sum(in0.gs, 16, S, H, x_, H, s)) return false;
-        TkbParams p;
-        p.L = pl_dev_; p.n_layers = c_.n_layers; p.head = codec_head_; p.out_norm = out_norm_;
-        p.x_in = x_; p.hidden = hidden_; p.logits = logits_;
-        p.rope = rope_; p.pos = pos_; p.kc = kc_; p.vc = vc_; p.kv_layer = kv_layer; p.n_ctx = max_ctx_;
-        if (select_next) { p.select = 1; p.sel = select_spec(SEL_CB0, gp_, 1, 0); }
-        p.S = S; p.eps = c_.eps;
-        p.state = tkb_state_;
-        p.prof = pprof_;
-        return persist_talker_batched(p, s);
-    }
-    if (mm) {
-        if (!decoder_stack_mm(c_, opt_.attn_split, L_, S, x_, xn_, parts_, qkv_, attn_, hmlp_, kc_, vc_, kv_layer, max_ctx_, max_splits, pos_,
-                              rope_, part_, ticket_, s, gather_input ? &in0 : nullptr, out_norm_, hidden_, policy_slots_))
-            return false;
-    } else if (!decoder_stack(c_, L_, S, x_, qkv_, attn_, hmlp_, kc_, vc_, kv_layer, max_ctx_, max_splits, pos_, rope_, part_,
-                              ticket_, s, gather_input ? &in0 : nullptr, false, nullptr, fam1_)) {
-        return false;
-    }
-    // final RMSNorm (hidden_states, side output) + codec_head -> logits  (:1496-1505); batched: the stack's last
-    // resid_norm already normalised x into xn (and wrote hidden_)
-    GemvParams h;
-    h.W = codec_head_; h.N = c_.codec_vocab; h.K = H; h.B = S;
-    h.pro = PRO_RMS; h.x = x_; h.ldx = H; h.nw = out_norm_; h.eps = c_.eps; h.side_out = hidden_; h.family_b = fam1_;
-    if (mm) { h.pro = PRO_F16; h.x = xn_; h.nw = nullptr; h.side_out = nullptr; }
-    h.out_f32 = logits_; h.ldo = c_.codec_vocab;
-    if (select_next && !mm) h.sel = select_spec(SEL_CB0, gp_, 1, 0);
-    if (!gemv(h, s)) return false;
-    if (select_next && mm) return select_tokens(select_spec(SEL_CB0, gp_, 1, 0), logits_, S, s);
-    return true;
+    if (S == 1 && persist_) return talker_persist_one(s, gather_input, select_next, fold_advance);
+    if (use_tkb(S)) return talker_persist_batched(S, s, gather_input && !prenormed, select_next);
+    return talker_per_op(S, s, gather_input, select_next, prenormed);
 }
 
-// 16 passes of the 5-layer code predictor, token chosen on device each pass (trt_code_predictor.cpp:484-600).
-// Pass inputs are assembled by layer 0's QKV prologue: pass 0 the talker hidden state, pass 1 codec_embd[code 0],
-// pass p >= 2 code_pred.codec_embd[p-2][code p-1]; the raw row lands in cpx_ (the pass's residual stream).
-// logits_host (tests only, never captured): every head's logits copied out after its GEMV.
+StackCache Engine::talker_cache() const {
+    return {kc_, vc_, (size_t)max_slots_ * c_.n_kv * max_ctx_ * c_.head_dim, max_ctx_, (max_ctx_ + ATTN_CHUNK - 1) / ATTN_CHUNK, pos_, rope_, part_, ticket_};
+}
+// pass p's position is p for every slot (cp_pos_ rows); its 16 positions are one attention chunk
+StackCache Engine::cp_cache(int p) const {
+    return {cpkc_, cpvc_, (size_t)max_slots_ * cpc_.n_kv * 16 * cpc_.head_dim, 16, 1, cp_pos_ + (size_t)p * max_slots_, rope_, part_, ticket_};
+}
+
+GatherSum Engine::step_embed_gather() const {
+    GatherSum gs;
+    gs.tok = tokens_; gs.tok_ld = 16; gs.tabs = tabs16_dev_;
+    gs.tr = trailing_; gs.tr_len = trailing_len_; gs.frame = frame_;
+    gs.tr_ld = max_trailing_ * c_.hidden; gs.pad = tts_pad_;
+    return gs;
+}
+
+// the one-slot step as one persistent launch (persist.hip / persist_tk.hip)
+bool Engine::talker_persist_one(hipStream_t s, bool gather_input, bool select_next, bool *fold_advance) {
+    const StackCache kv = talker_cache();
+    PersistParams p;
+    persist_carve(pstate_, p);
+    p.L = pl_dev_; p.n_layers = c_.n_layers; p.eps = c_.eps;
+    p.gather = gather_input ? 1 : 0; p.x_in = x_; p.gs = step_embed_gather();
+    p.rope = kv.rope; p.pos = kv.pos; p.kc = kv.kc; p.vc = kv.vc; p.kv_layer = kv.kv_layer; p.n_ctx = kv.n_ctx;
+    p.head = codec_head_; p.out_norm = out_norm_; p.hidden = hidden_; p.logits = logits_;
+    if (select_next) p.sel = select_spec(SEL_CB0, gp_, 1, 0);
+    p.prof = pprof_;
+    if (tk_roles_) {
+        if (fold_advance && opt_.fold_advance) {
+            p.adv_pos = pos_; p.adv_frame = frame_; p.adv_done = done_; *fold_advance = true;
+        }
+        return persist_tk_roles(p, s);
+    }
+    return persist_talker_step(p, s);
+}
+
+// batched: the whole step as one persistent launch (persist_tkb.hip); gather: x_ does not hold the step embedding yet
+bool Engine::talker_persist_batched(int S, hipStream_t s, bool gather, bool select_next) {
+    const StackCache kv = talker_cache();
+    if (gather && !gather_sum(step_embed_gather(), 16, S, c_.hidden, x_, c_.hidden, s)) return false;
+    TkbParams p;
+    p.L = pl_dev_; p.n_layers = c_.n_layers; p.head = codec_head_; p.out_norm = out_norm_;
+    p.x_in = x_; p.hidden = hidden_; p.logits = logits_;
+    p.rope = kv.rope; p.pos = kv.pos; p.kc = kv.kc; p.vc = kv.vc; p.kv_layer = kv.kv_layer; p.n_ctx = kv.n_ctx;
+    if (select_next) { p.select = 1; p.sel = select_spec(SEL_CB0, gp_, 1, 0); }
+    p.S = S; p.eps = c_.eps; p.state = tkb_state_; p.prof = pprof_;
+    return persist_talker_batched(p, s);
+}
+
+bool Engine::talker_per_op(int S, hipStream_t s, bool gather_input, bool select_next, bool prenormed) {
+    const bool mm = use_mm(S);   // batched: one selection workgroup per slot after the head
+    StackInput in0;
+    in0.pro = PRO_RMS_G16; in0.gs = step_embed_gather(); in0.prenormed = prenormed;
+    StackRun r;
+    r.buf = talker_bufs(); r.kv = talker_cache();
+    if (gather_input) r.in0 = &in0;
+    r.family = mm ? policy_slots_ : fam1_;
+    r.final_norm = out_norm_; r.final_side = hidden_;
+    if (mm ? !decoder_stack_mm(c_, opt_, L_, S, r, s) : !decoder_stack(c_, L_, S, r, s)) return false;
+    // final RMSNorm (hidden_states, side output) + codec_head -> logits  (:1496-1505)
+    GemvParams h;
+    h.W = codec_head_; h.N = c_.codec_vocab; h.nw = out_norm_; h.side_out = hidden_; h.out_f32 = logits_; h.family_b = fam1_;
+    if (select_next) h.sel = select_spec(SEL_CB0, gp_, 1, 0);
+    if (!head_gemv(c_, h, r.buf, mm, S, s)) return false;
+    return !(select_next && mm) || select_tokens(h.sel, logits_, S, s);
+}
+
 bool Engine::cp_project(int S, const float *x_talker, int ldx, hipStream_t s) {
     GemvParams g;   // ggml_mul_mat(mtp_proj, cur) + ggml_add(bias): f16-rounded input, f32 accumulation
     g.W = mtp_; g.N = c_.cp_hidden; g.K = c_.hidden; g.B = S;
@@ -1128,138 +1135,137 @@ bool Engine::cp_project(int S, const float *x_talker, int ldx, hipStream_t s) {
     return gemv(g, s);
 }
 
+// 16 passes of the 5-layer code predictor, token chosen on device each pass (trt_code_predictor.cpp:484-600).
+// Pass inputs are assembled by layer 0's QKV prologue: pass 0 the talker hidden state, pass 1 codec_embd[code 0],
+// pass p >= 2 code_pred.codec_embd[p-2][code p-1]; the raw row lands in cpx_ (the pass's residual stream).
+// logits_host (tests only, never captured): every head's logits copied out after its GEMV.
 bool Engine::enqueue_cp_frame(int S, hipStream_t s, float *logits_host, bool talker_next) {
-    const int H = cpc_.hidden;   // code-predictor width (the talker's for 0.6B)
-    const size_t kv_layer = (size_t)max_slots_ * cpc_.n_kv * 16 * cpc_.head_dim;
-    std::vector<float> lg;
+    if (S == 1 && persist_cp_ && !logits_host) return cp_frame_persist_one(s);
+    if (use_cpb(S) && !logits_host) return cp_frame_persist_batched(S, s, talker_next);
+    return cp_frame_per_op(S, s, logits_host, talker_next);
+}
+
+// one slot: the whole frame as one persistent launch (persist.hip / persist_cp.hip)
+bool Engine::cp_frame_persist_one(hipStream_t s) {
+    const StackCache kv = cp_cache(0);
+    PersistParams p;
+    persist_carve(pstate_, p);
+    p.L = pl_cp_dev_; p.n_layers = c_.cp_layers; p.eps = c_.eps; p.x_in = hidden_;
+    if (c_.has_mtp) {   // 1.7B: pass 0's projected input by the per-op GEMV, passes 1..15 from the projected table
+        if (!cp_project(1, hidden_, c_.hidden, s)) return false;
+        p.x_in = cpx_; p.xtab = cp_projtab_;
+    }
+    p.gs.tok = tokens_; p.gs.tok_ld = 16; p.gs.tabs = tabs16_dev_;
+    p.rope = kv.rope; p.kc = kv.kc; p.vc = kv.vc; p.kv_layer = kv.kv_layer; p.n_ctx = kv.n_ctx;
+    p.heads = heads_dev_; p.out_norm = cp_out_norm_; p.logits = cp_logits_; p.qkvtab = cp_qkvtab_;
+    p.sel = select_spec(SEL_CP, gp_, 0, 0); p.prof = pprof_;
+    if (cp_roles_ && p.qkvtab) return persist_cp_roles(p, s);   // (1.7B: layer 0's residual rows from xtab)
+    return persist_cp_frame(p, s);
+}
+
+// batched: the whole frame as one persistent launch (persist_cpb.hip)
+bool Engine::cp_frame_persist_batched(int S, hipStream_t s, bool talker_next) {
+    const StackCache kv = cp_cache(0);
+    CpbParams p;
+    p.L = pl_cp_dev_; p.heads = heads_dev_; p.tabs = tabs16_dev_; p.out_norm = cp_out_norm_; p.qkvtab = cp_qkvtab_;
+    p.x_in = hidden_; p.rope = kv.rope; p.pos = kv.pos; p.pos_ld = max_slots_; p.kc = kv.kc; p.vc = kv.vc;
+    p.kv_layer = kv.kv_layer; p.logits = cp_logits_; p.sel = select_spec(SEL_CP, gp_, 0, 0); p.S = S; p.eps = c_.eps;
+    if (talker_next) {
+        const GatherSum gs = step_embed_gather();
+        p.talker_next = 1;
+        p.tx = x_; p.txn = xn_; p.tnw = L_[0].attn_norm;
+        p.tr = gs.tr; p.tr_len = gs.tr_len; p.frame = gs.frame; p.tr_ld = gs.tr_ld; p.pad = gs.pad;
+    }
+    p.state = cpb_state_; p.prof = pprof_;
+    return persist_cp_batched(p, s);
+}
+
+// pass p >= 1 starts from the table row of code p - 1: codec_embd for pass 1, code_pred.codec_embd[p - 2] after it
+GatherSum Engine::cp_input_gather(int p) const {
+    GatherSum gs;
+    gs.tok = tokens_; gs.tok_ld = 16; gs.tok_col0 = p - 1; gs.tab0 = p == 1 ? codec_embd_ : cp_embd_[p - 2];
+    return gs;
+}
+
+// pass p's input: what layer 0 reads (in0), after the launches that prepare it
+bool Engine::cp_pass_input(int p, int S, bool defer, StackInput &in0, hipStream_t s) {
+    if (c_.has_mtp) {
+        // 1.7B: the pass input (talker hidden / table row, talker space) projected into cpx_ by code_pred.mtp_proj
+        // (tts_transformer.cpp:1554-1560, :1709-1714); layer 0 then normalises cpx_ like any later layer
+        if (p > 0 && !gather_sum(cp_input_gather(p), 1, S, c_.hidden, cp_in1_, c_.hidden, s)) return false;
+        in0.pro = PRO_RMS; in0.x = cpx_;
+        return cp_project(S, p > 0 ? cp_in1_ : hidden_, c_.hidden, s);
+    }
+    if (p == 0) { in0.pro = PRO_RMS; in0.x = hidden_; return true; }
+    in0.pro = PRO_RMS_G1; in0.gs = cp_input_gather(p);
+    if (defer && p >= 2) {   // the token of head p - 2 is selected in this pass's QKV launch
+        in0.pro = PRO_SEL_G1;
+        in0.sel = select_spec(SEL_CP, gp_, 0, p - 2);
+        in0.sel_logits = cp_logits_;
+    }
+    return true;
+}
+
+// tests only, never captured: head `step`'s logits of every slot into logits_host [S][15][cp_vocab]
+bool Engine::cp_copy_logits(int S, int step, float *logits_host, hipStream_t s) {
+    std::vector<float> lg((size_t)S * c_.cp_vocab);
+    Q3T_HIP(hipMemcpyAsync(lg.data(), cp_logits_, lg.size() * 4, hipMemcpyDeviceToHost, s));
+    Q3T_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < S; ++b)
+        std::memcpy(logits_host + ((size_t)b * 15 + step) * c_.cp_vocab, lg.data() + (size_t)b * c_.cp_vocab, c_.cp_vocab * 4);
+    return true;
+}
+
+// batched: the selecting workgroup of each slot also gathers and normalises the next stage's input (the next pass's
+// table row, or the talker step embedding after the last pass)
+bool Engine::cp_select_handoff(int S, int step, hipStream_t s) {
+    const bool last = step == 14;
+    EmbedNorm en;
+    en.nt = last ? 16 : 1; en.gs = last ? step_embed_gather() : cp_input_gather(step + 2);
+    en.x = last ? x_ : cpx_; en.nw = (last ? L_ : CP_)[0].attn_norm;
+    en.xn = xn_; en.eps = c_.eps; en.H = c_.hidden;   // (mm: no projection, code predictor width == talker's)
+    return select_embed_norm(select_spec(SEL_CP, gp_, 0, step), cp_logits_, en, S, s);
+}
+
+bool Engine::cp_frame_per_op(int S, hipStream_t s, float *logits_host, bool talker_next) {
+    const bool mm = use_mm(S);
     // vector path with fused selection: heads 0..13 only produce logits; the next pass's QKV launch selects the token
     // in every workgroup while its weights stream (PRO_SEL_G1), so the head's 256 -> 1 arrival chain and the serial
     // selection leave the critical path.  Head 14 (its token feeds the next talker step) keeps the fused selection.
-    if (S == 1 && persist_cp_ && !logits_host) {   // the whole frame as one persistent launch
-        PersistParams p;
-        persist_carve(pstate_, p);
-        p.L = pl_cp_dev_; p.n_layers = c_.cp_layers; p.eps = c_.eps;
-        p.x_in = hidden_;
-        if (c_.has_mtp) {   // 1.7B: pass 0's projected input by the per-op GEMV, passes 1..15 from the projected table
-            if (!cp_project(1, hidden_, c_.hidden, s)) return false;
-            p.x_in = cpx_;
-            p.xtab = cp_projtab_;
-        }
-        p.gs.tok = tokens_; p.gs.tok_ld = 16; p.gs.tabs = tabs16_dev_;
-        p.rope = rope_; p.kc = cpkc_; p.vc = cpvc_; p.kv_layer = kv_layer; p.n_ctx = 16;
-        p.heads = heads_dev_; p.out_norm = cp_out_norm_; p.logits = cp_logits_;
-        p.qkvtab = cp_qkvtab_;
-        p.sel = select_spec(SEL_CP, gp_, 0, 0);
-        p.prof = pprof_;
-        if (cp_roles_ && p.qkvtab) return persist_cp_roles(p, s);   // (1.7B: layer 0's residual rows from xtab)
-        return persist_cp_frame(p, s);
-    }
-    if (use_cpb(S) && !logits_host) {   // batched: the whole frame as one persistent launch (persist_cpb.hip)
-        CpbParams p;
-        p.L = pl_cp_dev_; p.heads = heads_dev_; p.tabs = tabs16_dev_; p.out_norm = cp_out_norm_; p.qkvtab = cp_qkvtab_;
-        p.x_in = hidden_; p.rope = rope_; p.pos = cp_pos_; p.pos_ld = max_slots_; p.kc = cpkc_; p.vc = cpvc_;
-        p.kv_layer = kv_layer; p.logits = cp_logits_; p.sel = select_spec(SEL_CP, gp_, 0, 0); p.S = S; p.eps = c_.eps;
-        if (talker_next) {
-            p.talker_next = 1;
-            p.tx = x_; p.txn = xn_; p.tnw = L_[0].attn_norm;
-            p.tr = trailing_; p.tr_len = trailing_len_; p.frame = frame_; p.tr_ld = max_trailing_ * H; p.pad = tts_pad_;
-        }
-        p.state = cpb_state_;
-        p.prof = pprof_;
-        return persist_cp_batched(p, s);
-    }
-    const bool fsel_all = fused_select_ && !use_mm(S);
+    const bool fsel_all = fused_select_ && !mm;
     // deferred selection gathers the next pass's table row inside its QKV launch: not with a projected input (1.7B)
     const bool defer = fsel_all && defer_cp_select_ && !c_.has_mtp;
     bool next_prenormed = false;   // batched: this pass's input was prepared by the previous selection launch
     for (int p = 0; p < 16; ++p) {
         StackInput in0;
-        in0.prenormed = next_prenormed;
-        next_prenormed = false;
-        if (c_.has_mtp) {
-            // 1.7B: the pass input (talker hidden / table row, talker space) projected into cpx_ by code_pred.mtp_proj
-            // (tts_transformer.cpp:1554-1560, :1709-1714); layer 0 then normalises cpx_ like any later layer
-            const float *src = hidden_;
-            if (p > 0) {
-                GatherSum gs;
-                gs.tok = tokens_; gs.tok_ld = 16; gs.tok_col0 = p - 1;
-                gs.tab0 = p == 1 ? codec_embd_ : cp_embd_[p - 2];
-                if (!gather_sum(gs, 1, S, c_.hidden, cp_in1_, c_.hidden, s)) return false;
-                src = cp_in1_;
-            }
-            if (!cp_project(S, src, c_.hidden, s)) return false;
-            in0.pro = PRO_RMS; in0.x = cpx_;
-        } else if (p == 0) {
-            in0.pro = PRO_RMS; in0.x = hidden_;
-        } else {
-            in0.pro = PRO_RMS_G1;
-            in0.gs.tok = tokens_; in0.gs.tok_ld = 16; in0.gs.tok_col0 = p - 1;
-            in0.gs.tab0 = p == 1 ? codec_embd_ : cp_embd_[p - 2];
-            if (defer && p >= 2) {
-                in0.pro = PRO_SEL_G1;
-                in0.sel = select_spec(SEL_CP, gp_, 0, p - 2);
-                in0.sel_logits = cp_logits_;
-            }
+        in0.prenormed = next_prenormed; next_prenormed = false;
+        if (!cp_pass_input(p, S, defer, in0, s)) return false;
+        // passes 1..15 of the matrix-core stack: layer 0's raw QKV rows from the per-token table (the 0.6B layout; the
+        // table's rows are the 1-slot GEMV's, within the batched family's f32 tolerance of its MFMA GEMM)
+        StackRun r;
+        if (opt_.mm_cp_table && p >= 1 && cp_qkvtab_ && !c_.has_mtp) {
+            r.l0tab.qkv_tab = cp_qkvtab_; r.l0tab.tab_tok = tokens_; r.l0tab.tab_ld = 16; r.l0tab.tab_col = p - 1;
+            r.l0tab.tab_row0 = cp_table_row0(p);
         }
-        const bool mm = use_mm(S);
-        if (mm) {
-            // passes 1..15: layer 0's raw QKV rows from the per-token table (the 0.6B layout; the table's rows are the
-            // 1-slot GEMV's, within the batched family's f32 tolerance of its MFMA GEMM)
-            AttnParams l0;
-            if (p >= 1 && cp_qkvtab_ && !c_.has_mtp) {
-                l0.qkv_tab = cp_qkvtab_; l0.tab_tok = tokens_; l0.tab_ld = 16; l0.tab_col = p - 1;
-                l0.tab_row0 = p == 1 ? 0 : (size_t)c_.codec_vocab + (size_t)(p - 2) * c_.cp_vocab;
-            }
-            if (!decoder_stack_mm(cpc_, opt_.attn_split, CP_, S, cpx_, xn_, parts_, qkv_, attn_, hmlp_, cpkc_, cpvc_, kv_layer, 16, 1,
-                                  cp_pos_ + (size_t)p * max_slots_, rope_, part_, ticket_, s, &in0,
-                                  p == 0 ? nullptr : cp_out_norm_, nullptr, policy_slots_, true, nullptr,
-                                  opt_.mm_cp_table ? &l0 : nullptr))
-                return false;
-        } else if (!decoder_stack(cpc_, CP_, S, cpx_, qkv_, attn_, hmlp_, cpkc_, cpvc_, kv_layer, 16, 1,
-                                  cp_pos_ + (size_t)p * max_slots_, rope_, part_, ticket_, s, c_.has_mtp ? nullptr : &in0,
-                                  cp_fused_attn_, nullptr, fam1_)) {
-            return false;
-        }
+        r.buf = cp_bufs(); r.kv = cp_cache(p);
+        if (mm || !c_.has_mtp) r.in0 = &in0;   // (vector stack, 1.7B: layer 0 reads cpx_ like any later layer)
+        r.family = mm ? policy_slots_ : fam1_; r.cp_attn = true; r.fused_cp_attn = cp_fused_attn_;
+        r.final_norm = p == 0 ? nullptr : cp_out_norm_;
+        if (mm ? !decoder_stack_mm(cpc_, opt_, CP_, S, r, s) : !decoder_stack(cpc_, CP_, S, r, s)) return false;
         if (p == 0) continue;
         const int step = p - 1;
-        GemvParams h;
-        h.W = cp_head_[step]; h.N = c_.cp_vocab; h.K = H; h.B = S;
-        h.pro = PRO_RMS; h.x = cpx_; h.ldx = H; h.nw = cp_out_norm_; h.eps = c_.eps; h.family_b = fam1_;
-        if (mm) { h.pro = PRO_F16; h.x = xn_; h.nw = nullptr; }
-        h.out_f32 = cp_logits_; h.ldo = c_.cp_vocab;
         const bool fsel = fsel_all && (!defer || step == 14);
+        GemvParams h;
+        h.W = cp_head_[step]; h.N = c_.cp_vocab; h.nw = cp_out_norm_; h.out_f32 = cp_logits_; h.family_b = fam1_;
         if (fsel) h.sel = select_spec(SEL_CP, gp_, 0, step);
-        if (!gemv(h, s)) return false;
-        if (logits_host) {
-            lg.resize((size_t)S * c_.cp_vocab);
-            Q3T_HIP(hipMemcpyAsync(lg.data(), cp_logits_, lg.size() * 4, hipMemcpyDeviceToHost, s));
-            Q3T_HIP(hipStreamSynchronize(s));
-            for (int b = 0; b < S; ++b)
-                std::memcpy(logits_host + ((size_t)b * 15 + step) * c_.cp_vocab, lg.data() + (size_t)b * c_.cp_vocab, c_.cp_vocab * 4);
-        }
-#ifdef Q3T_NO_SELFUSE
-        if (false) {
-#else
+        if (!head_gemv(cpc_, h, r.buf, mm, S, s)) return false;
+        if (logits_host && !cp_copy_logits(S, step, logits_host, s)) return false;
         if (mm && (step < 14 || talker_next)) {
-#endif
-            // batched: the selecting workgroup of each slot also gathers and normalises the next stage's input (the
-            // next pass's table row, or the talker step embedding after the last pass)
-            EmbedNorm en;
-            en.gs.tok = tokens_; en.gs.tok_ld = 16;
-            if (step < 14) {
-                en.nt = 1; en.gs.tok_col0 = step + 1; en.gs.tab0 = cp_embd_[step];
-                en.x = cpx_; en.nw = CP_[0].attn_norm;
-            } else {
-                en.nt = 16; en.gs.tabs = tabs16_dev_; en.gs.tr = trailing_; en.gs.tr_len = trailing_len_;
-                en.gs.frame = frame_; en.gs.tr_ld = max_trailing_ * H; en.gs.pad = tts_pad_;
-                en.x = x_; en.nw = L_[0].attn_norm;
-            }
-            en.xn = xn_; en.eps = c_.eps; en.H = c_.hidden;   // (mm: no projection, code predictor width == talker's)
-            if (!select_embed_norm(select_spec(SEL_CP, gp_, 0, step), cp_logits_, en, S, s)) return false;
+            if (!cp_select_handoff(S, step, s)) return false;
             next_prenormed = true;
-            continue;
+        } else if (!fsel && !(defer && step < 14)) {
+            if (!select_tokens(select_spec(SEL_CP, gp_, 0, step), cp_logits_, S, s)) return false;
         }
-        if (!fsel && !(defer && step < 14) && !select_tokens(select_spec(SEL_CP, gp_, 0, step), cp_logits_, S, s)) return false;
     }
     return true;
 }
@@ -1269,11 +1275,7 @@ bool Engine::enqueue_cp_frame(int S, hipStream_t s, float *logits_host, bool tal
 bool Engine::enqueue_frame(int S, hipStream_t s) {
     if (!fused_select_ && !select_tokens(select_spec(SEL_CB0, gp_, 0, 0), logits_, S, s)) return false;
     // batched: the last code-predictor selection also assembles and normalises the talker step's input
-#ifdef Q3T_NO_SELFUSE
-    const bool mm = false;
-#else
     const bool mm = use_mm(S);
-#endif
     if (!enqueue_cp_frame(S, s, nullptr, mm)) return false;
     bool folded = false;   // the single-slot role kernel advances pos / frame itself
     if (!enqueue_talker(S, s, true, fused_select_, mm, &folded)) return false;
@@ -1345,26 +1347,19 @@ bool Engine::ensure_prefill() {
 // the captured body: key = (S_main * 1024 + n_utt) * 16 + plen
 bool Engine::enqueue_prefill_rows(int key, hipStream_t s) {
     const int plen = key % 16, n_utt = key / 16 % 1024, S_main = key / (16 * 1024);
-    const int rows = n_utt * plen, H = c_.hidden, V = c_.codec_vocab;
-    const size_t kv_layer = (size_t)max_slots_ * c_.n_kv * max_ctx_ * c_.head_dim;
-    const int max_splits = (max_ctx_ + ATTN_CHUNK - 1) / ATTN_CHUNK;
+    const int rows = n_utt * plen;
+    const bool mm = use_mm(S_main);
     PrefillAttnParams pf;
     pf.slot = pf_slot_; pf.n_utt = n_utt; pf.plen = plen;
+    StackRun r;
+    r.buf = prefill_bufs(); r.kv = talker_cache();
+    r.family = S_main; r.pf = &pf;
+    r.final_norm = out_norm_; r.final_side = pf_hid_;
+    if (mm ? !decoder_stack_mm(c_, opt_, L_, rows, r, s) : !decoder_stack(c_, L_, rows, r, s)) return false;
     GemvParams h;   // final RMSNorm (hidden side output) + codec head over every row, as the S_main-slot step
-    h.W = codec_head_; h.N = V; h.K = H; h.B = rows; h.out_f32 = pf_logits_; h.ldo = V;
-    if (use_mm(S_main)) {
-        if (!decoder_stack_mm(c_, opt_.attn_split, L_, rows, pf_x_, pf_xn_, pf_parts_, pf_qkv_, pf_attn_, pf_hmlp_, kc_, vc_,
-                              kv_layer, max_ctx_, max_splits, pos_, rope_, part_, ticket_, s, nullptr, out_norm_, pf_hid_,
-                              S_main, false, &pf))
-            return false;
-        h.pro = PRO_F16; h.x = pf_xn_; h.ldx = H; h.force_mm = true;
-        return gemv(h, s);
-    }
-    if (!decoder_stack(c_, L_, rows, pf_x_, pf_qkv_, pf_attn_, pf_hmlp_, kc_, vc_, kv_layer, max_ctx_, max_splits, pos_, rope_,
-                       part_, ticket_, s, nullptr, false, &pf, S_main))
-        return false;
-    h.pro = PRO_RMS; h.x = pf_x_; h.ldx = H; h.nw = out_norm_; h.eps = c_.eps; h.side_out = pf_hid_; h.family_b = S_main;
-    return gemv(h, s);
+    h.W = codec_head_; h.N = c_.codec_vocab; h.nw = out_norm_; h.side_out = pf_hid_; h.out_f32 = pf_logits_;
+    h.family_b = S_main; h.force_mm = mm;
+    return head_gemv(c_, h, r.buf, mm, rows, s);
 }
 
 // src: [n_utt][10][H] prompt rows (rows [0, plen) of each used); pf_slot_[0, n_utt) must hold the target slots

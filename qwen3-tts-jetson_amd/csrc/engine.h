@@ -79,6 +79,8 @@ struct PromptEntry {
 //   Q3T_FUSED_SELECT=0     token selection as standalone launches
 //   Q3T_CP_DEFER_SELECT=0  code-predictor tokens selected in the head launch
 //   Q3T_ATTN_SPLIT=1       batched attention always split-K (k_attn) instead of k_attn_seq at >= 16 slots
+//   Q3T_MM_PREFETCH=1|2    batched talker stack: weight prefetch from the norms (1) and also the gate/up GEMM (2)
+//   Q3T_MM_GU_TT=1         batched stacks: gate/up GEMM on 32-token tiles instead of 64
 //   Q3T_PERSIST_FAULT_AT=n test hook: the n-th persistent launch of the context flags a hand-off fault
 // Development-only knobs (Q3T_TALKER_LAYERS, Q3T_PERSIST_PROF, ...) exist only in a -DQ3T_DEV build.
 struct Options {
@@ -91,9 +93,26 @@ struct Options {
     bool cpb = true;            // Q3T_PERSIST_CPB: the batched (2..64-slot) code-predictor frame as one persistent launch
     bool tkb = true;            // Q3T_PERSIST_TKB: the batched (16..64-policy-slot) talker step as one persistent launch
     bool attn_split = false;
+    int mm_prefetch = 0;        // Q3T_MM_PREFETCH (from_env)
+    int mm_gu_tt = 2;           // Q3T_MM_GU_TT: gate/up token tile in 32-token units (from_env)
     unsigned persist_fault_at = 0;
     int poll_every = 16;   // frames between done-flag polls
     static Options from_env();
+};
+
+// what one run of a launch-per-op decoder stack (engine.cpp: decoder_stack / decoder_stack_mm) computes in, and the
+// cache it attends over
+struct StackBufs {
+    float *x, *parts, *qkv;       // residual stream, split-K partial slabs (matrix-core path), raw QKV rows
+    uint16_t *xn, *attn, *hmlp;   // normalised rows (matrix-core path), attention output, SwiGLU output
+};
+struct StackCache {
+    uint16_t *kc, *vc;
+    size_t kv_layer;              // elements of one layer's cache
+    int n_ctx, max_splits;
+    const int *pos;               // [S] position of each slot's new token
+    const float *rope;
+    float *part; unsigned *ticket;   // split attention: partials and arrival counters
 };
 
 class Engine {
@@ -212,8 +231,28 @@ private:
     bool enqueue_talker_step(int S, hipStream_t s);
     bool enqueue_talker(int S, hipStream_t s, bool gather_input, bool select_next, bool prenormed = false,
                         bool *fold_advance = nullptr);
+    bool talker_persist_one(hipStream_t s, bool gather_input, bool select_next, bool *fold_advance);
+    bool talker_persist_batched(int S, hipStream_t s, bool gather, bool select_next);
+    bool talker_per_op(int S, hipStream_t s, bool gather_input, bool select_next, bool prenormed);
     SelectSpec select_spec(int mode, const GenParams &gp, int frame_offset, int step) const;
     bool enqueue_cp_frame(int S, hipStream_t s, float *logits_host = nullptr, bool talker_next = false);
+    bool cp_frame_persist_one(hipStream_t s);
+    bool cp_frame_persist_batched(int S, hipStream_t s, bool talker_next);
+    bool cp_frame_per_op(int S, hipStream_t s, float *logits_host, bool talker_next);
+    // the pieces of one launch-per-op code-predictor pass around its stack and head
+    bool cp_pass_input(int p, int S, bool defer, struct StackInput &in0, hipStream_t s);
+    bool cp_copy_logits(int S, int step, float *logits_host, hipStream_t s);
+    bool cp_select_handoff(int S, int step, hipStream_t s);
+    // the three activation sets of the launch-per-op stacks, and the caches of the talker / code-predictor pass p
+    StackBufs talker_bufs() const { return {x_, parts_, qkv_, xn_, attn_, hmlp_}; }
+    StackBufs cp_bufs() const { return {cpx_, parts_, qkv_, xn_, attn_, hmlp_}; }
+    StackBufs prefill_bufs() const { return {pf_x_, pf_parts_, pf_qkv_, pf_xn_, pf_attn_, pf_hmlp_}; }
+    StackCache talker_cache() const;
+    StackCache cp_cache(int p) const;
+    GatherSum step_embed_gather() const;     // the talker step embedding of the frame's 16 codes
+    GatherSum cp_input_gather(int p) const;   // code-predictor pass p >= 1: the table row of code p - 1
+    // that table's first row in cp_qkvtab_ / cp_projtab_
+    size_t cp_table_row0(int p) const { return p == 1 ? 0 : (size_t)c_.codec_vocab + (size_t)(p - 2) * c_.cp_vocab; }
     bool enqueue_frame(int S, hipStream_t s);
     bool enqueue_text_projection(int n_rows, hipStream_t s, const PromptScratch &ps);
     // the prompt rows (PromptScratch::rows), trailing-text rows and pad row of every entry, assembled on stream s;

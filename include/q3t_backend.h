@@ -192,6 +192,24 @@ int32_t q3t_vocoder_stream_frames(const q3t_voc_stream *s);  /* pushed so far */
 int32_t q3t_vocoder_stream_halo(const q3t_voc_stream *s);    /* frames of left context the convolution stack re-runs */
 void q3t_vocoder_stream_close(q3t_voc_stream *s);
 
+/* One push on each of n_streams streams through shared launches, for batched serving.  All streams belong to one
+ * context; they may stand at any positions and take any mix of n_frames.  codes[j]: [n_frames[j]][16]; pcm[j]: capacity
+ * pcm_cap[j] samples; n_samples[j] receives stream j's count.  Stream j's PCM is bit-identical to pushing it alone with
+ * q3t_vocoder_stream_push, so the concatenation over its pushes, batched or single in any mix, is still
+ * q3t_vocoder_decode(all frames, Q3T_VOCODER_FULL).  The frame-rate part runs once over the new frames of all streams
+ * (the attention and the cache append serve every stream's cache in one launch each per layer); the convolution
+ * stack runs once per group of streams with equal n_frames and equal carried history (min(frames, halo)), so streams
+ * in the steady state that push the same number of frames share every launch.  q3t_vocoder_stream_last_groups
+ * returns the number of such groups (convolution-stack launch sequences) of the context's last batched push, -1 on a
+ * null context.  The call takes the device lock a push takes and synchronises once.
+ * Q3T_ERR with a message, EVERY stream's state unchanged and every n_samples[j] = 0: n_streams <= 0, a null array or
+ * entry, a stream that is not open on the first stream's context, a stream given twice, and for any stream
+ * n_frames <= 0, more than max_frames frames in total, or pcm_cap smaller than the push's sample count. */
+int q3t_vocoder_stream_push_batch(q3t_voc_stream *const *streams, int32_t n_streams,
+                                  const int32_t *const *codes, const int32_t *n_frames,
+                                  float *const *pcm, const int64_t *pcm_cap, int64_t *n_samples);
+int32_t q3t_vocoder_stream_last_groups(const q3t_ctx *ctx);
+
 /* ---- speaker encoder (ECAPA-TDNN; the TTS GGUF's spk_enc.* tensors)
  * q3t_speaker_dim: embedding length, 0 when the model has no speaker encoder.
  * q3t_speaker_encode: AudioTokenizerEncoder::encode (src/audio_tokenizer_encoder.h:107-108): samples in [-1, 1] at

@@ -10,7 +10,8 @@
 //   --seed <n>           sampling seed (the counter-based sampler is reproducible per seed)
 //   --vocoder-chunk <n>  0 = whole-utterance vocoder; n > 0 = n-frame chunks streamed during generation
 //   --stream-full <n>    whole-utterance vocoder PCM produced during generation: every n frames pushed into a
-//                        vocoder stream (same WAV as without the flag; ignored with a chunked vocoder)
+//                        vocoder stream (same WAV as without the flag; ignored with a chunked vocoder).  With
+//                        --serve --batch: one stream per request, every interval's frames pushed as one batch
 //   --batch <n>          --serve decodes up to n queued requests together on the GPU (lock-step slots): requests
 //                        already waiting on stdin when one is read are batched; replies keep request order
 #include <poll.h>
@@ -45,6 +46,7 @@ void print_usage(const char *program) {
     fprintf(stderr, "  --seed <n>             Sampling seed (default: 0)\n");
     fprintf(stderr, "  --vocoder-chunk <n>    Vocoder chunk frames, 0 = whole utterance (default: model dir)\n");
     fprintf(stderr, "  --stream-full <n>      Decode every n generated frames with the streaming whole-utterance vocoder\n");
+    fprintf(stderr, "                         (with --serve --batch: the requests of a batch in shared launches)\n");
     fprintf(stderr, "  --batch <n>            Server mode: decode up to n queued requests together (default: 1)\n");
     fprintf(stderr, "  -h, --help             Show this help\n");
     fprintf(stderr, "\n");

@@ -150,6 +150,76 @@ int full_stream_cb(void *user, int32_t /*utt*/, const int32_t *codes, int32_t n_
     return 1;
 }
 
+// --stream-full for a batch: one vocoder stream per utterance.  The engine delivers the slots of one interval in
+// increasing utterance order, so the deliveries are collected (the codes copied: the chunk is pinned memory that is
+// reused) until the utterance index stops increasing, and pushed as ONE q3t_vocoder_stream_push_batch.
+struct BatchStreamState {
+    q3t_ctx *ctx = nullptr;
+    std::vector<q3t_voc_stream *> voc;       // per utterance
+    std::vector<tts_result> *out = nullptr;  // per utterance: audio appended in order
+    struct Piece { int32_t utt = 0, n = 0; std::vector<int32_t> codes; };
+    std::vector<Piece> pending;
+    int64_t decode_ms = 0;
+    bool error = false;
+    std::string error_msg;
+
+    ~BatchStreamState() {
+        for (q3t_voc_stream *v : voc) if (v) q3t_vocoder_stream_close(v);
+    }
+    bool fail(const std::string &m) {
+        error = true;
+        error_msg = m;
+        pending.clear();
+        return false;
+    }
+    // push the collected deliveries; on an error no stream has moved and no audio is kept from this call
+    bool flush() {
+        if (error) return false;
+        if (pending.empty()) return true;
+        const int64_t t0 = now_ms();
+        const size_t k = pending.size();
+        std::vector<q3t_voc_stream *> st(k);
+        std::vector<const int32_t *> cp(k);
+        std::vector<int32_t> nf(k);
+        std::vector<float *> pp(k);
+        std::vector<int64_t> cap(k), got(k, 0);
+        std::vector<size_t> at(k);
+        for (size_t j = 0; j < k; ++j) {
+            const Piece &q = pending[j];
+            st[j] = voc[q.utt];
+            cp[j] = q.codes.data();
+            nf[j] = q.n;
+            const int64_t total = q3t_vocoder_num_samples(ctx, q3t_vocoder_stream_frames(st[j]) + q.n, Q3T_VOCODER_FULL);
+            cap[j] = total - q3t_vocoder_stream_samples(st[j]);
+            if (total < 0 || cap[j] < 0) return fail("bad sample count of a vocoder stream");
+            std::vector<float> &a = (*out)[q.utt].audio;
+            at[j] = a.size();
+            a.resize(at[j] + (size_t)cap[j]);
+            pp[j] = a.data() + at[j];   // one piece per utterance and flush: no later resize moves it
+        }
+        const int rc = q3t_vocoder_stream_push_batch(st.data(), (int32_t)k, cp.data(), nf.data(), pp.data(), cap.data(), got.data());
+        for (size_t j = 0; j < k; ++j) (*out)[pending[j].utt].audio.resize(at[j] + (size_t)(rc == Q3T_OK ? got[j] : 0));
+        if (rc != Q3T_OK) return fail(q3t_error());
+        pending.clear();
+        decode_ms += now_ms() - t0;
+        return true;
+    }
+};
+
+int batch_full_stream_cb(void *user, int32_t utt, const int32_t *codes, int32_t n_frames, int32_t n_cb) {
+    auto *s = static_cast<BatchStreamState *>(user);
+    if (s->error) return 0;
+    if (n_frames <= 0) return 1;
+    if (utt < 0 || utt >= (int32_t)s->voc.size() || n_cb != 16) { s->fail("unexpected delivery from the generate"); return 0; }
+    if (!s->pending.empty() && utt <= s->pending.back().utt && !s->flush()) return 0;   // a new interval begins
+    BatchStreamState::Piece q;
+    q.utt = utt;
+    q.n = n_frames;
+    q.codes.assign(codes, codes + (size_t)n_frames * 16);
+    s->pending.push_back(std::move(q));
+    return 1;
+}
+
 }  // namespace
 
 // ===================================================================================================== Qwen3TTS
@@ -426,14 +496,43 @@ std::vector<tts_result> Qwen3TTS::synthesize_batch(const std::vector<std::string
     p.top_k = params.top_k;
     p.seed = seed_;
     std::vector<int32_t> codes((size_t)n * max_len * 16);
+    // --stream-full: one vocoder stream per utterance, the deliveries of an interval pushed as one batch while the
+    // generation runs; the audio is the whole-utterance FULL decode's, sample for sample
+    const bool stream_full = stream_full_ > 0 && vocoder_chunk_ <= 0;
+    BatchStreamState bs;   // closes its streams on every path
+    if (stream_full) {
+        bs.ctx = ctx_;
+        bs.out = &out;
+        bs.voc.assign(n, nullptr);
+        for (int32_t i = 0; i < n; ++i)
+            if (q3t_vocoder_stream_open(ctx_, max_len, &bs.voc[i]) != Q3T_OK)
+                return fail_all("Failed to open the vocoder stream: " + q3t_error());
+    }
     const int64_t tg = now_ms();
-    if (q3t_generate(ctx_, n, tp.data(), nt.data(), spk.data(), &p, codes.data(), nf.data()) != Q3T_OK)
+    const int rc_gen = stream_full
+        ? q3t_generate_stream(ctx_, n, tp.data(), nt.data(), spk.data(), &p, codes.data(), nf.data(), batch_full_stream_cb,
+                              &bs, stream_full_)
+        : q3t_generate(ctx_, n, tp.data(), nt.data(), spk.data(), &p, codes.data(), nf.data());
+    if (rc_gen != Q3T_OK) {
+        for (auto &r : out) r.audio.clear();
         return fail_all("Failed to generate speech codes: " + q3t_error());
-    const int64_t gen_ms = now_ms() - tg;
+    }
+    if (stream_full) bs.flush();   // the remainders
+    const int64_t gen_ms = now_ms() - tg - bs.decode_ms;
     for (int32_t i = 0; i < n; ++i) {
         tts_result &r = out[i];
         r.t_generate_ms = gen_ms;
-        if (nf[i] == 0) { r.error_msg = "No speech codes generated"; continue; }
+        if (nf[i] == 0) { r.error_msg = "No speech codes generated"; r.audio.clear(); continue; }
+        if (stream_full) {
+            if (!bs.error && q3t_vocoder_stream_frames(bs.voc[i]) != nf[i])
+                bs.fail("the callback saw " + std::to_string(q3t_vocoder_stream_frames(bs.voc[i])) + " of " +
+                        std::to_string(nf[i]) + " generated frames");
+            if (bs.error) { r.error_msg = "Vocoder stream decode failed: " + bs.error_msg; r.audio.clear(); continue; }
+            r.t_decode_ms = bs.decode_ms;
+            r.sample_rate = kSampleRate;
+            r.success = true;
+            continue;
+        }
         const int32_t *c = codes.data() + (size_t)i * max_len * 16;
         const int64_t td = now_ms();
         int64_t got = 0;

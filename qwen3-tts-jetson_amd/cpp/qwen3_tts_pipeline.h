@@ -67,7 +67,9 @@ public:
     int32_t vocoder_chunk() const { return vocoder_chunk_; }
     // n > 0 (and no chunked vocoder): synthesize() generates through the frame callback every n frames and pushes
     // each delivery into a vocoder stream (q3t_vocoder_stream_*): the whole-utterance vocoder's PCM, bit for bit,
-    // produced while the frames are generated.  0 (default): whole-utterance vocoder after generation
+    // produced while the frames are generated.  synthesize_batch() does the same with one stream per utterance, the
+    // deliveries of one interval pushed together (q3t_vocoder_stream_push_batch).  0 (default): whole-utterance
+    // vocoder after generation
     void set_stream_full(int32_t interval) { stream_full_ = interval; }
     int32_t stream_full() const { return stream_full_; }
     // n utterances decoded together on one GPU (lock-step slots); speaker_embeddings empty or one per text (an empty

@@ -358,6 +358,28 @@ int q3t_vocoder_stream_push(q3t_voc_stream *s, const int32_t *codes, int32_t n_f
     GUARD_END
 }
 
+int q3t_vocoder_stream_push_batch(q3t_voc_stream *const *streams, int32_t n_streams, const int32_t *const *codes,
+                                  const int32_t *n_frames, float *const *pcm, const int64_t *pcm_cap, int64_t *n_samples) {
+    GUARD_BEGIN
+    if (n_samples) for (int32_t j = 0; j < n_streams; ++j) n_samples[j] = 0;
+    if (n_streams <= 0) { q3t::set_error("vocoder stream batch: n_streams must be > 0"); return Q3T_ERR; }
+    if (!streams || !codes || !n_frames || !pcm || !pcm_cap || !n_samples) { q3t::set_error("null argument"); return Q3T_ERR; }
+    for (int32_t j = 0; j < n_streams; ++j)
+        if (!streams[j]) { q3t::set_error("null vocoder stream (entry " + std::to_string(j) + ")"); return Q3T_ERR; }
+    // the first stream names the context; the decoder checks that every stream is an open one of its own
+    q3t::Vocoder::Stream *first = vst(streams[0]);
+    q3t::DeviceLock lk(false, first->device);   // never beside a persistent grid (devlock.h)
+    return first->owner->stream_push_batch(n_streams, reinterpret_cast<q3t::Vocoder::Stream *const *>(streams), codes, n_frames,
+                                           pcm, pcm_cap, n_samples) ? Q3T_OK : Q3T_ERR;
+    GUARD_END
+}
+
+int32_t q3t_vocoder_stream_last_groups(const q3t_ctx *ctx) {
+    if (!ctx) return -1;
+    const q3t::Vocoder *v = const_cast<q3t::Engine &>(ctx->engine).vocoder();
+    return v ? v->stream_last_groups() : -1;
+}
+
 int64_t q3t_vocoder_stream_samples(const q3t_voc_stream *s) { return s ? cvst(s)->samples : -1; }
 int32_t q3t_vocoder_stream_frames(const q3t_voc_stream *s) { return s ? cvst(s)->frames : -1; }
 int32_t q3t_vocoder_stream_halo(const q3t_voc_stream *s) { return s ? cvst(s)->halo : -1; }

@@ -14,6 +14,8 @@ Vocoder::~Vocoder() {
     while (!streams_.empty()) stream_close(streams_.back());
     for (void *p : allocs_) hipFree(p);
     for (void *p : scratch_) hipFree(p);
+    if (sb_win_) hipFree(sb_win_);
+    if (sb_desc_) hipFree(sb_desc_);
 }
 
 template <class T>
@@ -308,7 +310,8 @@ int64_t Vocoder::n_samples(int n_frames, int mode) const {
 
 // scratch for nb utterances of F frames: sized by the totals (largest activation x nb, frames x nb), so a batch of
 // short utterances reuses the scratch of one long one
-bool Vocoder::ensure(int F, int nb) {
+// rows: packed frame rows of a row-wise pass that belong to no single sequence (a batched stream push)
+bool Vocoder::ensure(int F, int nb, size_t rows) {
     size_t big = 0;   // largest [T][C] activation of one utterance over the stages
     int64_t T = F;
     big = std::max(big, (size_t)F * std::max(latent_, 3 * latent_));
@@ -320,7 +323,9 @@ bool Vocoder::ensure(int F, int nb) {
         big = std::max(big, (size_t)T * dec_[d].ct.oc);
     }
     big *= (size_t)nb;
-    const size_t frames = (size_t)F * nb;
+    // per packed row: qkv, an RVQ row, or the attention output and the FFN's hidden row in f16
+    big = std::max(big, rows * (size_t)std::max({3 * latent_, hidden_, (latent_ + ffn_ + 1) / 2}));
+    const size_t frames = std::max((size_t)F * nb, rows);
     const size_t pcm = (size_t)nb * std::max<int64_t>(full_len(F), (int64_t)F * 1920);
     if (big <= cap_big_ && frames <= cap_ftot_ && pcm <= cap_pcm_ && F <= cap_frames_) return true;
     big = std::max(big, cap_big_);
@@ -481,18 +486,11 @@ bool Vocoder::decode_rows(const int32_t *codes_dev, int F, float *pcm_dev, int64
     return frame_rows(codes_dev, F, s, nullptr) && conv_stack(F, pcm_dev, n_out, s);
 }
 
-// Frame-rate half.  st null: the whole utterances of a one-shot decode.  st set (nb_ = 1): the F new frames of a stream
-// at positions P..P+F-1 -- pre_conv sees the RVQ rows of the previous two frames in front of the new ones, the
-// attention runs against the stream's K/V caches, and output_proj's rows land after the stream's halo rows in buf_[1],
-// which then holds the window the convolution stack runs on.  Every launch is the one-shot path's on fewer rows.
-bool Vocoder::frame_rows(const int32_t *codes_dev, int F, hipStream_t s, Stream *st) {
-    const int VH = hidden_, LAT = latent_;
-    const int FR = F * nb_;   // frame rows of the batch
-    float *A = buf_[0], *B = buf_[1], *C = buf_[2];
-    const int P = st ? st->frames : 0;
-    const int tail = st ? std::min(2, P) : 0;            // carried RVQ rows in front of the new ones
-    const int hrows = st ? std::min(st->halo, P) : 0;    // carried output_proj rows in front of the new ones
-    // 1) RVQ: latent = W_first . cb_first[c0] + sum_k W_rest . cb_rest_k[c_{k+1}]   (:650-703)
+// RVQ of FR packed frame rows: latent = W_first . cb_first[c0] + sum_k W_rest . cb_rest_k[c_{k+1}]   (:650-703) -> out
+// [FR][hidden]; buf_[1] holds the running sum (out may be any other buffer)
+bool Vocoder::rvq_rows(const int32_t *codes_dev, int FR, float *out, hipStream_t s) {
+    const int VH = hidden_;
+    float *B = buf_[1];
     if (!codes_cols(codes_dev, cols_, FR, 16, s)) return false;
     GemvParams g = row_gemv();
     g.N = VH; g.K = cb_dim_; g.B = FR; g.pro = PRO_F16; g.ldx = cb_dim_; g.ldo = VH;
@@ -502,19 +500,20 @@ bool Vocoder::frame_rows(const int32_t *codes_dev, int F, hipStream_t s, Stream 
         if (!gemv(g, s)) return false;
     }
     g.W = vq_first_out_; g.x = cb_first_; g.x_idx = cols_; g.resid = nullptr; g.aux = B; g.lda = VH;
-    g.out_f32 = A + (size_t)tail * VH;
-    if (!gemv(g, s)) return false;
-    if (st) {
-        if (tail) Q3T_HIP(hipMemcpyAsync(A, st->rvq_tail, (size_t)tail * VH * 4, hipMemcpyDeviceToDevice, s));
-        const int keep = std::min(2, P + F);   // the next push's tail: the last rows of [tail + F]
-        Q3T_HIP(hipMemcpyAsync(st->rvq_tail, A + (size_t)(tail + F - keep) * VH, (size_t)keep * VH * 4,
-                               hipMemcpyDeviceToDevice, s));
-    }
-    // 2) causal pre-conv k3 (left pad 2) -> [F][LAT]   (:705-718)
-    if (!run_conv(pre_conv_, A, tail + F, 2, 1, nullptr, C, nullptr, 0, s)) return false;
+    g.out_f32 = out;
+    return gemv(g, s);
+}
+
+// input_proj .. output_proj of FR packed frame rows: pre [FR][latent] (pre_conv's rows) -> out [FR][latent].  x lives
+// in buf_[0], qkv in buf_[1], the attention output and the FFN's hidden rows in buf_[2]; attn(layer, qkv, att) runs the
+// layer's attention (RoPE included) from qkv [FR][3*latent] into att [FR][latent] f16.  out may be in buf_[1] or buf_[2]
+bool Vocoder::layer_rows(const float *pre, int FR, float *out, hipStream_t s,
+                         const std::function<bool(int, float *, uint16_t *)> &attn) {
+    const int VH = hidden_, LAT = latent_;
+    float *A = buf_[0], *B = buf_[1], *C = buf_[2];
     // 3) input_proj + bias -> x [F][VH]
     GemvParams ip = row_gemv();
-    ip.W = in_proj_; ip.N = VH; ip.K = LAT; ip.B = FR; ip.pro = PRO_F32; ip.x = C + (size_t)tail * LAT; ip.ldx = LAT;
+    ip.W = in_proj_; ip.N = VH; ip.K = LAT; ip.B = FR; ip.pro = PRO_F32; ip.x = pre; ip.ldx = LAT;
     ip.bias = in_proj_b_; ip.out_f32 = A; ip.ldo = VH;
     if (!gemv(ip, s)) return false;
     float *x = A;
@@ -538,12 +537,7 @@ bool Vocoder::frame_rows(const int32_t *codes_dev, int F, hipStream_t s, Stream 
             q.eps = 1e-5f; q.out_f32 = qkv; q.ldo = 3 * LAT;
             if (!gemv(q, s)) return false;
         }
-        if (st) {
-            const size_t lo = (size_t)(&L - layers_.data()) * st->max_frames * LAT;   // this layer's cache
-            if (!voc_kv_append(qkv, st->rope, st->kc + lo, st->vc + lo, P, F, n_heads_, head_dim_, s) ||
-                !voc_attn_cached(qkv, st->kc + lo, st->vc + lo, att, P, F, n_heads_, head_dim_, s))
-                return false;
-        } else if (!attn_prefill(qkv, rope_, att, F, n_heads_, head_dim_, s, nb_)) return false;
+        if (!attn((int)(&L - layers_.data()), qkv, att)) return false;
         GemvParams o = row_gemv();
         o.W = L.o; o.N = VH; o.K = LAT; o.B = FR; o.pro = PRO_F16; o.x = att; o.ldx = LAT;
         o.scale = L.attn_scale; o.resid = x; o.ldr = VH; o.out_f32 = x; o.ldo = VH;
@@ -560,8 +554,39 @@ bool Vocoder::frame_rows(const int32_t *codes_dev, int F, hipStream_t s, Stream 
     // final RMSNorm + output_proj + bias -> [F][LAT]   (:740-744)
     GemvParams op = row_gemv();
     op.W = out_proj_; op.N = LAT; op.K = VH; op.B = FR; op.pro = PRO_RMS; op.x = x; op.ldx = VH; op.nw = pre_norm_;
-    op.eps = 1e-5f; op.bias = out_proj_b_; op.out_f32 = B + (size_t)hrows * LAT; op.ldo = LAT;
-    if (!gemv(op, s)) return false;
+    op.eps = 1e-5f; op.bias = out_proj_b_; op.out_f32 = out; op.ldo = LAT;
+    return gemv(op, s);
+}
+
+// Frame-rate half.  st null: the whole utterances of a one-shot decode.  st set (nb_ = 1): the F new frames of a stream
+// at positions P..P+F-1 -- pre_conv sees the RVQ rows of the previous two frames in front of the new ones, the
+// attention runs against the stream's K/V caches, and output_proj's rows land after the stream's halo rows in buf_[1],
+// which then holds the window the convolution stack runs on.  Every launch is the one-shot path's on fewer rows.
+bool Vocoder::frame_rows(const int32_t *codes_dev, int F, hipStream_t s, Stream *st) {
+    const int VH = hidden_, LAT = latent_;
+    const int FR = F * nb_;   // frame rows of the batch
+    float *A = buf_[0], *B = buf_[1], *C = buf_[2];
+    const int P = st ? st->frames : 0;
+    const int tail = st ? std::min(2, P) : 0;            // carried RVQ rows in front of the new ones
+    const int hrows = st ? std::min(st->halo, P) : 0;    // carried output_proj rows in front of the new ones
+    // 1) RVQ
+    if (!rvq_rows(codes_dev, FR, A + (size_t)tail * VH, s)) return false;
+    if (st) {
+        if (tail) Q3T_HIP(hipMemcpyAsync(A, st->rvq_tail, (size_t)tail * VH * 4, hipMemcpyDeviceToDevice, s));
+        const int keep = std::min(2, P + F);   // the next push's tail: the last rows of [tail + F]
+        Q3T_HIP(hipMemcpyAsync(st->rvq_tail, A + (size_t)(tail + F - keep) * VH, (size_t)keep * VH * 4,
+                               hipMemcpyDeviceToDevice, s));
+    }
+    // 2) causal pre-conv k3 (left pad 2) -> [F][LAT]   (:705-718)
+    if (!run_conv(pre_conv_, A, tail + F, 2, 1, nullptr, C, nullptr, 0, s)) return false;
+    // 3) the transformer over the new rows
+    auto attn = [&](int layer, float *qkv, uint16_t *att) {
+        if (!st) return attn_prefill(qkv, rope_, att, F, n_heads_, head_dim_, s, nb_);
+        const size_t lo = (size_t)layer * st->max_frames * LAT;   // this layer's cache
+        return voc_kv_append(qkv, st->rope, st->kc + lo, st->vc + lo, P, F, n_heads_, head_dim_, s) &&
+               voc_attn_cached(qkv, st->kc + lo, st->vc + lo, att, P, F, n_heads_, head_dim_, s);
+    };
+    if (!layer_rows(C + (size_t)tail * LAT, FR, B + (size_t)hrows * LAT, s, attn)) return false;
     if (st) {
         if (hrows) Q3T_HIP(hipMemcpyAsync(B, st->halo_rows, (size_t)hrows * LAT * 4, hipMemcpyDeviceToDevice, s));
         const int keep = std::min(st->halo, P + F);   // the next push's halo: the last rows of [hrows + F]
@@ -835,6 +860,218 @@ bool Vocoder::stream_push(Stream *st, const int32_t *codes, int n, float *pcm, i
     if (count) Q3T_HIP(hipMemcpyAsync(pcm, pcm_ + off, (size_t)count * 4, hipMemcpyDeviceToHost, stream_));
     Q3T_HIP(hipStreamSynchronize(stream_));
     if (n_out) *n_out = count;
+    return true;
+}
+
+bool Vocoder::stream_push_batch(int S, Stream *const *sts, const int32_t *const *codes, const int32_t *n_frames,
+                                float *const *pcm, const int64_t *pcm_cap, int64_t *n_out) {
+    last_groups_ = 0;
+    if (n_out) for (int j = 0; j < S; ++j) n_out[j] = 0;
+    if (S <= 0) { set_error("vocoder stream batch: n_streams must be > 0"); return false; }
+    if (!sts || !codes || !n_frames || !pcm || !pcm_cap || !n_out) { set_error("null argument"); return false; }
+    // ---- validation: nothing below this block fails on an argument
+    struct Item {
+        Stream *st;
+        int P, n, tail, hrows;   // position, new frames, carried RVQ rows, carried output_proj rows
+        int row0;                // first of its rows in the packed row-wise buffers
+        size_t wa, wh;           // first row of its pre_conv window / convolution-stack window among all windows
+        int64_t total, count;    // samples after the push, samples of the push
+    };
+    std::vector<Item> it((size_t)S);
+    {
+        std::vector<const Stream *> seen;
+        for (int j = 0; j < S; ++j) {
+            Stream *st = sts[j];
+            const std::string who = "vocoder stream batch: stream " + std::to_string(j);
+            if (!st || std::find(streams_.begin(), streams_.end(), st) == streams_.end()) {
+                set_error(who + " is not an open stream of this decoder");
+                return false;
+            }
+            seen.push_back(st);
+            const int n = n_frames[j], P = st->frames;
+            if (n <= 0) { set_error(who + ": n_frames must be > 0"); return false; }
+            if (!codes[j] || !pcm[j]) { set_error(who + ": null argument"); return false; }
+            if ((int64_t)P + n > st->max_frames) {
+                set_error(who + ": push of " + std::to_string(n) + " frames after " + std::to_string(P) +
+                          " exceeds max_frames " + std::to_string(st->max_frames));
+                return false;
+            }
+            Item &q = it[j];
+            q.st = st; q.P = P; q.n = n; q.tail = std::min(2, P); q.hrows = std::min(st->halo, P);
+            q.total = full_len(P + n);
+            q.count = std::max<int64_t>(q.total - st->samples, 0);
+            if (pcm_cap[j] < q.count) {
+                set_error(who + ": pcm_cap " + std::to_string(pcm_cap[j]) + " < " + std::to_string(q.count) +
+                          " samples of this push");
+                return false;
+            }
+        }
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) {
+            set_error("vocoder stream batch: a stream is given twice");
+            return false;
+        }
+    }
+    // ---- groups: streams whose pre_conv window (tail + n rows) and convolution-stack window (hrows + n rows) have the
+    // same lengths share those launch sequences, one sequence per grid z.  A window is never padded on the left: the
+    // biases make zero rows differ from the true left edge.  A group is split only at batch_frames() window rows.
+    std::vector<int> ord((size_t)S);
+    for (int j = 0; j < S; ++j) ord[j] = j;
+    auto key_less = [&](int a, int b) {
+        const Item &x = it[a], &y = it[b];
+        if (x.n != y.n) return x.n < y.n;
+        if (x.hrows != y.hrows) return x.hrows < y.hrows;
+        return x.tail < y.tail;
+    };
+    std::stable_sort(ord.begin(), ord.end(), key_less);
+    struct Group { int first, nb; };   // ord[first .. first+nb-1]
+    std::vector<Group> groups;
+    for (int i = 0; i < S;) {
+        const Item &q = it[ord[i]];
+        const int cap = std::max(1, batch_frames_ / (q.hrows + q.n));
+        int nb = 1;
+        while (i + nb < S && nb < cap && !key_less(ord[i], ord[i + nb])) ++nb;
+        groups.push_back({i, nb});
+        i += nb;
+    }
+    size_t R = 0, WA = 0, WH = 0;   // packed rows, pre_conv window rows, convolution-stack window rows
+    int max_n = 0, max_tiles = 0;
+    for (int j = 0; j < S; ++j) {
+        it[j].row0 = (int)R;
+        R += (size_t)it[j].n;
+        max_n = std::max(max_n, it[j].n);
+        max_tiles = std::max(max_tiles, (it[j].P + it[j].n + 31) / 32 - it[j].P / 32);
+    }
+    for (int i = 0; i < S; ++i) {
+        Item &q = it[ord[i]];
+        q.wa = WA; q.wh = WH;
+        WA += (size_t)(q.tail + q.n);
+        WH += (size_t)(q.hrows + q.n);
+    }
+    if (R > (size_t)1 << 30) { set_error("vocoder stream batch: too many frames in one call"); return false; }
+    // ---- scratch: every growth before the first launch (ensure() frees what it replaces)
+    for (const Group &g : groups) {
+        const Item &q = it[ord[g.first]];
+        if (!ensure(std::max(q.hrows + q.n, q.n + 2), g.nb, WA)) return false;
+    }
+    const int VH = hidden_, LAT = latent_;
+    const size_t n_copy = 7 * (size_t)S;
+    const size_t desc_bytes = (size_t)S * sizeof(VocStreamDesc) + n_copy * sizeof(VocCopyDesc);
+    if (WH * LAT > sb_win_cap_) {
+        if (sb_win_) hipFree(sb_win_);
+        sb_win_ = nullptr; sb_win_cap_ = 0;
+        void *p = nullptr;
+        if (hipMalloc(&p, WH * LAT * 4) != hipSuccess) { (void)hipGetLastError(); set_error("vocoder stream batch: window alloc"); return false; }
+        sb_win_ = (float *)p; sb_win_cap_ = WH * LAT;
+    }
+    if (desc_bytes > sb_desc_cap_) {
+        if (sb_desc_) hipFree(sb_desc_);
+        sb_desc_ = nullptr; sb_desc_cap_ = 0;
+        if (hipMalloc(&sb_desc_, desc_bytes) != hipSuccess) { (void)hipGetLastError(); sb_desc_ = nullptr; set_error("vocoder stream batch: descriptor alloc"); return false; }
+        sb_desc_cap_ = desc_bytes;
+    }
+    float *A = buf_[0], *B = buf_[1], *C = buf_[2], *WIN = sb_win_;
+    // ---- descriptors of the whole call, one upload: the attention's per stream, then the five copy launches'
+    std::vector<VocStreamDesc> sd((size_t)S);
+    std::vector<VocCopyDesc> cd;
+    cd.reserve(n_copy);
+    struct Span { size_t first = 0; int count = 0; int64_t max_n = 0; } sp[5];
+    auto add = [&](Span &spn, const float *src, float *dst, size_t nfl) {
+        if (!nfl) return;
+        if (!spn.count) spn.first = cd.size();
+        cd.push_back(VocCopyDesc{src, dst, (int64_t)nfl});
+        ++spn.count;
+        spn.max_n = std::max<int64_t>(spn.max_n, (int64_t)nfl);
+    };
+    for (int j = 0; j < S; ++j) {
+        const Item &q = it[j];
+        Stream *st = q.st;
+        sd[j].kc = st->kc; sd[j].vc = st->vc; sd[j].rope = st->rope;
+        sd[j].layer_stride = (int64_t)st->max_frames * LAT;
+        sd[j].P = q.P; sd[j].n = q.n; sd[j].row0 = q.row0;
+    }
+    for (int j = 0; j < S; ++j) {   // 0: [tail | new RVQ rows] windows in A, from the state and the packed rows in C
+        const Item &q = it[j];
+        add(sp[0], q.st->rvq_tail, A + q.wa * VH, (size_t)q.tail * VH);
+        add(sp[0], C + (size_t)q.row0 * VH, A + (q.wa + q.tail) * VH, (size_t)q.n * VH);
+    }
+    for (int j = 0; j < S; ++j) {   // 1: the next push's tail, the last rows of the window
+        const Item &q = it[j];
+        const int keep = std::min(2, q.P + q.n);
+        add(sp[1], A + (q.wa + q.tail + q.n - keep) * VH, q.st->rvq_tail, (size_t)keep * VH);
+    }
+    for (int j = 0; j < S; ++j) {   // 2: pre_conv's rows of the new frames (windows in B), packed into C
+        const Item &q = it[j];
+        add(sp[2], B + (q.wa + q.tail) * LAT, C + (size_t)q.row0 * LAT, (size_t)q.n * LAT);
+    }
+    for (int j = 0; j < S; ++j) {   // 3: [halo rows | new output_proj rows] windows, from the state and the packed rows in C
+        const Item &q = it[j];
+        add(sp[3], q.st->halo_rows, WIN + q.wh * LAT, (size_t)q.hrows * LAT);
+        add(sp[3], C + (size_t)q.row0 * LAT, WIN + (q.wh + q.hrows) * LAT, (size_t)q.n * LAT);
+    }
+    for (int j = 0; j < S; ++j) {   // 4: the next push's halo, the last rows of the window
+        const Item &q = it[j];
+        const int keep = std::min(q.st->halo, q.P + q.n);
+        add(sp[4], WIN + (q.wh + q.hrows + q.n - keep) * LAT, q.st->halo_rows, (size_t)keep * LAT);
+    }
+    std::vector<unsigned char> hd(desc_bytes, 0);
+    std::memcpy(hd.data(), sd.data(), sd.size() * sizeof(VocStreamDesc));
+    std::memcpy(hd.data() + (size_t)S * sizeof(VocStreamDesc), cd.data(), cd.size() * sizeof(VocCopyDesc));
+    const VocStreamDesc *dsd = static_cast<const VocStreamDesc *>(sb_desc_);
+    const VocCopyDesc *dcd = reinterpret_cast<const VocCopyDesc *>(static_cast<const unsigned char *>(sb_desc_) +
+                                                                   (size_t)S * sizeof(VocStreamDesc));
+    const bool vec4 = VH % 4 == 0 && LAT % 4 == 0;
+    hipStream_t s = stream_;
+    auto copies = [&](const Span &spn) { return voc_copy_batch(dcd + spn.first, spn.count, spn.max_n, vec4, s); };
+    std::vector<int32_t> hc(R * 16);
+    for (int j = 0; j < S; ++j) std::memcpy(hc.data() + (size_t)it[j].row0 * 16, codes[j], (size_t)it[j].n * 16 * 4);
+    Q3T_HIP(hipMemcpyAsync(codes_, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, s));
+    Q3T_HIP(hipMemcpyAsync(sb_desc_, hd.data(), desc_bytes, hipMemcpyHostToDevice, s));
+    // ---- frame-rate half: frame_rows' stages, the row-wise ones over all R rows at once
+    nb_ = 1;
+    if (!rvq_rows(codes_, (int)R, C, s) || !copies(sp[0]) || !copies(sp[1])) return false;
+    for (const Group &g : groups) {
+        const Item &q = it[ord[g.first]];
+        nb_ = g.nb;
+        const bool ok = run_conv(pre_conv_, A + q.wa * VH, q.tail + q.n, 2, 1, nullptr, B + q.wa * LAT, nullptr, 0, s);
+        nb_ = 1;
+        if (!ok) return false;
+    }
+    if (!copies(sp[2])) return false;
+    auto attn = [&](int layer, float *qkv, uint16_t *att) {
+        return voc_kv_append_batch(qkv, dsd, S, max_n, layer, n_heads_, head_dim_, s) &&
+               voc_attn_cached_batch(qkv, att, dsd, S, max_tiles, layer, n_heads_, head_dim_, s);
+    };
+    if (!layer_rows(C, (int)R, C, s, attn) || !copies(sp[3]) || !copies(sp[4])) return false;
+    // from here on every stream's state is that of P + n frames
+    for (Item &q : it) {
+        q.st->frames = q.P + q.n;
+        q.st->samples = q.total;
+    }
+    // ---- convolution half: one launch sequence per group, its windows copied to where conv_stack reads them
+    const int64_t rate = full_len(2) - full_len(1);
+    for (const Group &g : groups) {
+        const Item &q0 = it[ord[g.first]];
+        const int W = q0.hrows + q0.n;
+        Q3T_HIP(hipMemcpyAsync(B, WIN + q0.wh * LAT, (size_t)g.nb * W * LAT * 4, hipMemcpyDeviceToDevice, s));
+        int64_t nwin = 0;
+        nb_ = g.nb;
+        const bool ok = conv_stack(W, pcm_, &nwin, s);
+        nb_ = 1;
+        if (!ok) return false;
+        ++last_groups_;
+        for (int k = 0; k < g.nb; ++k) {
+            const int j = ord[g.first + k];
+            const Item &q = it[j];
+            // as in stream_push: the window's decode is the full decode shifted by (P - hrows) * rate samples
+            const int64_t off = (q.total - q.count) - (int64_t)(q.P - q.hrows) * rate;
+            if (off < 0 || off + q.count != nwin) { set_error("vocoder stream: window bookkeeping"); return false; }
+            if (q.count)
+                Q3T_HIP(hipMemcpyAsync(pcm[j], pcm_ + (size_t)k * nwin + off, (size_t)q.count * 4, hipMemcpyDeviceToHost, s));
+        }
+    }
+    Q3T_HIP(hipStreamSynchronize(s));
+    for (int j = 0; j < S; ++j) n_out[j] = it[j].count;
     return true;
 }
 

@@ -2,6 +2,7 @@
 // (src/trt_vocoder.cpp) and the GGML AudioTokenizerDecoder (src/audio_tokenizer_decoder.cpp).
 #pragma once
 #include <cstdlib>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -28,7 +29,7 @@ public:
                       int64_t *n_out, int chunk_frames = 40);
     // FULL decode of device-resident codes [nb][F][16] into pcm_dev [nb][n_samples(F, 0)]; ensure(F, nb) first
     bool decode_device(const int32_t *codes_dev, int n_frames, float *pcm_dev, int64_t *n_out, hipStream_t s, int nb = 1);
-    bool ensure(int n_frames, int nb = 1);
+    bool ensure(int n_frames, int nb = 1, size_t rows = 0);
     // frames per batched launch sequence (utterances x frames); scratch grows to this (~3 MB per frame)
     int batch_frames() const { return batch_frames_; }
     void set_batch_frames(int f) { batch_frames_ = f > 0 ? f : 4096; }
@@ -63,6 +64,18 @@ public:
     // Bad arguments (n_frames <= 0, more than max_frames in total, pcm_cap too small) fail before any state changes
     bool stream_push(Stream *st, const int32_t *codes_host, int n_frames, float *pcm_host, int64_t pcm_cap, int64_t *n_out);
     void stream_close(Stream *st);
+    // One push on each of n_streams streams of this decoder (any mix of positions and sizes) through shared launches:
+    // the row-wise stages run once over the packed new rows of all streams, the per-layer append and attention are one
+    // launch each for all streams (voc_kv_append_batch / voc_attn_cached_batch), and pre_conv and the convolution
+    // stack run once per group of streams with the same (n_frames, carried halo rows, carried tail rows), the group
+    // as grid z.  pcm_host[j] receives stream j's samples, n_out[j] their count; they are, bit for bit, what
+    // stream_push on stream j alone returns.  Every stream is validated before any state changes (a closed or foreign
+    // stream, a duplicate, n_frames <= 0, more than max_frames in total, pcm_cap too small, a null pointer): on an
+    // error no stream has moved and every n_out[j] is 0.
+    bool stream_push_batch(int n_streams, Stream *const *sts, const int32_t *const *codes_host, const int32_t *n_frames,
+                           float *const *pcm_host, const int64_t *pcm_cap, int64_t *n_out);
+    // convolution-stack launch sequences (groups) of the last stream_push_batch; 0 after one that failed validation
+    int stream_last_groups() const { return last_groups_; }
 
 private:
     struct Conv { uint16_t *w = nullptr; float *b = nullptr; int k = 0, ic = 0, oc = 0; };   // w: [k][oc][ic]
@@ -97,6 +110,10 @@ private:
     // rows: against its state, written after the rows of its halo); conv_stack: upsample blocks .. output conv of the
     // T-frame sequences in buf_[1]
     bool frame_rows(const int32_t *codes_dev, int F, hipStream_t s, Stream *st);
+    // frame_rows' row-wise parts, shared with stream_push_batch (packed rows of many streams)
+    bool rvq_rows(const int32_t *codes_dev, int FR, float *out, hipStream_t s);
+    bool layer_rows(const float *pre, int FR, float *out, hipStream_t s,
+                    const std::function<bool(int, float *, uint16_t *)> &attn);
     bool conv_stack(int F, float *pcm_dev, int64_t *n_out, hipStream_t s);
 
     bool loaded_ = false;
@@ -126,6 +143,11 @@ private:
     int *cols_ = nullptr;
     float *pcm_ = nullptr, *rope_ = nullptr;
     std::vector<Stream *> streams_;   // open streams (freed with the decoder)
+    // stream_push_batch: the convolution-stack windows of every stream of a call, its device descriptors, group count
+    float *sb_win_ = nullptr;
+    void *sb_desc_ = nullptr;
+    size_t sb_win_cap_ = 0, sb_desc_cap_ = 0;   // floats, bytes
+    int last_groups_ = 0;
 };
 
 }  // namespace q3t

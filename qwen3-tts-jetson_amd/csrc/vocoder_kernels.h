@@ -103,6 +103,32 @@ bool attn_prefill(float *qkv, const float *rope, uint16_t *out, int F, int nH, i
 bool voc_kv_append(float *qkv, const float *rope, float *kc, float *vc, int P, int n, int nH, int D, hipStream_t s);
 bool voc_attn_cached(const float *qkv, const float *kc, const float *vc, uint16_t *out, int P, int n, int nH, int D,
                      hipStream_t s);
+// The same for many streams in ONE launch each (Vocoder::stream_push_batch).  descs is a device array of n_streams
+// descriptors; stream j's n new rows are rows row0 .. row0+n-1 of the packed qkv [sum n][3*nH*D] and out [sum n][nH*D],
+// its caches of layer `layer` start layer * layer_stride floats into kc / vc.  Per stream the arithmetic is
+// voc_kv_append's and voc_attn_cached's (one shared body each), so its bits do not depend on the batch around it.
+// max_n / max_tiles: the largest n, and the largest tile count (P + n + 31) / 32 - P / 32, over the streams (the
+// grids; a workgroup past its own stream's count returns at once).
+struct VocStreamDesc {
+    float *kc = nullptr, *vc = nullptr;   // [layers][max_frames][nH*D], layer 0
+    const float *rope = nullptr;          // [max_frames][D]
+    int64_t layer_stride = 0;             // max_frames * nH * D
+    int32_t P = 0, n = 0, row0 = 0, pad_ = 0;
+};
+bool voc_kv_append_batch(float *qkv, const VocStreamDesc *descs, int n_streams, int max_n, int layer, int nH, int D,
+                         hipStream_t s);
+bool voc_attn_cached_batch(const float *qkv, uint16_t *out, const VocStreamDesc *descs, int n_streams, int max_tiles,
+                           int layer, int nH, int D, hipStream_t s);
+// n_descs independent copies of `n` floats each in one launch (descs: a device array; max_n: the largest n).  The
+// carried state of a batched stream push: windows assembled from state and new rows, rows compacted, state written
+// back.  Copies only.  A source and a destination of one launch must not overlap.  vec4: every n of the launch is a
+// multiple of 4 and every pointer 16-byte aligned (16-byte moves).
+struct VocCopyDesc {
+    const float *src = nullptr;
+    float *dst = nullptr;
+    int64_t n = 0;
+};
+bool voc_copy_batch(const VocCopyDesc *descs, int n_descs, int64_t max_n, bool vec4, hipStream_t s);
 bool codes_cols(const int32_t *codes, int *cols, int F, int ncb, hipStream_t s);
 
 }  // namespace q3t

@@ -1112,9 +1112,10 @@ bool attn_prefill(float *qkv, const float *rope, uint16_t *out, int F, int nH, i
 // P..P+n-1, the keys and values of every frame so far in a per-layer f32 cache [max_frames][nH*64].
 // k_voc_kv_append is k_rope_qk on the new rows (q rotated in place; k rotated into the cache, v copied into it; the
 // same expressions, the rope table indexed by absolute position).
-__global__ void k_voc_kv_append(float *qkv, const float *rope, float *kc, float *vc, int P, int n, int nH) {
+__device__ __forceinline__ void voc_kv_append_rows(float *qkv, const float *rope, float *kc, float *vc, int P, int n, int nH,
+                                                   int blk) {
     constexpr int D = 64;
-    const int idx = blockIdx.x * 256 + threadIdx.x;   // (row, q/k/v, head, pair)
+    const int idx = blk * 256 + threadIdx.x;   // (row, q/k/v, head, pair)
     const int total = n * 3 * nH * 32;
     if (idx >= total) return;
     const int i = idx & 31, hh = (idx >> 5) % (3 * nH), r = idx / (96 * nH);
@@ -1136,6 +1137,17 @@ __global__ void k_voc_kv_append(float *qkv, const float *rope, float *kc, float 
     dst[i + 32] = __builtin_fmaf(x0, sn, x1 * c);
 }
 
+__global__ void k_voc_kv_append(float *qkv, const float *rope, float *kc, float *vc, int P, int n, int nH) {
+    voc_kv_append_rows(qkv, rope, kc, vc, P, n, nH, blockIdx.x);
+}
+// many streams in one launch: grid (blocks of the largest n, streams); the body above on stream blockIdx.y's rows
+__global__ void k_voc_kv_append_batch(float *qkv, const VocStreamDesc *descs, int layer, int nH) {
+    const VocStreamDesc d = descs[blockIdx.y];
+    if ((int)blockIdx.x * 256 >= d.n * 3 * nH * 32) return;
+    const size_t lo = (size_t)layer * d.layer_stride;
+    voc_kv_append_rows(qkv + (size_t)d.row0 * 3 * nH * 64, d.rope, d.kc + lo, d.vc + lo, d.P, d.n, nH, blockIdx.x);
+}
+
 // k_attn_prefill with the keys and values read from the cache: a second copy of its body rather than a shared
 // __device__ function, so that k_attn_prefill's own code is untouched.  Per query the arithmetic is k_attn_prefill's
 // for a sequence of Ft = P + n frames: query tiles stay aligned to absolute multiples of 32 (the first tile starts at
@@ -1143,14 +1155,15 @@ __global__ void k_voc_kv_append(float *qkv, const float *rope, float *kc, float 
 // lane assignment, online-softmax update and P.V order, f16 output.  Cache rows at or past Ft are never loaded (rows
 // clamped to Ft - 1 and zeroed at the LDS store, as k_attn_prefill does past F).
 // qkv: the n new rows [n][3*nH*64] (q already rotated); out [n][nH*64] f16.
-__global__ void __launch_bounds__(512) k_voc_attn_cached(const float *qkv, const float *kc, const float *vc, uint16_t *out,
-                                                         int P, int n, int nH) {
+// (tile: the workgroup's query tile counted from P / 32, h: its head -- the grid x and y of the one-stream launch)
+__device__ __forceinline__ void voc_attn_cached_tile(const float *qkv, const float *kc, const float *vc, uint16_t *out, int P,
+                                                     int n, int nH, int tile, int h) {
     constexpr int D = 64, QT = 32, KT = 64, KP = D + 4, LQ = 16;
     __shared__ __attribute__((aligned(16))) float ks[KT * KP];
     __shared__ __attribute__((aligned(16))) float vs[KT * KP];
     __shared__ float ps[QT][KT + 1];
     const int F = P + n;
-    const int h = blockIdx.y, q0 = (P / QT + blockIdx.x) * QT;
+    const int q0 = (P / QT + tile) * QT;
     const int tid = threadIdx.x, qi = tid / LQ, g = tid % LQ;
     const int LD = 3 * nH * D, LC = nH * D;
     const int qpos = q0 + qi;
@@ -1234,6 +1247,20 @@ __global__ void __launch_bounds__(512) k_voc_attn_cached(const float *qkv, const
         *reinterpret_cast<uint2 *>(out + (size_t)(qpos - P) * nH * D + h * D + g * 4) = o;
     }
 }
+__global__ void __launch_bounds__(512) k_voc_attn_cached(const float *qkv, const float *kc, const float *vc, uint16_t *out,
+                                                         int P, int n, int nH) {
+    voc_attn_cached_tile(qkv, kc, vc, out, P, n, nH, blockIdx.x, blockIdx.y);
+}
+// many streams in one launch: grid (largest tile count, heads, streams).  A workgroup past its stream's tile count
+// returns before the body's first barrier; the condition is uniform over the workgroup.
+__global__ void __launch_bounds__(512) k_voc_attn_cached_batch(const float *qkv, uint16_t *out, const VocStreamDesc *descs,
+                                                               int layer, int nH) {
+    const VocStreamDesc d = descs[blockIdx.z];
+    if ((int)blockIdx.x >= (d.P + d.n + 31) / 32 - d.P / 32) return;
+    const size_t lo = (size_t)layer * d.layer_stride;
+    voc_attn_cached_tile(qkv + (size_t)d.row0 * 3 * nH * 64, d.kc + lo, d.vc + lo, out + (size_t)d.row0 * nH * 64, d.P, d.n,
+                         nH, blockIdx.x, blockIdx.y);
+}
 bool voc_kv_append(float *qkv, const float *rope, float *kc, float *vc, int P, int n, int nH, int D, hipStream_t s) {
     if (D != 64) { set_error("voc_kv_append: head_dim must be 64"); return false; }
     if (P < 0 || nH <= 0) { set_error("voc_kv_append: bad position or head count"); return false; }
@@ -1250,6 +1277,58 @@ bool voc_attn_cached(const float *qkv, const float *kc, const float *vc, uint16_
     const int tiles = (P + n + 31) / 32 - P / 32;
     hipLaunchKernelGGL(k_voc_attn_cached, dim3(tiles, nH), dim3(512), 0, s, qkv, kc, vc, out, P, n, nH);
     Q3T_HIP(hipGetLastError());
+    return true;
+}
+
+bool voc_kv_append_batch(float *qkv, const VocStreamDesc *descs, int n_streams, int max_n, int layer, int nH, int D,
+                         hipStream_t s) {
+    if (D != 64) { set_error("voc_kv_append_batch: head_dim must be 64"); return false; }
+    if (nH <= 0 || layer < 0) { set_error("voc_kv_append_batch: bad layer or head count"); return false; }
+    if (n_streams <= 0 || max_n <= 0) return true;
+    if (!descs) { set_error("voc_kv_append_batch: null descriptors"); return false; }
+    for (int j = 0; j < n_streams; j += 65535) {   // grid y holds the streams
+        const int ns = std::min(n_streams - j, 65535);
+        hipLaunchKernelGGL(k_voc_kv_append_batch, dim3((max_n * 3 * nH * 32 + 255) / 256, ns), dim3(256), 0, s, qkv, descs + j,
+                           layer, nH);
+        Q3T_HIP(hipGetLastError());
+    }
+    return true;
+}
+bool voc_attn_cached_batch(const float *qkv, uint16_t *out, const VocStreamDesc *descs, int n_streams, int max_tiles,
+                           int layer, int nH, int D, hipStream_t s) {
+    if (D != 64) { set_error("voc_attn_cached_batch: head_dim must be 64"); return false; }
+    if (nH <= 0 || layer < 0) { set_error("voc_attn_cached_batch: bad layer or head count"); return false; }
+    if (n_streams <= 0 || max_tiles <= 0) return true;
+    if (!descs) { set_error("voc_attn_cached_batch: null descriptors"); return false; }
+    for (int j = 0; j < n_streams; j += 65535) {   // grid z holds the streams
+        const int ns = std::min(n_streams - j, 65535);
+        hipLaunchKernelGGL(k_voc_attn_cached_batch, dim3(max_tiles, nH, ns), dim3(512), 0, s, qkv, out, descs + j, layer, nH);
+        Q3T_HIP(hipGetLastError());
+    }
+    return true;
+}
+
+// descs[blockIdx.y].n floats from src to dst, grid-stride over x; V = float4 when every pointer and count of the launch
+// allows it
+template <typename V>
+__global__ void k_voc_copy_batch(const VocCopyDesc *descs) {
+    const VocCopyDesc d = descs[blockIdx.y];
+    const V *src = reinterpret_cast<const V *>(d.src);
+    V *dst = reinterpret_cast<V *>(d.dst);
+    const int64_t cnt = d.n / (int64_t)(sizeof(V) / 4);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * 256) dst[i] = src[i];
+}
+bool voc_copy_batch(const VocCopyDesc *descs, int n_descs, int64_t max_n, bool vec4, hipStream_t s) {
+    if (n_descs <= 0 || max_n <= 0) return true;
+    if (!descs) { set_error("voc_copy_batch: null descriptors"); return false; }
+    const int64_t per = vec4 ? 1024 : 256;   // floats per workgroup and pass
+    const int gx = (int)std::min<int64_t>((max_n + per - 1) / per, 64);
+    for (int j = 0; j < n_descs; j += 65535) {
+        const int nd = std::min(n_descs - j, 65535);
+        if (vec4) hipLaunchKernelGGL(k_voc_copy_batch<float4>, dim3(gx, nd), dim3(256), 0, s, descs + j);
+        else hipLaunchKernelGGL(k_voc_copy_batch<float>, dim3(gx, nd), dim3(256), 0, s, descs + j);
+        Q3T_HIP(hipGetLastError());
+    }
     return true;
 }
 

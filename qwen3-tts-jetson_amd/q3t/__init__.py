@@ -83,6 +83,9 @@ _lib.q3t_vocoder_decode_batch.argtypes = [_P, C.c_int32, C.POINTER(C.c_void_p), 
 _lib.q3t_vocoder_set_batch_frames.argtypes = [_P, C.c_int32]
 _lib.q3t_vocoder_stream_open.argtypes = [_P, C.c_int32, C.POINTER(_P)]
 _lib.q3t_vocoder_stream_push.argtypes = [_P, _P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]
+_lib.q3t_vocoder_stream_push_batch.argtypes = [_P, C.c_int32, _P, _P, _P, _P, _P]
+_lib.q3t_vocoder_stream_last_groups.restype = C.c_int32
+_lib.q3t_vocoder_stream_last_groups.argtypes = [_P]
 _lib.q3t_vocoder_stream_samples.restype = C.c_int64
 _lib.q3t_vocoder_stream_samples.argtypes = [_P]
 _lib.q3t_vocoder_stream_frames.restype = C.c_int32
@@ -113,7 +116,8 @@ EXPORTS = ["q3t_last_error", "q3t_default_params", "q3t_ctx_create", "q3t_ctx_de
            "q3t_generate", "q3t_generate_stream", "q3t_generate_queue", "q3t_comm_unique_id", "q3t_ctx_create_shared",
            "q3t_plan_weight_layout", "q3t_ctx_create_replica", "q3t_comm_allreduce_max", "q3t_set_mfma_min_batch", "q3t_synchronize", "q3t_last_timing", "q3t_time_stage", "q3t_persist_status", "q3t_persist_kernels", "q3t_vocoder_num_samples", "q3t_vocoder_flops", "q3t_vocoder_decode",
            "q3t_vocoder_decode_chunked", "q3t_vocoder_decode_batch", "q3t_vocoder_set_batch_frames",
-           "q3t_vocoder_stream_open", "q3t_vocoder_stream_push", "q3t_vocoder_stream_samples",
+           "q3t_vocoder_stream_open", "q3t_vocoder_stream_push", "q3t_vocoder_stream_push_batch",
+           "q3t_vocoder_stream_last_groups", "q3t_vocoder_stream_samples",
            "q3t_vocoder_stream_frames", "q3t_vocoder_stream_halo", "q3t_vocoder_stream_close", "q3t_speaker_dim", "q3t_ctx_create_speaker", "q3t_speaker_encode", "q3t_speaker_mel",
            "q3t_tokenizer_load", "q3t_tokenizer_free", "q3t_tokenizer_info", "q3t_tokenizer_encode",
            "q3t_tokenizer_decode", "q3t_talker_forward", "q3t_talker_prefill",
@@ -466,6 +470,32 @@ class Engine:
     def vocoder_stream(self, max_frames=4096):
         """a VocoderStream on this context: .push(codes) -> float32 PCM, .frames, .samples, .halo, .close()"""
         return VocoderStream(self, max_frames)
+
+    def vocoder_stream_push_batch(self, streams, pieces):
+        """one push on each of the VocoderStreams `streams` of this context through shared launches
+        (q3t_vocoder_stream_push_batch): pieces[j] is stream j's codes [n_j][16].  Returns the list of each stream's
+        next samples (float32), bit-identical to streams[j].push(pieces[j]).  On an error no stream has moved."""
+        streams, pieces = list(streams), list(pieces)
+        if len(streams) != len(pieces):
+            raise ValueError("one piece of codes per stream")
+        k = len(streams)
+        codes = [np.ascontiguousarray(p, np.int32).reshape(-1, 16) for p in pieces]
+        handles = [st._handle() for st in streams]
+        caps = [max(self.vocoder_num_samples(st.frames + c.shape[0], VOCODER_FULL) - st.samples, 0) if c.shape[0] > 0 else 0
+                for st, c in zip(streams, codes)]
+        pcm = [np.zeros(max(cap, 1), np.float32) for cap in caps]
+        harr = (C.c_void_p * max(k, 1))(*[h.value for h in handles])
+        carr = (C.c_void_p * max(k, 1))(*[c.ctypes.data for c in codes])
+        parr = (C.c_void_p * max(k, 1))(*[p.ctypes.data for p in pcm])
+        nf = (C.c_int32 * max(k, 1))(*[c.shape[0] for c in codes])
+        cap = (C.c_int64 * max(k, 1))(*caps)
+        ns = (C.c_int64 * max(k, 1))()
+        _check(_lib.q3t_vocoder_stream_push_batch(harr, k, carr, nf, parr, cap, ns))
+        return [p[:ns[j]] for j, p in enumerate(pcm)]
+
+    def vocoder_stream_last_groups(self):
+        """convolution-stack launch sequences (groups of streams that shared every launch) of the last batched push"""
+        return _lib.q3t_vocoder_stream_last_groups(self.h)
 
     def vocoder_set_batch_frames(self, frames):
         _check(_lib.q3t_vocoder_set_batch_frames(self.h, int(frames)))

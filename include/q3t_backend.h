@@ -116,6 +116,32 @@ int q3t_generate_stream(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens, c
 int q3t_generate_queue(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens, const int32_t *n_tokens,
                        const float *const *speaker, const q3t_gen_params *p, int32_t *codes, int32_t *n_frames,
                        int32_t max_active);
+/* q3t_generate_queue that hands frames out while it runs, reports an utterance when it ends and lets the caller cancel
+ * one.  Every `interval` frames of the queue's frame loop (a tick) the new frames of all running utterances are
+ * collected by one launch and one copy; when utterances end (EOS or max_len) the rest of their frames are collected
+ * the same way and marked final, before their slots are refilled.
+ * one call per tick or finish: n entries; utt[i] = utterance index in the call, codes[i] -> [n_frames[i]][16] (valid during
+ * the call only), final[i] != 0 on the utterance's last delivery; stop[i] (zeroed by the caller of the callback) set
+ * non-zero cancels utt[i].  Entries come in increasing utt[i].  Return 0 to abort the whole queue.
+ * Per utterance: deliveries arrive in order; a non-final one carries 1..interval frames; there is exactly one final
+ * one, of 0..interval frames; their concatenation is, bit for bit and in length, what q3t_generate_queue returns for the
+ * utterance (the EOS frame excluded); a delivery that is not the utterance's first and does not complete it has exactly
+ * `interval` frames.  A delivery is made one tick late (a final one a frame late), so the device keeps running during
+ * the callback.  A cancelled utterance gets no further delivery, n_frames[u] = the frames it was handed, and its slot
+ * is refilled like a finished one; the other utterances' codes do not change (sampling is keyed by the utterance index).
+ * After an abort the call returns Q3T_OK with every n_frames[u] = the frames handed out.
+ * codes may be NULL: the per-utterance device copies (n_utt x max_len x 64 bytes) and the end-of-call copy are skipped.
+ * cb == NULL or interval <= 0: Q3T_ERR (use q3t_generate_queue).
+ * The callback runs on the caller's thread while the call holds its device lock.  It may call q3t_vocoder_stream_push,
+ * q3t_vocoder_stream_push_batch, q3t_vocoder_stream_reset and q3t_vocoder_decode on the same context, under the rule
+ * stated for q3t_generate_stream: they run behind the frames already queued; the callback must not start a
+ * one-utterance generate on another context of the same device, and a wait in it for another thread's work on the same
+ * device can be delayed up to 20 ms by a one-utterance generate queued meanwhile (devlock.h). */
+typedef int (*q3t_queue_cb)(void *user, int32_t n, const int32_t *utt, const int32_t *const *codes,
+                            const int32_t *n_frames, const int32_t *final, int32_t *stop);
+int q3t_generate_queue_stream(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens, const int32_t *n_tokens,
+                              const float *const *speaker, const q3t_gen_params *p, int32_t *codes /* may be NULL */,
+                              int32_t *n_frames, int32_t max_active, q3t_queue_cb cb, void *user, int32_t interval);
 /* tuning knob (process-wide): batches of >= min_batch slots run the projections on the matrix cores (MFMA GEMM,
  * gemm_mfma.hip) instead of the weight-streaming GEMV; 0 disables the matrix-core path.  Default 4 (env
  * Q3T_MFMA_MIN_B).  Applies to graphs captured afterwards (create contexts after changing it). */
@@ -191,6 +217,11 @@ int64_t q3t_vocoder_stream_samples(const q3t_voc_stream *s); /* emitted so far *
 int32_t q3t_vocoder_stream_frames(const q3t_voc_stream *s);  /* pushed so far */
 int32_t q3t_vocoder_stream_halo(const q3t_voc_stream *s);    /* frames of left context the convolution stack re-runs */
 void q3t_vocoder_stream_close(q3t_voc_stream *s);
+/* rewind an open stream to zero frames and zero samples, keeping its caches (and the carried tails and halos, which a
+ * push reads only as far as the frame count reaches): the pushes after a reset give, bit for bit, the PCM of a fresh
+ * stream.  A serving loop keeps one stream per slot instead of opening and closing one per utterance (which allocates
+ * and frees the per-layer K/V caches and synchronises the device).  Q3T_ERR: a null or closed stream. */
+int q3t_vocoder_stream_reset(q3t_voc_stream *s);
 
 /* One push on each of n_streams streams through shared launches, for batched serving.  All streams belong to one
  * context; they may stand at any positions and take any mix of n_frames.  codes[j]: [n_frames[j]][16]; pcm[j]: capacity

@@ -14,6 +14,12 @@
 //                        --serve --batch: one stream per request, every interval's frames pushed as one batch
 //   --batch <n>          --serve decodes up to n queued requests together on the GPU (lock-step slots): requests
 //                        already waiting on stdin when one is read are batched; replies keep request order
+//   --queue <n>          --serve runs the requests through n continuously batched slots (Qwen3TTS::synthesize_queue):
+//                        as many requests as are waiting on stdin (at most 8 n) are queued, a slot is refilled when
+//                        its request ends, and each reply (and WAV) is written when its request finishes, so replies
+//                        may come out of request order; each carries its output path.  Combines with --stream-full
+//                        (one vocoder stream per slot, a callback's frames pushed as one batch).  Takes precedence
+//                        over --batch
 #include <poll.h>
 #include <unistd.h>
 
@@ -48,6 +54,8 @@ void print_usage(const char *program) {
     fprintf(stderr, "  --stream-full <n>      Decode every n generated frames with the streaming whole-utterance vocoder\n");
     fprintf(stderr, "                         (with --serve --batch: the requests of a batch in shared launches)\n");
     fprintf(stderr, "  --batch <n>            Server mode: decode up to n queued requests together (default: 1)\n");
+    fprintf(stderr, "  --queue <n>            Server mode: run the waiting requests (up to 8n) through n continuously batched\n");
+    fprintf(stderr, "                         slots; a reply is written when its request ends (replies may be out of order)\n");
     fprintf(stderr, "  -h, --help             Show this help\n");
     fprintf(stderr, "\n");
     fprintf(stderr, "Example:\n");
@@ -159,14 +167,14 @@ void reply(const qwen3_tts::tts_result &result, const Request &q) {
 }
 
 int run_server(qwen3_tts::Qwen3TTS &tts, const std::vector<float> &speaker_embd, const std::string &reference_audio,
-               const qwen3_tts::tts_params &params, int batch) {   // main.cpp:109-163
+               const qwen3_tts::tts_params &params, int batch, int queue) {   // main.cpp:109-163
     fprintf(stderr, "\nServer ready. Send: text<TAB>output.wav  (or 'quit' to exit)\n");
     fflush(stderr);
     bool quit = false;
     for (;;) {
         std::vector<Request> reqs(1);
         if (!read_request(reqs[0], quit)) break;
-        while ((int)reqs.size() < batch && !quit && stdin_ready()) {
+        while ((int)reqs.size() < (queue > 0 ? 8 * queue : batch) && !quit && stdin_ready()) {
             Request r;
             if (!read_request(r, quit)) break;
             reqs.push_back(r);
@@ -174,6 +182,12 @@ int run_server(qwen3_tts::Qwen3TTS &tts, const std::vector<float> &speaker_embd,
         for (const Request &q : reqs) fprintf(stderr, "Synthesizing: \"%s\" -> %s\n", q.text.c_str(), q.output.c_str());
         if (reqs.size() == 1 || (speaker_embd.empty() && !reference_audio.empty())) {
             for (const Request &q : reqs) reply(synthesize_one(tts, q.text, speaker_embd, reference_audio, params), q);
+        } else if (queue > 0) {   // each reply when its request ends
+            std::vector<std::string> texts;
+            for (const Request &q : reqs) texts.push_back(q.text);
+            std::vector<std::vector<float>> spk;
+            if (!speaker_embd.empty()) spk.assign(reqs.size(), speaker_embd);
+            tts.synthesize_queue(texts, spk, params, [&](int32_t i, const qwen3_tts::tts_result &r) { reply(r, reqs[i]); });
         } else {
             std::vector<std::string> texts;
             for (const Request &q : reqs) texts.push_back(q.text);
@@ -193,7 +207,7 @@ int run_server(qwen3_tts::Qwen3TTS &tts, const std::vector<float> &speaker_embd,
 int main(int argc, char **argv) {
     std::string model_dir, text, output_file = "output.wav", reference_audio, embedding_file;
     bool serve_mode = false;
-    int device = 0, batch = 1, vocoder_chunk = -1, stream_full = 0;
+    int device = 0, batch = 1, queue = 0, vocoder_chunk = -1, stream_full = 0;
     unsigned long long seed = 0;
     qwen3_tts::tts_params params;
     auto need = [&](int &i, const char *what) -> const char * {
@@ -225,6 +239,7 @@ int main(int argc, char **argv) {
             else if (arg == "--stream-full") { if (!(v = need(i, "stream-full interval"))) return 1; stream_full = std::stoi(v); }
             else if (arg == "--vocoder-chunk") { if (!(v = need(i, "vocoder-chunk value"))) return 1; vocoder_chunk = std::stoi(v); }
             else if (arg == "--batch") { if (!(v = need(i, "batch value"))) return 1; batch = std::max(1, std::stoi(v)); }
+            else if (arg == "--queue") { if (!(v = need(i, "queue value"))) return 1; queue = std::max(1, std::stoi(v)); }
             else {
                 fprintf(stderr, "Error: unknown argument: %s\n", arg.c_str());
                 print_usage(argv[0]);
@@ -250,6 +265,7 @@ int main(int argc, char **argv) {
     tts.set_seed(seed);
     if (vocoder_chunk >= 0) tts.set_vocoder_chunk(vocoder_chunk);
     if (stream_full > 0) tts.set_stream_full(stream_full);
+    if (queue > 0) tts.set_queue_slots(queue);
     fprintf(stderr, "Loading models from: %s\n", model_dir.c_str());
     if (!tts.load_models(model_dir)) {
         fprintf(stderr, "Error: %s\n", tts.get_error().c_str());
@@ -259,7 +275,7 @@ int main(int argc, char **argv) {
     std::vector<float> speaker_embd;
     if (embedding_file.empty() && !reference_audio.empty()) embedding_file = reference_audio + ".embd";
     if (!embedding_file.empty() && !resolve_embedding(tts, embedding_file, reference_audio, speaker_embd)) return 1;
-    if (serve_mode) return run_server(tts, speaker_embd, reference_audio, params, batch);
+    if (serve_mode) return run_server(tts, speaker_embd, reference_audio, params, batch, queue);
     fprintf(stderr, "Synthesizing: \"%s\"\n", text.c_str());
     if (!reference_audio.empty() && speaker_embd.empty()) fprintf(stderr, "Reference audio: %s\n", reference_audio.c_str());
     const qwen3_tts::tts_result result = synthesize_one(tts, text, speaker_embd, reference_audio, params);

@@ -100,6 +100,7 @@ bool file_exists(const std::string &p) {
 
 constexpr int32_t kPrefillLen = 10;   // prefill rows with a speaker row (tts_transformer.cpp:1093-1231)
 constexpr int32_t kSampleRate = 24000;
+constexpr int32_t kQueueTick = 12;   // synthesize_queue without a stream interval: frames per delivery tick
 
 struct StreamState {
     q3t_ctx *ctx = nullptr;
@@ -218,6 +219,135 @@ int batch_full_stream_cb(void *user, int32_t utt, const int32_t *codes, int32_t 
     q.codes.assign(codes, codes + (size_t)n_frames * 16);
     s->pending.push_back(std::move(q));
     return 1;
+}
+
+// synthesize_queue: the deliveries of q3t_generate_queue_stream.  With a stream interval every running utterance
+// holds one vocoder stream of a pool that never grows past the slots in use (reset, not reopened, when the next
+// utterance takes it) and a callback's pieces go through ONE q3t_vocoder_stream_push_batch; without it the codes are
+// kept and decoded at the utterance's final delivery.  The result is handed out at that delivery.
+struct QueueSynthState {
+    q3t_ctx *ctx = nullptr;
+    bool stream_full = false;
+    int32_t vocoder_chunk = 0, max_len = 0;
+    int64_t t0 = 0;
+    std::vector<tts_result> *out = nullptr;
+    std::vector<char> reported;
+    std::vector<int32_t> n_frames;                  // per utterance, as delivered
+    std::vector<double> decode_ms;                  // per utterance: its share of the pushes, or its whole decode
+    std::vector<std::vector<int32_t>> codes;        // per utterance (no stream interval)
+    std::vector<q3t_voc_stream *> pool, free_list;  // every stream opened; those no utterance holds
+    std::vector<q3t_voc_stream *> mine;             // per utterance
+    const std::function<void(int32_t, const tts_result &)> *on_result = nullptr;
+    std::string error_msg;
+
+    ~QueueSynthState() {
+        for (q3t_voc_stream *v : pool) q3t_vocoder_stream_close(v);
+    }
+    void report(int32_t u, bool ok, const std::string &msg) {
+        tts_result &r = (*out)[u];
+        r.success = ok;
+        r.error_msg = msg;
+        if (!ok) r.audio.clear();
+        r.sample_rate = kSampleRate;
+        r.t_total_ms = now_ms() - t0;
+        r.t_decode_ms = u < (int32_t)decode_ms.size() ? (int64_t)(decode_ms[u] + 0.5) : 0;
+        r.t_generate_ms = std::max<int64_t>(r.t_total_ms - r.t_decode_ms, 0);   // includes the wait for a slot
+        reported[u] = 1;
+        if (on_result && *on_result) (*on_result)(u, r);
+    }
+    // the pool: one stream per slot, opened before the queue starts (an open allocates the K/V caches and
+    // synchronises the device: not something to do between two frames)
+    bool open_pool(int32_t slots) {
+        for (int32_t i = 0; i < slots; ++i) {
+            q3t_voc_stream *v = nullptr;
+            if (q3t_vocoder_stream_open(ctx, max_len, &v) != Q3T_OK) return false;
+            pool.push_back(v);
+            free_list.push_back(v);
+        }
+        return true;
+    }
+    bool take_stream(int32_t u) {   // at most `slots` utterances run at a time, so the pool never runs dry
+        if (free_list.empty()) { error_msg = "more utterances in flight than vocoder streams in the pool"; return false; }
+        mine[u] = free_list.back();
+        free_list.pop_back();
+        if (q3t_vocoder_stream_reset(mine[u]) == Q3T_OK) return true;
+        error_msg = "Failed to reset the vocoder stream: " + q3t_error();
+        return false;
+    }
+    bool decode_whole(int32_t u) {
+        tts_result &r = (*out)[u];
+        const int32_t nf = n_frames[u];
+        int64_t got = 0;
+        int rc;
+        if (vocoder_chunk > 0) {
+            r.audio.resize((size_t)nf * 1920);
+            rc = q3t_vocoder_decode_chunked(ctx, codes[u].data(), nf, 16, vocoder_chunk, r.audio.data(), &got);
+        } else {
+            r.audio.resize((size_t)std::max<int64_t>(q3t_vocoder_num_samples(ctx, nf, Q3T_VOCODER_FULL), 0));
+            rc = q3t_vocoder_decode(ctx, codes[u].data(), nf, Q3T_VOCODER_FULL, r.audio.data(), &got);
+        }
+        if (rc != Q3T_OK) return false;
+        r.audio.resize((size_t)got);
+        return true;
+    }
+    // one callback: false aborts the queue (error_msg set)
+    bool deliver(int32_t n, const int32_t *utt, const int32_t *const *cp, const int32_t *nf, const int32_t *fin) {
+        const int64_t td = now_ms();
+        std::vector<q3t_voc_stream *> st;
+        std::vector<const int32_t *> pc;
+        std::vector<int32_t> pn, pu;
+        std::vector<float *> pp;
+        std::vector<int64_t> cap;
+        std::vector<size_t> at;
+        for (int32_t i = 0; i < n; ++i) {
+            const int32_t u = utt[i];
+            if (u < 0 || u >= (int32_t)out->size() || reported[u]) { error_msg = "unexpected delivery from the queue"; return false; }
+            if (nf[i] <= 0) continue;
+            n_frames[u] += nf[i];
+            if (!stream_full) { codes[u].insert(codes[u].end(), cp[i], cp[i] + (size_t)nf[i] * 16); continue; }
+            if (!mine[u] && !take_stream(u)) return false;
+            const int64_t total = q3t_vocoder_num_samples(ctx, q3t_vocoder_stream_frames(mine[u]) + nf[i], Q3T_VOCODER_FULL);
+            const int64_t c = total - q3t_vocoder_stream_samples(mine[u]);
+            if (total < 0 || c < 0) { error_msg = "bad sample count of a vocoder stream"; return false; }
+            std::vector<float> &a = (*out)[u].audio;
+            at.push_back(a.size());
+            a.resize(a.size() + (size_t)c);
+            st.push_back(mine[u]); pc.push_back(cp[i]); pn.push_back(nf[i]); pu.push_back(u); cap.push_back(c);
+            pp.push_back(a.data() + at.back());   // one piece per utterance and callback: no later resize moves it
+        }
+        if (!st.empty()) {
+            std::vector<int64_t> got(st.size(), 0);
+            const int rc = q3t_vocoder_stream_push_batch(st.data(), (int32_t)st.size(), pc.data(), pn.data(), pp.data(),
+                                                         cap.data(), got.data());
+            for (size_t j = 0; j < st.size(); ++j) (*out)[pu[j]].audio.resize(at[j] + (size_t)(rc == Q3T_OK ? got[j] : 0));
+            if (rc != Q3T_OK) { error_msg = "Vocoder stream decode failed: " + q3t_error(); return false; }
+        }
+        // the batched push serves all its pieces at once: its time is split over them by their frames
+        const double push_ms = (double)(now_ms() - td);
+        int64_t pushed = 0;
+        for (int32_t f : pn) pushed += f;
+        for (size_t j = 0; j < pu.size(); ++j) decode_ms[pu[j]] += push_ms * pn[j] / (double)pushed;
+        for (int32_t i = 0; i < n; ++i) {
+            if (!fin[i]) continue;
+            const int32_t u = utt[i];
+            if (mine[u]) { free_list.push_back(mine[u]); mine[u] = nullptr; }
+            if (n_frames[u] == 0) { report(u, false, "No speech codes generated"); continue; }
+            if (!stream_full) {
+                const int64_t t = now_ms();
+                const bool ok = decode_whole(u);
+                decode_ms[u] += (double)(now_ms() - t);
+                if (!ok) { report(u, false, "Failed to decode speech codes: " + q3t_error()); continue; }
+                std::vector<int32_t>().swap(codes[u]);
+            }
+            report(u, true, "");
+        }
+        return true;
+    }
+};
+
+int queue_synth_cb(void *user, int32_t n, const int32_t *utt, const int32_t *const *codes, const int32_t *n_frames,
+                   const int32_t *final, int32_t * /*stop*/) {
+    return static_cast<QueueSynthState *>(user)->deliver(n, utt, codes, n_frames, final) ? 1 : 0;
 }
 
 }  // namespace
@@ -553,6 +683,67 @@ std::vector<tts_result> Qwen3TTS::synthesize_batch(const std::vector<std::string
     const int64_t total = now_ms() - t0;
     for (auto &r : out) r.t_total_ms = total;
     return out;
+}
+
+std::vector<tts_result> Qwen3TTS::synthesize_queue(const std::vector<std::string> &texts,
+                                                   const std::vector<std::vector<float>> &speaker_embeddings,
+                                                   const tts_params &params,
+                                                   const std::function<void(int32_t, const tts_result &)> &on_result) {
+    const int32_t n = (int32_t)texts.size();
+    std::vector<tts_result> out(n);
+    QueueSynthState qs;
+    qs.out = &out;
+    qs.on_result = &on_result;
+    qs.reported.assign(n, 0);
+    qs.t0 = now_ms();
+    auto fail_rest = [&](const std::string &m) {   // every utterance not handed out yet ends with the error
+        for (int32_t i = 0; i < n; ++i)
+            if (!qs.reported[i]) qs.report(i, false, m);
+        return out;
+    };
+    if (!models_loaded_) return fail_rest("Models not loaded");
+    if (n == 0) return out;
+    if (!speaker_embeddings.empty() && (int32_t)speaker_embeddings.size() != n)
+        return fail_rest("speaker_embeddings must be empty or hold one entry per text");
+    std::vector<std::vector<int32_t>> toks(n);
+    std::vector<const int32_t *> tp(n);
+    std::vector<int32_t> nt(n), nf(n);
+    const std::vector<float> zero(hidden_, 0.0f);
+    std::vector<const float *> spk(n);
+    for (int32_t i = 0; i < n; ++i) {
+        const int64_t t = now_ms();
+        toks[i] = tokenizer_.encode_for_tts(texts[i]);
+        out[i].t_tokenize_ms = now_ms() - t;
+        if (toks[i].empty()) return fail_rest("Failed to tokenize text");
+        tp[i] = toks[i].data();
+        nt[i] = (int32_t)toks[i].size();
+        spk[i] = speaker_embeddings.empty() || speaker_embeddings[i].empty() ? zero.data() : speaker_embeddings[i].data();
+    }
+    const int32_t max_len = std::max(params.max_audio_tokens, 1);
+    const int32_t slots = std::min(n, std::max(queue_slots_, 1));
+    if (!ensure_slots(slots, max_len)) return fail_rest("Failed to generate speech codes: " + error_msg_);
+    q3t_gen_params p;
+    q3t_default_params(&p);
+    p.max_len = max_len;
+    p.repetition_penalty = params.repetition_penalty;
+    p.temperature = params.temperature;
+    p.top_k = params.top_k;
+    p.seed = seed_;
+    qs.ctx = ctx_;
+    qs.stream_full = stream_full_ > 0 && vocoder_chunk_ <= 0;
+    qs.vocoder_chunk = vocoder_chunk_;
+    qs.max_len = max_len;
+    qs.n_frames.assign(n, 0);
+    qs.codes.assign(n, {});
+    qs.mine.assign(n, nullptr);
+    qs.decode_ms.assign(n, 0.0);
+    if (qs.stream_full && !qs.open_pool(slots)) return fail_rest("Failed to open the vocoder stream: " + q3t_error());
+    // the context may hold more slots than this queue uses (it only grows): max_active keeps it to `slots`
+    const int rc = q3t_generate_queue_stream(ctx_, n, tp.data(), nt.data(), spk.data(), &p, nullptr, nf.data(), slots,
+                                             queue_synth_cb, &qs, qs.stream_full ? stream_full_ : kQueueTick);
+    if (rc != Q3T_OK) return fail_rest("Failed to generate speech codes: " + q3t_error());
+    if (!qs.error_msg.empty()) return fail_rest(qs.error_msg);
+    return fail_rest("the queue ended without the utterance's final delivery");   // none is left after a clean run
 }
 
 // ======================================================================================================= audio

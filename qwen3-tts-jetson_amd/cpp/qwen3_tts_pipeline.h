@@ -4,6 +4,8 @@
 #ifndef QWEN3_TTS_PIPELINE_H
 #define QWEN3_TTS_PIPELINE_H
 
+#include <functional>
+
 #include "qwen3_tts_hip.h"
 
 namespace qwen3_tts {
@@ -78,6 +80,23 @@ public:
                                              const std::vector<std::vector<float>> &speaker_embeddings,
                                              const tts_params &params = tts_params());
 
+    // Continuous batching (q3t_generate_queue_stream): any number of texts through set_queue_slots(n) slots, a slot
+    // refilled with the next text when its utterance ends.  on_result(index, result) fires at the utterance's final
+    // delivery, while the others still run, so results come in completion order; the returned vector holds them in
+    // text order.  With set_stream_full(n) every running utterance holds one vocoder stream of a pool of one per slot,
+    // opened before the queue starts (reset when the next utterance takes it), and each delivery callback makes one
+    // q3t_vocoder_stream_push_batch over its pieces; without it an utterance is decoded whole (or in
+    // vocoder_chunk() chunks) at its final delivery.  The audio equals synthesize_with_embedding's vocoder output of
+    // the queue's codes.  t_decode_ms is the utterance's share (by frames) of the batched pushes, or its own decode;
+    // t_generate_ms the rest of its time since the call began, the wait for a slot included.  An error ends the
+    // queue: every utterance not handed out yet gets the message.
+    void set_queue_slots(int32_t slots) { queue_slots_ = slots; }
+    int32_t queue_slots() const { return queue_slots_; }
+    std::vector<tts_result> synthesize_queue(const std::vector<std::string> &texts,
+                                             const std::vector<std::vector<float>> &speaker_embeddings,
+                                             const tts_params &params = tts_params(),
+                                             const std::function<void(int32_t, const tts_result &)> &on_result = nullptr);
+
 private:
     tts_result synthesize_internal(const std::string &text, const float *speaker_embedding, const tts_params &params,
                                    tts_result &result);
@@ -90,6 +109,7 @@ private:
     int32_t slots_ = 0, n_ctx_ = 0, hidden_ = 1024;
     int32_t vocoder_chunk_ = 0;
     int32_t stream_full_ = 0;
+    int32_t queue_slots_ = 1;
     bool models_loaded_ = false;
     std::string error_msg_;
     std::string tts_model_path_;

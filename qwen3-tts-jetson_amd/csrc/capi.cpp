@@ -208,6 +208,20 @@ int q3t_generate_queue(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens, co
     GUARD_END
 }
 
+int q3t_generate_queue_stream(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens, const int32_t *n_tokens,
+                              const float *const *speaker, const q3t_gen_params *p, int32_t *codes, int32_t *n_frames,
+                              int32_t max_active, q3t_queue_cb cb, void *user, int32_t interval) {
+    GUARD_BEGIN
+    CHECK_CTX(ctx);
+    CHECK_TALKER(ctx);
+    if (!cb) { q3t::set_error("q3t_generate_queue_stream: null callback (use q3t_generate_queue)"); return Q3T_ERR; }
+    if (interval <= 0) { q3t::set_error("q3t_generate_queue_stream: interval must be > 0 (use q3t_generate_queue)"); return Q3T_ERR; }
+    if (n_utt < 0 || (n_utt > 0 && (!tokens || !n_tokens || !n_frames))) { q3t::set_error("null argument"); return Q3T_ERR; }
+    return ctx->engine.generate_queue(n_utt, tokens, n_tokens, speaker, to_gp(p), codes, n_frames, max_active, cb, user, interval)
+               ? Q3T_OK : Q3T_ERR;
+    GUARD_END
+}
+
 int q3t_synchronize(q3t_ctx *ctx) {
     GUARD_BEGIN
     CHECK_CTX(ctx);
@@ -371,6 +385,15 @@ int q3t_vocoder_stream_push_batch(q3t_voc_stream *const *streams, int32_t n_stre
     q3t::DeviceLock lk(false, first->device);   // never beside a persistent grid (devlock.h)
     return first->owner->stream_push_batch(n_streams, reinterpret_cast<q3t::Vocoder::Stream *const *>(streams), codes, n_frames,
                                            pcm, pcm_cap, n_samples) ? Q3T_OK : Q3T_ERR;
+    GUARD_END
+}
+
+int q3t_vocoder_stream_reset(q3t_voc_stream *s) {
+    GUARD_BEGIN
+    if (!s) { q3t::set_error("null vocoder stream"); return Q3T_ERR; }
+    q3t::Vocoder::Stream *st = vst(s);
+    q3t::DeviceLock lk(false, st->device);   // as a push: the decoder's stream list is read under the lock
+    return st->owner->stream_reset(st) ? Q3T_OK : Q3T_ERR;
     GUARD_END
 }
 

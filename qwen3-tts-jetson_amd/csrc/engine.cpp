@@ -2,6 +2,7 @@
 #include "engine.h"
 #include "persist.h"
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -86,6 +87,7 @@ Engine::~Engine() {
     voc_.reset();
     for (void *p : allocs_) hipFree(p);
     if (qout_) hipFree(qout_);
+    if (qstage_) hipFree(qstage_);
     if (pin_) hipHostFree(pin_);
     for (PinnedChunk &c : chunk_pool_) { hipHostFree(c.codes); hipEventDestroy(c.ev); }
     if (stream_) hipStreamDestroy(stream_);
@@ -128,6 +130,29 @@ bool Engine::ensure_qout(size_t bytes) {
     qout_cap_ = 0;
     if (hipMalloc(&qout_, bytes) != hipSuccess) { qout_ = nullptr; set_error("device allocation failed"); return false; }
     qout_cap_ = bytes;
+    return true;
+}
+bool Engine::ensure_qstage(size_t bytes) {
+    if (bytes <= qstage_cap_) return true;
+    if (qstage_) hipFree(qstage_);
+    qstage_ = nullptr;
+    qstage_cap_ = 0;
+    if (hipMalloc(&qstage_, bytes) != hipSuccess) { qstage_ = nullptr; set_error("device allocation failed"); return false; }
+    qstage_cap_ = bytes;
+    return true;
+}
+bool Engine::pinned_chunk(size_t idx, size_t bytes, PinnedChunk **out) {
+    while (chunk_pool_.size() <= idx) chunk_pool_.push_back(PinnedChunk{});
+    PinnedChunk &pc = chunk_pool_[idx];
+    if (pc.cap < bytes) {
+        if (pc.codes) hipHostFree(pc.codes);
+        pc.codes = nullptr;
+        pc.cap = 0;
+        Q3T_HIP(hipHostMalloc(&pc.codes, bytes, hipHostMallocDefault));
+        pc.cap = bytes;
+    }
+    if (!pc.ev) Q3T_HIP(hipEventCreateWithFlags(&pc.ev, hipEventDisableTiming));
+    *out = &pc;
     return true;
 }
 
@@ -1801,8 +1826,10 @@ bool Engine::alloc_admission() {
     if (!ensure_prefill()) return false;
     ahidden_ = dalloc<float>((size_t)S * H);
     alogits_ = dalloc<float>((size_t)S * c_.codec_vocab);
+    delivered_ = dalloc<int>(S);
+    qmask_ = dalloc<int>(S);
     if (!alloc_prompt_scratch(adm_ps_, nullptr)) return false;
-    if (!ahidden_ || !alogits_) { set_error("device allocation failed"); return false; }
+    if (!ahidden_ || !alogits_ || !delivered_ || !qmask_) { set_error("device allocation failed"); return false; }
     // every buffer was zeroed on stream_ and drained by dalloc before the admission stream exists
     Q3T_HIP(hipStreamCreateWithFlags(&astream_, hipStreamNonBlocking));
     return true;
@@ -1838,7 +1865,8 @@ bool Engine::admit_batch(const std::vector<int> &tgt, const std::vector<int> &ut
 // slot k joins the frame loop (main stream, between two frames, after its admission batch): per-slot state, the
 // last prefill step's hidden state, and the CB0 of its first frame selected from the last prefill logits.
 // state_h: pinned [8]
-bool Engine::activate_slot(int k, uint64_t utt, int trailing_len, int n_tok, const GenParams &gp, int plen, int *state_h) {
+bool Engine::activate_slot(int k, uint64_t utt, int trailing_len, int n_tok, const GenParams &gp, int plen, int *state_h,
+                           bool deliveries) {
     const int H = c_.hidden, NCB = 16;
     state_h[0] = trailing_len; state_h[1] = n_tok; state_h[2] = gp.force_frames; state_h[3] = -1;
     state_h[4] = plen; state_h[5] = 0;
@@ -1852,6 +1880,7 @@ bool Engine::activate_slot(int k, uint64_t utt, int trailing_len, int n_tok, con
     Q3T_HIP(hipMemcpyAsync(hidden_ + (size_t)k * H, ahidden_ + (size_t)k * H, H * 4, hipMemcpyDeviceToDevice, stream_));
     Q3T_HIP(hipMemcpyAsync(pos_ + k, state_h + 4, 4, hipMemcpyHostToDevice, stream_));
     Q3T_HIP(hipMemcpyAsync(frame_ + k, state_h + 5, 4, hipMemcpyHostToDevice, stream_));
+    if (deliveries) Q3T_HIP(hipMemsetAsync(delivered_ + k, 0, 4, stream_));   // queue deliveries: nothing collected yet
     Q3T_HIP(hipMemcpyAsync(done_ + k, state_h + 3, 4, hipMemcpyHostToDevice, stream_));
     SelectSpec sp = select_spec(SEL_CB0, gp_, 0, 0);   // the slot's rows of every per-slot array
     sp.tokens += (size_t)k * 16; sp.codes += (size_t)k * codes_max_len_ * NCB; sp.frame += k; sp.done += k; sp.utt += k;
@@ -1860,8 +1889,114 @@ bool Engine::activate_slot(int k, uint64_t utt, int trailing_len, int n_tok, con
     return select_tokens(sp, alogits_ + (size_t)k * c_.codec_vocab, 1, stream_);
 }
 
+// Deliveries of generate_queue() (DESIGN 2f "Queue deliveries").  A collection is ONE k_queue_collect launch over the
+// slots of a mask, one copy of the staging chunk (rows, header, error word) into a pinned chunk of the context's pool
+// and one event.  The device keeps each slot's collected-frames counter, so the host uploads the mask and nothing
+// else.  Chunks are delivered in stream order, a tick's chunk one tick late and a finish chunk one frame late, so
+// the GPU runs the queued frames during the callback; each is handed out only once the persistent kernels behind it
+// are known to be fault-free.
+class Engine::QueueStreamer {
+public:
+    QueueStreamer(Engine &e, int S, int n_utt, int max_len, QueueCb cb, void *user, int interval, QueueState &st, bool *fault)
+        : e_(e), S_(S), max_len_(max_len), interval_(interval), cb_(cb), user_(user), st_(st), fault_(fault),
+          run_(n_utt) {}
+    bool active() const { return cb_ != nullptr; }
+    int interval() const { return interval_; }
+    bool begin() {   // the staging chunk with a clear error word
+        if (!e_.ensure_qstage(stage_ints() * 4)) return false;
+        Q3T_HIP(hipMemsetAsync(static_cast<int *>(e_.qstage_) + stage_ints() - 1, 0, 4, e_.stream_));
+        return true;
+    }
+    // one collection over the slots k with sel[k] != 0 (slot_utt[k]: the slot's utterance), queued behind what the
+    // stream holds; its chunk is due when the loop clock reaches `due`
+    bool collect(const std::vector<int> &slot_utt, const std::vector<char> &sel, bool final, int due) {
+        Chunk c;
+        if (!pool_.empty()) { c = pool_.back(); pool_.pop_back(); }
+        else {
+            PinnedChunk *pc = nullptr;   // rows [S][interval][16], header [S], error word, then the mask's source [S]
+            if (!e_.pinned_chunk(next_chunk_++, (stage_ints() + S_) * 4, &pc)) return false;
+            c.rows = pc->codes;
+            c.ev = pc->ev;
+        }
+        c.final = final;
+        c.due = due;
+        c.utt.assign(S_, -1);
+        int *mask = c.rows + stage_ints();
+        for (int k = 0; k < S_; ++k) {
+            mask[k] = sel[k] ? 1 : 0;
+            if (sel[k]) c.utt[k] = slot_utt[k];
+        }
+        int32_t *stage = static_cast<int32_t *>(e_.qstage_);
+        Q3T_HIP(hipMemcpyAsync(e_.qmask_, mask, S_ * 4, hipMemcpyHostToDevice, e_.stream_));
+        QueueCollect q;
+        q.mask = e_.qmask_; q.done = e_.done_; q.frame = e_.frame_; q.delivered = e_.delivered_;
+        q.codes = e_.codes_;
+        q.rows = stage;
+        q.header = stage + (size_t)S_ * interval_ * NCB;
+        q.error = stage + stage_ints() - 1;
+        q.interval = interval_; q.codes_max_len = e_.codes_max_len_; q.max_len = max_len_;
+        if (!queue_collect(q, S_, e_.stream_)) return false;
+        Q3T_HIP(hipMemcpyAsync(c.rows, stage, stage_ints() * 4, hipMemcpyDeviceToHost, e_.stream_));
+        Q3T_HIP(hipEventRecord(c.ev, e_.stream_));
+        pend_.push_back(c);
+        return true;
+    }
+    // the pending chunks up to the last one due at loop clock f, oldest first
+    bool deliver_due(int f) {
+        size_t n = 0;
+        for (size_t i = 0; i < pend_.size(); ++i)
+            if (pend_[i].due <= f) n = i + 1;
+        for (size_t i = 0; i < n && !st_.aborted; ++i) {
+            Chunk c = pend_.front();
+            pend_.erase(pend_.begin());
+            pool_.push_back(c);
+            if (!deliver(c)) { hipStreamSynchronize(e_.stream_); return false; }
+        }
+        return true;
+    }
+    bool flush() { return deliver_due(INT_MAX); }
+    // utterances the callback cancelled since the last call (their slots are still running)
+    std::vector<int> take_stops() { std::vector<int> s; s.swap(stops_); return s; }
+
+private:
+    static constexpr int NCB = 16;
+    struct Chunk { int32_t *rows = nullptr; hipEvent_t ev = nullptr; bool final = false; int due = 0; std::vector<int> utt; };
+    size_t stage_ints() const { return (size_t)S_ * interval_ * NCB + S_ + 1; }
+    bool deliver(const Chunk &c) {
+        Q3T_HIP(hipEventSynchronize(c.ev));
+        if (e_.persist_error()) { *fault_ = true; return false; }
+        const int *hdr = c.rows + (size_t)S_ * interval_ * NCB;
+        if (hdr[S_] != 0) { set_error("generate_queue: a collection was out of step with its slot"); return false; }
+        // (a fallback re-run generates every utterance again: queue_deliver.h keeps what was handed out apart)
+        std::vector<QueueEntry> ent;
+        queue_plan(hdr, c.utt, c.final, st_, run_, ent, stops_);
+        if (ent.empty()) return true;
+        const size_t m = ent.size();
+        std::vector<int32_t> utt(m), nf(m), fin(m), stop(m, 0);
+        std::vector<const int32_t *> cp(m);
+        for (size_t i = 0; i < m; ++i) {
+            utt[i] = ent[i].utt; nf[i] = ent[i].n; fin[i] = ent[i].final;
+            cp[i] = c.rows + ((size_t)ent[i].slot * interval_ + ent[i].skip) * NCB;
+        }
+        const int go = cb_(user_, (int32_t)m, utt.data(), cp.data(), nf.data(), fin.data(), stop.data());
+        queue_commit(ent, stop.data(), go != 0, st_, run_, stops_);
+        return true;
+    }
+    Engine &e_;
+    const int S_, max_len_, interval_;
+    const QueueCb cb_;
+    void *const user_;
+    QueueState &st_;
+    bool *const fault_;
+    QueueRun run_;                    // this run's per-utterance progress (queue_deliver.h)
+    std::vector<int> stops_;          // utterances to cancel: their slots may still be running
+    size_t next_chunk_ = 0;           // chunk_pool_[0, next_chunk_) are in use by this call
+    std::vector<Chunk> pend_, pool_;  // collections in flight, oldest first; chunks delivered and free for reuse
+};
+
 bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
-                                 const GenParams &gp, int32_t *codes, int *n_frames, int max_active, bool *faulted) {
+                                 const GenParams &gp, int32_t *codes, int *n_frames, int max_active, bool *faulted,
+                                 QueueCb on_batch, void *user, int interval, QueueState &qst) {
     *faulted = false;
     if (n_utt <= 0) return true;
     const int S = std::min(max_slots_, n_utt), NCB = 16;
@@ -1878,8 +2013,13 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
     set_gen_params(gp);
     if (!set_seed(gp.seed, stream_)) return false;
     // the finished utterances' codes, copied to the caller once at the end (device scratch kept by the context)
-    if (!ensure_qout((size_t)n_utt * gp.max_len * NCB * 4)) return false;
-    int32_t *out_dev = static_cast<int32_t *>(qout_);
+    // (a caller that takes deliveries may pass no codes buffer: nothing is parked then)
+    if (codes && !ensure_qout((size_t)n_utt * gp.max_len * NCB * 4)) return false;
+    int32_t *out_dev = codes ? static_cast<int32_t *>(qout_) : nullptr;
+    QueueStreamer qs(*this, S, n_utt, gp.max_len, on_batch, user, interval, qst, faulted);
+    if (qs.active() && !qs.begin()) return false;
+    if (qs.active() && out_dev)   // an aborted call copies out rows of utterances that never ran
+        Q3T_HIP(hipMemsetAsync(out_dev, 0, (size_t)n_utt * gp.max_len * NCB * 4, stream_));
     // [S][8] activation staging, [S] done flags, [S] admission targets, one constant 0 (parking): pinned, kept
     if (!ensure_pinned(((size_t)S * 10 + 1) * 4)) return false;
     int *pin = static_cast<int *>(pin_);
@@ -1933,7 +2073,7 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         if (as != stream_) Q3T_HIP(hipStreamWaitEvent(stream_, aev, 0));
         for (int k : batch_tgt) {
             const int u = slot_utt[k];
-            if (!activate_slot(k, (uint64_t)u, tl[k], n_tokens[u], gp, plen, pin + (size_t)k * 8)) return false;
+            if (!activate_slot(k, (uint64_t)u, tl[k], n_tokens[u], gp, plen, pin + (size_t)k * 8, qs.active())) return false;
             state[k] = ACTIVE;
             started[k] = f;
         }
@@ -1954,11 +2094,41 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         *g = g_frame_[se + 65536 * S];
         return true;
     };
+    // an utterance leaves its slot (ended, or cancelled by the delivery callback): its codes are parked for the
+    // end-of-call copy and the slot is free for the next admission
+    auto release = [&](int k, bool park_slot) -> bool {
+        const int u = slot_utt[k];
+        if (out_dev)
+            Q3T_HIP(hipMemcpyAsync(out_dev + (size_t)u * gp.max_len * NCB, codes_ + (size_t)k * codes_max_len_ * NCB,
+                                   (size_t)gp.max_len * NCB * 4, hipMemcpyDeviceToDevice, stream_));
+        if (park_slot)   // still running: park the slot (no selection, no advance)
+            Q3T_HIP(hipMemcpyAsync(done_ + k, park, 4, hipMemcpyHostToDevice, stream_));
+        state[k] = FREE;
+        slot_utt[k] = -1;
+        --n_busy;
+        ++n_fin;
+        return true;
+    };
+    // the chunks due at loop clock `due`, then the slots of the utterances their callbacks cancelled
+    auto deliver = [&](int due) -> bool {
+        if (!qs.deliver_due(due)) return false;
+        for (int u : qs.take_stops()) {
+            for (int k = 0; k < S; ++k)
+                if (state[k] == ACTIVE && slot_utt[k] == u && !release(k, true)) return false;
+            // its length is what it was handed, also when it had ended (and left its slot) before the piece the
+            // callback cancelled it at was delivered
+            n_frames[u] = qst.delivered[u];
+        }
+        return true;
+    };
+    std::vector<char> sel(S, 0);
     bool polled = false;   // one frame in flight: frame f is launched before frame f-1's done flags are read
-    while (n_fin < n_utt) {
+    while (n_fin < n_utt && !qst.aborted) {
         int n_active = 0;
         for (int k = 0; k < S; ++k) n_active += state[k] == ACTIVE;
         if (n_active == 0) {   // only an admission in flight: wait for it instead of running empty frames
+            if (qs.active() && !deliver(INT_MAX)) return false;   // nothing runs behind them: hand out what is pending
+            if (qst.aborted) break;
             if (batch_tgt.empty() && !admit()) return false;
             Q3T_HIP(hipEventSynchronize(aev));
             if (!activate()) return false;
@@ -1970,23 +2140,31 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         if (!persist_fault_hook(S, (persist_ ? 1 : 0) + (persist_cp_ ? 1 : 0))) return false;
         Q3T_HIP(hipGraphLaunch(fg, stream_));
         ++f;
+        if (qs.active()) {
+            // a tick: the new frames of every active slot, behind this frame's graph; then the chunks due by now (the
+            // previous tick's, and the finish chunks of the previous frame)
+            if (f % qs.interval() == 0) {
+                for (int k = 0; k < S; ++k) sel[k] = state[k] == ACTIVE;
+                if (!qs.collect(slot_utt, sel, false, f + qs.interval())) return false;
+            }
+            if (!deliver(f)) return false;
+            if (qst.aborted) break;
+        }
         if (polled) {
             Q3T_HIP(hipEventSynchronize(pev));
+            bool any = false;
             for (int k = 0; k < S; ++k) {   // done_h: after frame f-1
-                if (state[k] != ACTIVE) continue;
                 const int ran = f - 1 - started[k];
+                sel[k] = state[k] == ACTIVE && !(done_h[k] < 0 && ran < gp.max_len);
+                any = any || sel[k];
+            }
+            // the rest of the finished slots' frames, before a slot is parked or handed to a successor
+            if (qs.active() && any && !qs.collect(slot_utt, sel, true, f + 1)) return false;
+            for (int k = 0; k < S; ++k) {
+                if (!sel[k]) continue;
                 const int d = done_h[k];
-                if (d < 0 && ran < gp.max_len) continue;
-                const int u = slot_utt[k];
-                n_frames[u] = d >= 0 ? std::min(d, gp.max_len) : gp.max_len;
-                Q3T_HIP(hipMemcpyAsync(out_dev + (size_t)u * gp.max_len * NCB, codes_ + (size_t)k * codes_max_len_ * NCB,
-                                       (size_t)gp.max_len * NCB * 4, hipMemcpyDeviceToDevice, stream_));
-                if (d < 0)   // stopped at max_len: park the slot (no selection, no advance)
-                    Q3T_HIP(hipMemcpyAsync(done_ + k, park, 4, hipMemcpyHostToDevice, stream_));
-                state[k] = FREE;
-                slot_utt[k] = -1;
-                --n_busy;
-                ++n_fin;
+                n_frames[slot_utt[k]] = d >= 0 ? std::min(d, gp.max_len) : gp.max_len;
+                if (!release(k, d < 0)) return false;   // d < 0: stopped at max_len
             }
         }
         if (!batch_tgt.empty() && (as == stream_ || hipEventQuery(aev) == hipSuccess) && !activate()) return false;
@@ -1997,25 +2175,48 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         polled = true;
         if (f > (n_utt + 1) * (gp.max_len + plen + 2)) { set_error("generate_queue: no progress"); return false; }
     }
-    for (int u = 0; u < n_utt; ++u)
-        Q3T_HIP(hipMemcpyAsync(codes + (size_t)u * gp.max_len * NCB, out_dev + (size_t)u * gp.max_len * NCB,
-                               (size_t)gp.max_len * NCB * 4, hipMemcpyDeviceToHost, stream_));
+    if (qs.active()) {
+        if (!qst.aborted && !qs.flush()) return false;   // the last finish chunks
+        if (qst.aborted) {   // the callback ended the call: every utterance is as long as what it was handed
+            for (int k = 0; k < S; ++k)
+                if (state[k] == ACTIVE && !release(k, false)) return false;
+            for (int u = 0; u < n_utt; ++u) n_frames[u] = qst.delivered[u];
+        } else {
+            for (int u = 0; u < n_utt; ++u)
+                if (qst.stopped[u]) n_frames[u] = qst.delivered[u];   // (a re-run: cancelled before the fault)
+            for (int u = 0; u < n_utt; ++u)
+                if (!(qst.stopped[u] || (qst.finaled[u] && qst.delivered[u] == n_frames[u]))) {
+                    set_error("generate_queue: utterance " + std::to_string(u) + " ended without its final delivery");
+                    return false;
+                }
+        }
+    }
+    if (codes)
+        for (int u = 0; u < n_utt; ++u)
+            Q3T_HIP(hipMemcpyAsync(codes + (size_t)u * gp.max_len * NCB, out_dev + (size_t)u * gp.max_len * NCB,
+                                   (size_t)gp.max_len * NCB * 4, hipMemcpyDeviceToHost, stream_));
     Q3T_HIP(hipStreamSynchronize(stream_));
     if (persist_error()) { set_error("persistent kernel: an in-launch hand-off timed out"); *faulted = true; return false; }
     return true;
 }
 
 bool Engine::generate_queue(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
-                            const GenParams &gp, int32_t *codes, int *n_frames, int max_active) {
+                            const GenParams &gp, int32_t *codes, int *n_frames, int max_active, QueueCb on_batch, void *user,
+                            int interval) {
+    if (!on_batch && !codes && n_utt > 0) { set_error("generate_queue: no codes buffer and no callback"); return false; }
+    if (on_batch && interval <= 0) { set_error("generate_queue: the delivery interval must be > 0"); return false; }
     const int S = std::min(max_slots_, std::max(n_utt, 1));
     DeviceLock lk(persist_exclusive(S), device_);
+    QueueState qst(std::max(n_utt, 0));
     bool fault = false;
-    if (generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, codes, n_frames, max_active, &fault)) return true;
+    if (generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, codes, n_frames, max_active, &fault, on_batch, user, interval, qst))
+        return true;
     if (!fault) return false;
     // a single-slot persistent launch gave up on a hand-off: continue on the launch-per-op graphs, which are
-    // bit-identical, and re-run the queue (sampling is keyed by utterance, so the re-run gives the same codes)
+    // bit-identical, and re-run the queue (sampling is keyed by utterance, so the re-run gives the same codes; what
+    // was delivered, cancelled or finished before the fault is kept in qst and not delivered again)
     if (!persist_recover()) return false;
-    return generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, codes, n_frames, max_active, &fault);
+    return generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, codes, n_frames, max_active, &fault, on_batch, user, interval, qst);
 }
 
 bool Engine::time_stage(int stage, int S, int pos, int iters, double *ms) {

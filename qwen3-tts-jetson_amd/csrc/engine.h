@@ -11,6 +11,7 @@
 #include "arena.h"
 #include "gguf.h"
 #include "kernels.h"
+#include "queue_deliver.h"
 
 namespace q3t {
 
@@ -157,8 +158,18 @@ public:
     // index in the call (utt id), so an utterance's codes do not depend on its slot, its admission frame or the
     // other utterances in flight (the S-slot decode step never mixes tokens); on the matrix-core path (>= 4 slots) the
     // admission prefill runs the batch's kernels for its one slot, so the first wave's codes equal generate()'s.
+    // on_batch (q3t_queue_cb) with interval > 0: the queue hands frames out while it runs (DESIGN 2f "Queue
+    // deliveries").  Every `interval` frames of the loop clock one collection launch gathers the new frames of all
+    // active slots (a tick); when a slot's utterance ends, one more gathers the rest of the finished slots and is
+    // marked final.  One callback per collection: n entries in increasing utterance index, codes[i] -> [n_frames[i]][16]
+    // valid during the call, final[i] on the utterance's last delivery; stop[i] set non-zero cancels utterance utt[i]
+    // (its slot is parked, freed and refilled; n_frames[u] = the frames delivered); returning 0 aborts the call
+    // (n_frames = the frames delivered).  With a callback codes may be null: no per-utterance device copy is kept.
+    typedef int (*QueueCb)(void *user, int32_t n, const int32_t *utt, const int32_t *const *codes, const int32_t *n_frames,
+                           const int32_t *final, int32_t *stop);
     bool generate_queue(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
-                        const GenParams &gp, int32_t *codes, int *n_frames, int max_active);
+                        const GenParams &gp, int32_t *codes, int *n_frames, int max_active, QueueCb on_batch = nullptr,
+                        void *user = nullptr, int interval = 0);
     // fill this context's weight arenas (laid out with recv_weights) from another context's, device to device
     bool copy_weights_from(Engine &src);
     // after the weight arenas of a receiving context were filled by a broadcast: build what is derived from the weights
@@ -219,15 +230,19 @@ private:
     bool generate_once(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                        const GenParams &gp, int32_t *codes, int *n_frames, FrameCb on_frames, void *user, int interval,
                        StreamState &st, bool *fault);
+    class QueueStreamer;   // the queue callback's collections and deliveries (engine.cpp)
     bool generate_queue_once(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
-                             const GenParams &gp, int32_t *codes, int *n_frames, int max_active, bool *faulted);
+                             const GenParams &gp, int32_t *codes, int *n_frames, int max_active, bool *faulted,
+                             QueueCb on_batch, void *user, int interval, QueueState &qst);
     // host scratch kept across calls (a per-call hipFree / hipHostFree synchronises the whole device)
     struct PinnedChunk { size_t cap = 0; int32_t *codes = nullptr; hipEvent_t ev = nullptr; };
-    std::vector<PinnedChunk> chunk_pool_;   // streaming chunks of generate()
-    void *pin_ = nullptr, *qout_ = nullptr;
-    size_t pin_cap_ = 0, qout_cap_ = 0;
+    std::vector<PinnedChunk> chunk_pool_;   // streaming chunks of generate() and of the queue's deliveries
+    bool pinned_chunk(size_t idx, size_t bytes, PinnedChunk **out);   // chunk_pool_[idx], grown to bytes, with its event
+    void *pin_ = nullptr, *qout_ = nullptr, *qstage_ = nullptr;
+    size_t pin_cap_ = 0, qout_cap_ = 0, qstage_cap_ = 0;
     bool ensure_pinned(size_t bytes);
     bool ensure_qout(size_t bytes);
+    bool ensure_qstage(size_t bytes);   // the queue deliveries' device staging chunk [S][interval][16] + header [S] + error word
     bool enqueue_talker_step(int S, hipStream_t s);
     bool enqueue_talker(int S, hipStream_t s, bool gather_input, bool select_next, bool prenormed = false,
                         bool *fold_advance = nullptr);
@@ -284,8 +299,10 @@ private:
     bool admit_batch(const std::vector<int> &tgt, const std::vector<int> &utt, const int32_t *const *tokens,
                      const int *n_tokens, const float *const *speaker, const GenParams &gp, int plen, hipStream_t as,
                      int *tgt_h, std::vector<int> &trailing_len);
-    bool activate_slot(int slot, uint64_t utt, int trailing_len, int n_tok, const GenParams &gp, int plen, int *state_h);
+    bool activate_slot(int slot, uint64_t utt, int trailing_len, int n_tok, const GenParams &gp, int plen, int *state_h,
+                       bool deliveries = false);
     hipStream_t astream_ = nullptr;
+    int *delivered_ = nullptr, *qmask_ = nullptr;   // queue deliveries: per-slot frames collected so far; a collection's slot mask
     float *ahidden_ = nullptr, *alogits_ = nullptr;
     int q_slots_ = 0;            // slot count of the running queue (the batch the admissions reproduce)
 

@@ -181,6 +181,21 @@ constexpr int ATTN_MAX_SPLITS = 160;   // n_ctx <= 10240
 // pos[s]++, frame[s]++
 bool advance(int *pos, int *frame, const int *done, int S, hipStream_t s);   // done: slots with done >= 0 stay (may be null)
 
+// Queue deliveries: one launch over slots [0, S).  For every slot k with mask[k] != 0: avail = the slot's complete
+// frames (done[k] >= 0 ? min(done[k], max_len) : min(frame[k], max_len)), n = avail - delivered[k]; rows
+// [delivered[k], avail) of codes [S][codes_max_len][16] go to rows [k][0, n) of the staging chunk [S][interval][16],
+// header[k] = n, delivered[k] = avail.  A slot with mask[k] == 0 is not touched (rows, header entry, counter).
+// n outside [0, interval] (or a negative counter): *error = 1, header[k] = 0, nothing copied, counter unchanged.
+struct QueueCollect {
+    const int *mask, *done, *frame;
+    int *delivered;
+    const int32_t *codes;
+    int32_t *rows;
+    int *header, *error;
+    int interval, codes_max_len, max_len;
+};
+bool queue_collect(const QueueCollect &q, int S, hipStream_t s);
+
 // *out = t[0] + t[1] + t[2] (f32 rows or f16 table rows; null terms skipped); recipe built on the host
 struct RowTerm { const void *ptr; int is_f16; };
 struct RowRecipe { float *out; RowTerm t[3]; };

@@ -78,6 +78,33 @@ bool advance(int *pos, int *frame, const int *done, int S, hipStream_t s) {
     return true;
 }
 
+// One workgroup (one wave) per slot.  A slot's complete frames: the EOS frame index once it ended (select_commit sets
+// done to the frame whose CB0 was EOS, and that frame is not part of the utterance), otherwise the frame counter,
+// which k_advance and the fused advance of k_tkb / k_cpb raise only after all 16 codes of the frame are written.
+// The header entry and the counter are written after every lane has read the counter (one wave: program order).
+__global__ void __launch_bounds__(64) k_queue_collect(const QueueCollect q) {
+    const int k = blockIdx.x;
+    if (!q.mask[k]) return;
+    const int done = q.done[k], delivered = q.delivered[k];
+    const int avail = min(done >= 0 ? done : q.frame[k], q.max_len);
+    const int n = avail - delivered;
+    if (delivered < 0 || n < 0 || n > q.interval) {   // never expected: nothing is copied, the host sees the word
+        if (threadIdx.x == 0) { *q.error = 1; q.header[k] = 0; }
+        return;
+    }
+    const int4 *src = reinterpret_cast<const int4 *>(q.codes + ((size_t)k * q.codes_max_len + delivered) * 16);
+    int4 *dst = reinterpret_cast<int4 *>(q.rows + (size_t)k * q.interval * 16);
+    for (int i = threadIdx.x; i < n * 4; i += 64) dst[i] = src[i];   // a row is 4 x 16 bytes
+    if (threadIdx.x == 0) { q.header[k] = n; q.delivered[k] = avail; }
+}
+bool queue_collect(const QueueCollect &q, int S, hipStream_t s) {
+    if (S <= 0) return true;
+    if (q.interval <= 0 || q.max_len < 0 || q.max_len > q.codes_max_len) { set_error("queue_collect: bad shape"); return false; }
+    hipLaunchKernelGGL(k_queue_collect, dim3(S), dim3(64), 0, s, q);
+    Q3T_HIP(hipGetLastError());
+    return true;
+}
+
 __global__ void k_rows_recipe(const RowRecipe *rec, int H) {
     const RowRecipe R = rec[blockIdx.x];
     for (int h = threadIdx.x; h < H; h += blockDim.x) {

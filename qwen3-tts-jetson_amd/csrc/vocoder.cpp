@@ -826,6 +826,14 @@ void Vocoder::stream_close(Stream *st) {
     delete st;
 }
 
+bool Vocoder::stream_reset(Stream *st) {
+    if (!st || std::find(streams_.begin(), streams_.end(), st) == streams_.end()) { set_error("vocoder stream: not an open stream"); return false; }
+    // pushes synchronise before they return, so nothing in flight reads the counters
+    st->frames = 0;
+    st->samples = 0;
+    return true;
+}
+
 bool Vocoder::stream_push(Stream *st, const int32_t *codes, int n, float *pcm, int64_t pcm_cap, int64_t *n_out) {
     if (n_out) *n_out = 0;
     if (!st || std::find(streams_.begin(), streams_.end(), st) == streams_.end()) { set_error("vocoder stream: not an open stream"); return false; }

@@ -64,6 +64,10 @@ public:
     // Bad arguments (n_frames <= 0, more than max_frames in total, pcm_cap too small) fail before any state changes
     bool stream_push(Stream *st, const int32_t *codes_host, int n_frames, float *pcm_host, int64_t pcm_cap, int64_t *n_out);
     void stream_close(Stream *st);
+    // back to zero frames and zero samples, keeping the caches: every carried row a push reads is bounded by the
+    // frame count (cache rows [0, frames), min(2, frames) tail rows, min(halo, frames) halo rows), so nothing of the
+    // previous utterance reaches the next one and the pushes after a reset are bit for bit a fresh stream's
+    bool stream_reset(Stream *st);
     // One push on each of n_streams streams of this decoder (any mix of positions and sizes) through shared launches:
     // the row-wise stages run once over the packed new rows of all streams, the per-layer append and attention are one
     // launch each for all streams (voc_kv_append_batch / voc_attn_cached_batch), and pre_conv and the convolution

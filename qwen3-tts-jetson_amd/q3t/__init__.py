@@ -58,6 +58,10 @@ _lib.q3t_generate_queue.argtypes = [_P, _I, C.POINTER(C.POINTER(C.c_int32)), _ip
 FRAME_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32)
 _lib.q3t_generate_stream.argtypes = [_P, _I, C.POINTER(C.POINTER(C.c_int32)), _ip, C.POINTER(C.POINTER(C.c_float)),
                                      C.POINTER(GenParams), _ip, _ip, FRAME_CB, C.c_void_p, C.c_int32]
+QUEUE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_int32)),
+                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32))
+_lib.q3t_generate_queue_stream.argtypes = [_P, _I, C.POINTER(C.POINTER(C.c_int32)), _ip, C.POINTER(C.POINTER(C.c_float)),
+                                           C.POINTER(GenParams), _P, _ip, C.c_int32, QUEUE_CB, C.c_void_p, C.c_int32]
 COMM_ID_BYTES = 128
 _lib.q3t_comm_unique_id.argtypes = [C.c_char_p]
 _lib.q3t_ctx_create_shared.argtypes = [C.c_char_p, C.c_char_p, _I, _I, _I, _I, _I, C.c_char_p, C.POINTER(_P)]
@@ -92,6 +96,7 @@ _lib.q3t_vocoder_stream_frames.restype = C.c_int32
 _lib.q3t_vocoder_stream_frames.argtypes = [_P]
 _lib.q3t_vocoder_stream_halo.restype = C.c_int32
 _lib.q3t_vocoder_stream_halo.argtypes = [_P]
+_lib.q3t_vocoder_stream_reset.argtypes = [_P]
 _lib.q3t_vocoder_stream_close.restype = None
 _lib.q3t_vocoder_stream_close.argtypes = [_P]
 _lib.q3t_speaker_dim.argtypes = [_P]
@@ -113,12 +118,12 @@ _lib.q3t_prefill_embd.argtypes = [_P, _ip, _I, _P, _I, _fp, C.POINTER(C.c_int32)
 
 # names the C ABI must export (checked by tests without a GPU)
 EXPORTS = ["q3t_last_error", "q3t_default_params", "q3t_ctx_create", "q3t_ctx_destroy", "q3t_get_config",
-           "q3t_generate", "q3t_generate_stream", "q3t_generate_queue", "q3t_comm_unique_id", "q3t_ctx_create_shared",
+           "q3t_generate", "q3t_generate_stream", "q3t_generate_queue", "q3t_generate_queue_stream", "q3t_comm_unique_id", "q3t_ctx_create_shared",
            "q3t_plan_weight_layout", "q3t_ctx_create_replica", "q3t_comm_allreduce_max", "q3t_set_mfma_min_batch", "q3t_synchronize", "q3t_last_timing", "q3t_time_stage", "q3t_persist_status", "q3t_persist_kernels", "q3t_vocoder_num_samples", "q3t_vocoder_flops", "q3t_vocoder_decode",
            "q3t_vocoder_decode_chunked", "q3t_vocoder_decode_batch", "q3t_vocoder_set_batch_frames",
            "q3t_vocoder_stream_open", "q3t_vocoder_stream_push", "q3t_vocoder_stream_push_batch",
            "q3t_vocoder_stream_last_groups", "q3t_vocoder_stream_samples",
-           "q3t_vocoder_stream_frames", "q3t_vocoder_stream_halo", "q3t_vocoder_stream_close", "q3t_speaker_dim", "q3t_ctx_create_speaker", "q3t_speaker_encode", "q3t_speaker_mel",
+           "q3t_vocoder_stream_frames", "q3t_vocoder_stream_halo", "q3t_vocoder_stream_close", "q3t_vocoder_stream_reset", "q3t_speaker_dim", "q3t_ctx_create_speaker", "q3t_speaker_encode", "q3t_speaker_mel",
            "q3t_tokenizer_load", "q3t_tokenizer_free", "q3t_tokenizer_info", "q3t_tokenizer_encode",
            "q3t_tokenizer_decode", "q3t_talker_forward", "q3t_talker_prefill",
            "q3t_codepred_frame", "q3t_cb0_select", "q3t_project_text", "q3t_prefill_embd", "gpu_fp32_to_fp16",
@@ -237,6 +242,10 @@ class VocoderStream:
         ns = C.c_int64(0)
         _check(_lib.q3t_vocoder_stream_push(h, _addr(codes), n, _addr(pcm), cap, C.byref(ns)))
         return pcm[:ns.value]
+
+    def reset(self):
+        """back to zero frames and zero samples, keeping the caches: the next pushes equal a fresh stream's"""
+        _check(_lib.q3t_vocoder_stream_reset(self._handle()))
 
     @property
     def frames(self):
@@ -397,6 +406,65 @@ class Engine:
         del sp
         if errors:
             raise errors[0]
+        return [codes[i, :nf[i]].copy() for i in range(n)]
+
+    def generate_queue_stream(self, prompts, on_batch, interval=12, speakers=None, max_active=0, want_codes=True,
+                              **params):
+        """generate_queue() that hands frames out while it runs (q3t_generate_queue_stream).  on_batch(entries) is
+        called once per tick (every `interval` frames of the queue's loop) or finish with a list of
+        (utt, codes [n][16] int32, final); it returns None or True to continue, an iterable of utterance indices to
+        cancel, or False to abort the call.  Per utterance the pieces arrive in order, concatenate to generate_queue's
+        codes, and exactly one is final.  Returns the codes like generate_queue() (a cancelled utterance: the frames
+        it was handed), or with want_codes=False (no code buffers kept) the list of frame counts."""
+        if not callable(on_batch):
+            raise TypeError("generate_queue_stream: on_batch must be callable (use generate_queue without one)")
+        if isinstance(interval, bool) or not isinstance(interval, (int, np.integer)) or interval <= 0:
+            raise ValueError("generate_queue_stream: interval must be an integer > 0")
+        if speakers is not None and len(speakers) != len(prompts):
+            raise ValueError("generate_queue_stream: one speaker embedding per prompt, or none")
+        p = default_params(**params)
+        n = len(prompts)
+        toks = [np.ascontiguousarray(t, np.int32) for t in prompts]
+        tarr = (C.POINTER(C.c_int32) * n)(*[t.ctypes.data_as(C.POINTER(C.c_int32)) for t in toks])
+        ntok = np.array([len(t) for t in toks], np.int32)
+        sarr = None
+        sp = []
+        if speakers is not None:
+            sp = [np.ascontiguousarray(s, np.float32) for s in speakers]
+            sarr = (C.POINTER(C.c_float) * n)(*[s.ctypes.data_as(C.POINTER(C.c_float)) for s in sp])
+        codes = np.zeros((n, p.max_len, 16), np.int32) if want_codes else None
+        nf = np.zeros(n, np.int32)
+        errors = []
+
+        def _cb(_user, m, utt, cptr, nfr, fin, stop):
+            try:
+                entries = []
+                for i in range(m):
+                    k = int(nfr[i])
+                    arr = (np.ctypeslib.as_array(cptr[i], shape=(k * 16,)).reshape(k, 16).copy() if k > 0
+                           else np.zeros((0, 16), np.int32))
+                    entries.append((int(utt[i]), arr, bool(fin[i])))
+                r = on_batch(entries)
+                if r is False:
+                    return 0
+                if r is not None and r is not True:
+                    where = {int(utt[i]): i for i in range(m)}
+                    for u in r:
+                        if int(u) in where:
+                            stop[where[int(u)]] = 1
+                return 1
+            except Exception as e:  # never let an exception unwind through the C frames
+                errors.append(e)
+                return 0
+
+        cb = QUEUE_CB(_cb)
+        _check(_lib.q3t_generate_queue_stream(self.h, n, tarr, ntok, sarr, C.byref(p), _addr(codes) if want_codes else None,
+                                              nf, int(max_active), cb, None, int(interval)))
+        del sp
+        if errors:
+            raise errors[0]
+        if not want_codes:
+            return [int(x) for x in nf]
         return [codes[i, :nf[i]].copy() for i in range(n)]
 
     def synchronize(self):

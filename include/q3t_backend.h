@@ -166,6 +166,12 @@ int q3t_persist_status(q3t_ctx *ctx);
  * 4 = code-predictor frame on role-specialised workgroups (persist_cp.hip), 8 = code-predictor frame on all-role
  * workgroups (persist.hip k_persist<1|2,16>) */
 int q3t_persist_kernels(q3t_ctx *ctx);
+/* which kernels a frame loop of n_slots slots launches on this context: 0 = the weight-streaming vector kernels (one
+ * slot: as persistent launches where q3t_persist_kernels says so), 1 = the launch-per-op matrix-core stack (MFMA GEMMs,
+ * hoisted norms, batched attention), 2 = the batched persistent launches (code-predictor frame and / or talker step).
+ * Q3T_ERR for n_slots outside [1, max_slots].  A model with code_pred.mtp_proj (1.7B) reports 1 from 4 slots on, or 0 at
+ * every slot count when the context was created under Q3T_MM17=0. */
+int q3t_decode_family(q3t_ctx *ctx, int n_slots);
 
 /* ---- vocoder */
 int64_t q3t_vocoder_num_samples(const q3t_ctx *ctx, int32_t n_frames, int mode);

@@ -272,6 +272,13 @@ int q3t_persist_kernels(q3t_ctx *ctx) {
     return ctx->engine.persist_kernels();
 }
 
+int q3t_decode_family(q3t_ctx *ctx, int n_slots) {
+    if (!ctx || !ctx->engine.has_talker()) return Q3T_ERR;
+    const int f = ctx->engine.decode_family(n_slots);
+    if (f < 0) q3t::set_error("q3t_decode_family: n_slots outside [1, max_slots]");
+    return f < 0 ? Q3T_ERR : f;
+}
+
 int64_t q3t_vocoder_num_samples(const q3t_ctx *ctx, int32_t n_frames, int mode) {
     if (!ctx) return -1;
     q3t::Vocoder *v = const_cast<q3t::Engine &>(ctx->engine).vocoder();

@@ -62,6 +62,9 @@ Options Options::from_env() {
     o.fused_select = env_flag("Q3T_FUSED_SELECT", true);
     o.defer_cp_select = env_flag("Q3T_CP_DEFER_SELECT", true);
     o.attn_split = env_flag("Q3T_ATTN_SPLIT", false);
+    // models with code_pred.mtp_proj (1.7B) on the batched matrix-core stack; 0: every projection of such a model on the
+    // vector kernels with a 1-slot K split at any batch size, as before the stack covered them
+    o.mm17 = env_flag("Q3T_MM17", true);
     // weight prefetch of the batched talker stack: 0 off (default), 1 the norms before QKV and gate/up, 2 also the gate/up
     // GEMM for the down projection (its 64-token tiles leave a quarter of the CUs free).  Off since round 5: level 2 saved
     // 0.3 % of the 64-slot step (1.5960 -> 1.5912 ms, two A/B pairs) for 755 MB more fabric reads per step (FETCH 3,111 ->
@@ -209,9 +212,19 @@ bool Engine::parse_config(const Gguf &g) {
     if (cp_head_dim != c_.head_dim) { set_error("code predictor head_dim must equal the talker's (shared RoPE table)"); return false; }
     cpc_ = c_;
     cpc_.hidden = c_.cp_hidden; cpc_.inter = c_.cp_inter; cpc_.n_heads = c_.cp_heads; cpc_.n_kv = c_.cp_kv;
-    // the batched matrix-core stack (hoisted norms, k_resid_norm) is built for widths <= 1024 and the 0.6B layout;
-    // other models (1.7B) run every projection on the vector kernels with a 1-slot K split at any batch size
-    mm_ok_ = !c_.has_mtp && c_.hidden <= 1024 && c_.cp_hidden <= 1024;
+    // the batched matrix-core stack (hoisted norms, k_resid_norm): widths <= 1024 without code_pred.mtp_proj (0.6B); with
+    // it (1.7B) a talker up to 2,048 wide over a code predictor up to 1,024 wide whose every projection is a shape of
+    // the MFMA GEMM (Q3T_MM17=0: off).  Other models run every projection on the vector kernels with a 1-slot K split
+    // at any batch size.
+    auto mm_stack_shapes = [](const Config &k, int head_vocab) {
+        auto kdim = [](int K) { return K == 256 || K == 512 || K == 1024 || K == 2048 || K == 3072; };
+        const int A = k.n_heads * k.head_dim, QKV = (k.n_heads + 2 * k.n_kv) * k.head_dim;
+        // (K of QKV / gate-up / head, of the O projection, of the down projection -- slabs only at 6,144; N in 32-row tiles)
+        return kdim(k.hidden) && kdim(A) && (kdim(k.inter) || k.inter == 6144) && QKV % 32 == 0 && head_vocab % 32 == 0;
+    };
+    mm_ok_ = c_.has_mtp ? opt_.mm17 && c_.hidden <= 2048 && c_.cp_hidden <= 1024 && mm_stack_shapes(c_, c_.codec_vocab) &&
+                              mm_stack_shapes(cpc_, c_.cp_vocab)
+                        : c_.hidden <= 1024 && c_.cp_hidden <= 1024;
     fam1_ = mm_ok_ ? 0 : 1;
     if (c_.n_codebooks != 16) { set_error("n_codebooks must be 16"); return false; }
     // the fused code-predictor attention prologue is specialised to the 0.6B head layout (16 q / 8 kv heads x 128)
@@ -447,6 +460,7 @@ bool Engine::alloc_state() {
     hidden_ = dalloc<float>((size_t)S * H);
     cpx_ = dalloc<float>((size_t)S * c_.cp_hidden);
     cp_in1_ = dalloc<float>((size_t)S * H);
+    if (c_.has_mtp) mtp_in_ = dalloc<uint16_t>((size_t)S * H);
     cp_logits_ = dalloc<float>((size_t)S * c_.cp_vocab);
     // (the code-predictor stack runs attn_decode on these too: sized for the wider of the two head layouts)
     part_ = dalloc<float>((size_t)S * std::max(c_.n_heads, c_.cp_heads) * talker_cache().max_splits * (D + 2));
@@ -649,7 +663,8 @@ bool Engine::build_persist_tables() {
     if (tables_built_) return true;
     const bool qkv_shapes = opt_.cp_qkv_table && c_.codec_vocab == 3072 && c_.cp_vocab == 2048 && (int)cp_embd_.size() >= 14 &&
                             cpc_.hidden == 1024 && (int)CP_.size() >= 1;
-    const bool want_proj = persist_cp_ && c_.has_mtp;
+    // (1.7B on the matrix-core stack: the selection hand-offs of passes 1..15 read the projected rows)
+    const bool want_proj = c_.has_mtp && (persist_cp_ || (mm_ok_ && max_slots_ > 1));
     const bool want_qkv = qkv_shapes && (persist_cp_ || (opt_.mm_cp_table && mm_ok_ && max_slots_ > 1));
     if (!want_proj && !want_qkv) { tables_built_ = true; return true; }
     struct stat st{};
@@ -1157,6 +1172,14 @@ bool Engine::cp_project(int S, const float *x_talker, int ldx, hipStream_t s) {
     g.pro = PRO_F32; g.x = x_talker; g.ldx = ldx;
     g.bias = mtp_b_;
     g.out_f32 = cpx_; g.ldo = c_.cp_hidden; g.family_b = fam1_;
+    if (use_mm(S)) {
+        // matrix-core family: one PRO_F16 GEMM over the f16 of the rows.  Staged in a buffer of its own: the talker's
+        // last resid_norm left the same halves in xn_, which the code predictor's stack is about to reuse (and a
+        // caller of the frame alone only fills hidden_)
+        launch_f32_to_f16(x_talker, mtp_in_, S * c_.hidden, s);
+        Q3T_HIP(hipGetLastError());
+        g.pro = PRO_F16; g.x = mtp_in_; g.family_b = policy_slots_;
+    }
     return gemv(g, s);
 }
 
@@ -1214,6 +1237,15 @@ GatherSum Engine::cp_input_gather(int p) const {
 
 // pass p's input: what layer 0 reads (in0), after the launches that prepare it
 bool Engine::cp_pass_input(int p, int S, bool defer, StackInput &in0, hipStream_t s) {
+    if (c_.has_mtp && use_mm(S)) {
+        // 1.7B on the matrix-core stack: pass 0 projects the talker's rows with one GEMM; the projected input of a pass
+        // p >= 1 is a function of its token alone, the row of cp_projtab_ (built with the 1-slot GEMV, so independent
+        // of the batch) -- gathered here for pass 1 (CB0 was selected by the talker's launch) and by the previous
+        // pass's selection hand-off after it (prenormed)
+        in0.pro = PRO_RMS; in0.x = cpx_;
+        if (p == 0) return cp_project(S, hidden_, c_.hidden, s);
+        return in0.prenormed || gather_rows_f32(cp_projtab_, cp_table_row0(p), tokens_, 16, p - 1, S, c_.cp_hidden, cpx_, s);
+    }
     if (c_.has_mtp) {
         // 1.7B: the pass input (talker hidden / table row, talker space) projected into cpx_ by code_pred.mtp_proj
         // (tts_transformer.cpp:1554-1560, :1709-1714); layer 0 then normalises cpx_ like any later layer
@@ -1248,7 +1280,8 @@ bool Engine::cp_select_handoff(int S, int step, hipStream_t s) {
     EmbedNorm en;
     en.nt = last ? 16 : 1; en.gs = last ? step_embed_gather() : cp_input_gather(step + 2);
     en.x = last ? x_ : cpx_; en.nw = (last ? L_ : CP_)[0].attn_norm;
-    en.xn = xn_; en.eps = c_.eps; en.H = c_.hidden;   // (mm: no projection, code predictor width == talker's)
+    en.xn = xn_; en.eps = c_.eps; en.H = last ? c_.hidden : c_.cp_hidden;
+    if (c_.has_mtp && !last) { en.ftab = cp_projtab_; en.ftab_row0 = cp_table_row0(step + 2); }   // the projected row
     return select_embed_norm(select_spec(SEL_CP, gp_, 0, step), cp_logits_, en, S, s);
 }
 
@@ -1268,7 +1301,7 @@ bool Engine::cp_frame_per_op(int S, hipStream_t s, float *logits_host, bool talk
         // passes 1..15 of the matrix-core stack: layer 0's raw QKV rows from the per-token table (the 0.6B layout; the
         // table's rows are the 1-slot GEMV's, within the batched family's f32 tolerance of its MFMA GEMM)
         StackRun r;
-        if (opt_.mm_cp_table && p >= 1 && cp_qkvtab_ && !c_.has_mtp) {
+        if (opt_.mm_cp_table && p >= 1 && cp_qkvtab_) {
             r.l0tab.qkv_tab = cp_qkvtab_; r.l0tab.tab_tok = tokens_; r.l0tab.tab_ld = 16; r.l0tab.tab_col = p - 1;
             r.l0tab.tab_row0 = cp_table_row0(p);
         }

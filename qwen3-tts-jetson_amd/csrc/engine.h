@@ -94,6 +94,7 @@ struct Options {
     bool cpb = true;            // Q3T_PERSIST_CPB: the batched (2..64-slot) code-predictor frame as one persistent launch
     bool tkb = true;            // Q3T_PERSIST_TKB: the batched (16..64-policy-slot) talker step as one persistent launch
     bool attn_split = false;
+    bool mm17 = true;           // Q3T_MM17: models with code_pred.mtp_proj (1.7B) on the batched matrix-core stack
     int mm_prefetch = 0;        // Q3T_MM_PREFETCH (from_env)
     int mm_gu_tt = 2;           // Q3T_MM_GU_TT: gate/up token tile in 32-token units (from_env)
     unsigned persist_fault_at = 0;
@@ -198,6 +199,12 @@ public:
     bool persist_enabled() const { return persist_ || persist_cp_ || cpb_ || tkb_; }
     int persist_kernels() const {   // q3t_persist_kernels
         return (persist_ ? (tk_roles_ ? 1 : 2) : 0) | (persist_cp_ ? (cp_roles_ && cp_qkvtab_ ? 4 : 8) : 0) | (cpb_ ? 16 : 0) | (tkb_ ? 32 : 0);
+    }
+    // q3t_decode_family: what a frame loop of S slots launches -- 0 the weight-streaming vector kernels (and the one-slot
+    // persistent kernels built on them), 1 the launch-per-op matrix-core stack, 2 the batched persistent launches
+    int decode_family(int S) const {
+        if (S < 1 || S > max_slots_) return -1;
+        return use_cpb(S) || use_tkb(S) ? 2 : use_mm(S) ? 1 : 0;
     }
     // runs with S slots launch a persistent grid (the 1-slot kernels, or the batched code-predictor frame / talker
     // step): they hold the device lock exclusively (devlock.h)
@@ -338,6 +345,7 @@ private:
     unsigned *sel_ticket_ = nullptr;   // fused head+select arrival counters [S]
     uint16_t *attn_ = nullptr, *hmlp_ = nullptr;
     uint16_t *xn_ = nullptr;      // batched path: normalised f16 activations (resid_norm output)
+    uint16_t *mtp_in_ = nullptr;  // batched path, 1.7B: the f16 talker rows code_pred.mtp_proj reads in pass 0
     float *parts_ = nullptr;      // batched path: split-K partial slabs [4][S][H]
     uint16_t *kc_ = nullptr, *vc_ = nullptr, *cpkc_ = nullptr, *cpvc_ = nullptr;
     int *pos_ = nullptr, *frame_ = nullptr, *done_ = nullptr, *token_ = nullptr, *tokens_ = nullptr;

@@ -592,6 +592,7 @@ static int nch_of(int K) {
         case 1024: return 4;
         case 2048: return 8;
         case 3072: return 12;
+        case 6144: return 24;   // (the 1.7B talker's down projection: through split-K slabs only)
         default: return 0;
     }
 }
@@ -601,12 +602,14 @@ bool gemm_mfma_supported(const GemvParams &p) {
     const int nch = nch_of(p.K);
     if (!nch) return false;
     const bool swiglu = p.act == ACT_SWIGLU;
-    if (swiglu && p.pro != PRO_RMS && !(p.pro == PRO_F16 && nch <= 4 && !p.x_idx)) return false;
+    if (swiglu && p.pro != PRO_RMS && !(p.pro == PRO_F16 && (nch <= 4 || nch == 8) && !p.x_idx)) return false;
     if (p.parts) {   // split-K slabs: f16 rows, no epilogue, K slices of 256-multiples
         const int nk = p.ksplit > 0 && nch % p.ksplit == 0 ? nch / p.ksplit : 0;
         if (p.pro != PRO_F16 || swiglu || !(nk == 1 || nk == 2 || nk == 3 || nk == 4 || nk == 8 || nk == 12) ||
             p.N % 4 != 0)
             return false;
+    } else if (nch > 12) {
+        return false;   // no whole-K instantiation holds 24 chunks of weights
     }
     const uintptr_t xa = reinterpret_cast<uintptr_t>(p.x);
     switch (p.pro) {
@@ -664,7 +667,7 @@ static bool launch_f16_sw(const GemvParams &p, hipStream_t s) {
 }
 template <int NCH, int TT>
 static bool launch_f16(const GemvParams &p, hipStream_t s) {
-    if constexpr (NCH <= 4) {
+    if constexpr (NCH <= 4 || NCH == 8) {   // (8: the 1.7B talker's gate / up projection at K = 2,048)
         if (p.act == ACT_SWIGLU) return launch_f16_sw<NCH, TT, true>(p, s);
     }
     return launch_f16_sw<NCH, TT, false>(p, s);

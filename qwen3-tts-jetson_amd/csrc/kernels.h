@@ -66,6 +66,9 @@ struct GatherSum {
 // the GatherSum rows as a plain f32 buffer out[b][0..K) (nt = 1 or 16 table rows; batched path)
 bool gather_sum(const GatherSum &gs, int nt, int S, int K, float *out, int ldo, hipStream_t s);
 
+// out[b][0..H) = tab[row0 + tok[b * tok_ld + col]][0..H): f32 table rows as a plain buffer
+bool gather_rows_f32(const float *tab, size_t row0, const int *tok, int tok_ld, int col, int S, int H, float *out, hipStream_t s);
+
 // PRO_CPATT source: one new token per slot at position pos[b] (< 16) over a 16-position F16 cache
 // (scripts/export_code_predictor.py:132-231 step semantics; 16 q heads / 8 kv heads / D 128 only)
 struct CpAttnSrc {
@@ -122,7 +125,8 @@ struct GemvParams {
 };
 bool gemv(const GemvParams &p, hipStream_t s);   // routes wide batches to gemm_mfma (gemm_mfma.hip)
 // matrix-core path for B >= gemm_mfma_min_batch() tokens (Q3T_MFMA_MIN_B, default 4; 0 = off): F16 / F32 / RMS / LN
-// prologues, K in {256, 512, 1024, 2048, 3072} (norm prologues K <= 1024), N % 32 == 0, no fused selection
+// prologues, K in {256, 512, 1024, 2048, 3072} (norm prologues K <= 1024; K = 6144 as split-K slabs only), N % 32 == 0,
+// no fused selection
 bool gemm_mfma_supported(const GemvParams &p);
 bool gemm_mfma(const GemvParams &p, hipStream_t s);
 int gemm_mfma_min_batch();
@@ -200,7 +204,8 @@ bool queue_collect(const QueueCollect &q, int S, hipStream_t s);
 struct RowTerm { const void *ptr; int is_f16; };
 struct RowRecipe { float *out; RowTerm t[3]; };
 bool rows_recipe(const RowRecipe *recipe_dev, int n_rows, int H, hipStream_t s);
-// batched residual + RMSNorm between the matrix-core projections (one workgroup per token, H <= 1024):
+// batched residual + RMSNorm between the matrix-core projections (one workgroup per token, H <= 2048; rows wider
+// than 1024 take the kernel's two-chunk form, resid_norm_chunks() == 2):
 //   x[b] = xin[b] + parts[0][b] + ... + parts[ksplit-1][b]   (written to x when parts or xin != x)
 //   xn[b] = f16((x[b] * rsqrt(mean(x[b]^2) + eps)) * nw)       (double sums, as the GEMV prologues)
 //   side[b] = the same normalised row in f32 (optional: hidden_states side output)
@@ -220,14 +225,19 @@ struct ResidNorm {
     size_t prefetch_bytes = 0;
 };
 bool resid_norm(const ResidNorm &r, hipStream_t s);
+int resid_norm_chunks(int H);   // 1024-wide chunks per thread of the instantiation resid_norm() launches for H
 
 // batched: the selection launch also prepares the NEXT stage's input (one workgroup per slot): the token selected
 // for slot b, then x[b] = the GatherSum row (nt = 1: the next code-predictor pass; nt = 16: the talker step
 // embedding, the selected token among its 16), then xn[b] = f16(RMSNorm(x[b]) * nw) -- k_gather_sum + k_resid_norm
-// arithmetic, so the fused and the three-launch forms give the same bits
+// arithmetic, so the fused and the three-launch forms give the same bits.  H <= 2048.
+// ftab (nt = 1 only, H <= 1024): the row is the f32 row ftab[ftab_row0 + token] instead of an f16 row of gs.tab0
+// (1.7B: the code predictor's projected pass inputs, Engine::build_cp_proj_table); gs then only names the token.
 struct EmbedNorm {
     GatherSum gs;
     int nt = 0;
+    const float *ftab = nullptr;
+    size_t ftab_row0 = 0;
     float *x = nullptr;
     uint16_t *xn = nullptr;
     const float *nw = nullptr;

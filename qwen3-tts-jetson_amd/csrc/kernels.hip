@@ -191,17 +191,20 @@ void launch_sample_topk_f32(const float *logits, const float *rand_val, int32_t 
 }
 
 // ------------------------------------------------------------------------------------------ batched residual + norm
-// one workgroup per token; thread t owns elements 4t .. 4t+3 (H <= 1024).  Partial slabs are added in slice order;
-// the RMS sum runs in double over the block (gemv.hip / gemm_mfma.hip prologue numerics).  KS (the slab count) is a
-// template argument so the x and slab loads issue back to back: with a runtime count each sat in its own branch and
-// waited for its own round trip.
+// one workgroup per token; thread t owns elements 4t .. 4t+3 of every 1024-wide chunk of the row: W = 1 chunk for
+// H <= 1024 (the 0.6B widths and both code predictors), W = 2 for the 1.7B talker's 2,048 -- the narrow form's
+// arithmetic is that of W = 1 term for term, so its bits do not depend on the wide form existing.  Partial slabs are
+// added in slice order; the RMS sum runs in double over the block (gemv.hip / gemm_mfma.hip prologue numerics), a
+// thread's chunks in ascending order before the wave reduction.  KS (the slab count) is a template argument so the x
+// and slab loads issue back to back: with a runtime count each sat in its own branch and waited for its own round
+// trip.
 // Workgroups past the S token rows only prefetch (ResidNorm::prefetch): global->LDS dword loads, one per 128-B line
 // of the next projection's weights, which leave no register to wait on; the lines land in the Infinity Cache.
 constexpr int RN_PF_LINES = 2;   // prefetched lines per thread
-template <int KS>
+template <int KS, int W>
 __global__ void __launch_bounds__(256) k_resid_norm(const ResidNorm r) {
     __shared__ double scr[4];
-    const int b = blockIdx.x, t = threadIdx.x, k = 4 * t;
+    const int b = blockIdx.x, t = threadIdx.x;
     if (b >= r.S) {
         __shared__ uint32_t sink[256];
         const size_t lines = r.prefetch_bytes / 128, nthr = (size_t)(gridDim.x - r.S) * 256;
@@ -214,36 +217,58 @@ __global__ void __launch_bounds__(256) k_resid_norm(const ResidNorm r) {
         }
         return;
     }
-    const bool ok = k < r.H;
-    const size_t o = (size_t)b * r.H + (ok ? k : 0);
-    float4 x = *reinterpret_cast<const float4 *>((r.xin ? r.xin : r.x) + o);
-    float4 pz[KS > 0 ? KS : 1];
+    bool ok[W];
+    size_t o[W];
+    float4 x[W], pz[W][KS > 0 ? KS : 1];
 #pragma unroll
-    for (int z = 0; z < KS; ++z) pz[z] = *reinterpret_cast<const float4 *>(r.parts + (size_t)z * r.S * r.H + o);
+    for (int i = 0; i < W; ++i) {
+        const int k = 4 * t + 1024 * i;
+        ok[i] = k < r.H;
+        o[i] = (size_t)b * r.H + (ok[i] ? k : 0);
+        x[i] = *reinterpret_cast<const float4 *>((r.xin ? r.xin : r.x) + o[i]);
+    }
 #pragma unroll
-    for (int z = 0; z < KS; ++z) x = make_float4(x.x + pz[z].x, x.y + pz[z].y, x.z + pz[z].z, x.w + pz[z].w);
-    if (!ok) x = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ok && (KS > 0 || (r.xin && r.xin != r.x))) *reinterpret_cast<float4 *>(r.x + o) = x;
-    double ss = (double)(x.x * x.x) + (double)(x.y * x.y) + (double)(x.z * x.z) + (double)(x.w * x.w);
+    for (int i = 0; i < W; ++i)
+#pragma unroll
+        for (int z = 0; z < KS; ++z) pz[i][z] = *reinterpret_cast<const float4 *>(r.parts + (size_t)z * r.S * r.H + o[i]);
+    double ss = 0.0;
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        float4 v = x[i];
+#pragma unroll
+        for (int z = 0; z < KS; ++z) v = make_float4(v.x + pz[i][z].x, v.y + pz[i][z].y, v.z + pz[i][z].z, v.w + pz[i][z].w);
+        if (!ok[i]) v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok[i] && (KS > 0 || (r.xin && r.xin != r.x))) *reinterpret_cast<float4 *>(r.x + o[i]) = v;
+        const double si = (double)(v.x * v.x) + (double)(v.y * v.y) + (double)(v.z * v.z) + (double)(v.w * v.w);
+        ss = i == 0 ? si : ss + si;
+        x[i] = v;
+    }
     ss = wave_sum_d(ss);
     if ((t & 63) == 0) scr[t >> 6] = ss;
     __syncthreads();
     ss = (scr[0] + scr[1]) + (scr[2] + scr[3]);
-    if (!ok) return;
     const float scale = 1.0f / sqrtf((float)(ss / r.H) + r.eps);
-    const float4 w = *reinterpret_cast<const float4 *>(r.nw + k);
-    const float y0 = (x.x * scale) * w.x, y1 = (x.y * scale) * w.y, y2 = (x.z * scale) * w.z, y3 = (x.w * scale) * w.w;
-    if (r.side) *reinterpret_cast<float4 *>(r.side + o) = make_float4(y0, y1, y2, y3);
-    uint2 h;
-    h.x = (uint32_t)f2h(y0) | ((uint32_t)f2h(y1) << 16);
-    h.y = (uint32_t)f2h(y2) | ((uint32_t)f2h(y3) << 16);
-    *reinterpret_cast<uint2 *>(r.xn + o) = h;
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        if (!ok[i]) continue;
+        const float4 v = x[i];
+        const float4 w = *reinterpret_cast<const float4 *>(r.nw + 4 * t + 1024 * i);
+        const float y0 = (v.x * scale) * w.x, y1 = (v.y * scale) * w.y, y2 = (v.z * scale) * w.z, y3 = (v.w * scale) * w.w;
+        if (r.side) *reinterpret_cast<float4 *>(r.side + o[i]) = make_float4(y0, y1, y2, y3);
+        uint2 h;
+        h.x = (uint32_t)f2h(y0) | ((uint32_t)f2h(y1) << 16);
+        h.y = (uint32_t)f2h(y2) | ((uint32_t)f2h(y3) << 16);
+        *reinterpret_cast<uint2 *>(r.xn + o[i]) = h;
+    }
 }
+// W as k_resid_norm's.  F32TAB: the nt = 1 source is an f32 row of EmbedNorm::ftab (the 1.7B code predictor's
+// projected pass inputs) instead of an f16 table row.
+template <int W, bool F32TAB>
 __global__ void __launch_bounds__(256) k_select_embed_norm(const SelectSpec sp, const float *logits, const EmbedNorm en) {
     __shared__ SelLds S;
     __shared__ double scr[4];
     __shared__ int stok;
-    const int b = blockIdx.x, t = threadIdx.x, k = 4 * t;
+    const int b = blockIdx.x, t = threadIdx.x;
     const int tok = select_token<false>(sp, logits + (size_t)b * sp.V, b, S);
     if (t == 0) {
         if (tok >= 0) select_commit(sp, b, tok);
@@ -256,72 +281,133 @@ __global__ void __launch_bounds__(256) k_select_embed_norm(const SelectSpec sp, 
         const int tt = gs.tok[(size_t)b * gs.tok_ld + col];   // loaded unconditionally: no branch around the load
         return col == sel_col && stok >= 0 ? stok : tt;
     };
-    const bool ok = k < en.H;
-    const int kk = ok ? k : 0;
-    float a[4];
-    {
-        const uint16_t *r0 = en.nt == 1 ? gs.tab0 + (size_t)token(gs.tok_col0) * en.H : gs.tabs[0] + (size_t)token(0) * en.H;
-        const uint2 u = *reinterpret_cast<const uint2 *>(r0 + kk);
-        a[0] = h2f(u.x & 0xffff); a[1] = h2f(u.x >> 16); a[2] = h2f(u.y & 0xffff); a[3] = h2f(u.y >> 16);
+    bool ok[W];
+    int kk[W];
+    float a[W][4];
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        const int k = 4 * t + 1024 * i;
+        ok[i] = k < en.H;
+        kk[i] = ok[i] ? k : 0;
     }
-    if (en.nt == 16) {
-#pragma unroll   // the 15 token loads, then the 15 row loads, each group in flight together
-        for (int j = 1; j < 16; ++j) {
-            const uint2 u = *reinterpret_cast<const uint2 *>(gs.tabs[j] + (size_t)token(j) * en.H + kk);
-            a[0] += h2f(u.x & 0xffff); a[1] += h2f(u.x >> 16); a[2] += h2f(u.y & 0xffff); a[3] += h2f(u.y >> 16);
+    if constexpr (F32TAB) {
+        const float *r0 = en.ftab + (en.ftab_row0 + (size_t)token(gs.tok_col0)) * en.H;
+#pragma unroll
+        for (int i = 0; i < W; ++i) {
+            const float4 e = *reinterpret_cast<const float4 *>(r0 + kk[i]);
+            a[i][0] = e.x; a[i][1] = e.y; a[i][2] = e.z; a[i][3] = e.w;
         }
-        const int fr = gs.frame[b];
-        const float *extra = fr < gs.tr_len[b] ? gs.tr + (size_t)b * gs.tr_ld + (size_t)fr * en.H : gs.pad + (size_t)b * en.H;
-        const float4 e = *reinterpret_cast<const float4 *>(extra + kk);
-        a[0] += e.x; a[1] += e.y; a[2] += e.z; a[3] += e.w;
+    } else {
+        {
+            const uint16_t *r0 = en.nt == 1 ? gs.tab0 + (size_t)token(gs.tok_col0) * en.H : gs.tabs[0] + (size_t)token(0) * en.H;
+#pragma unroll
+            for (int i = 0; i < W; ++i) {
+                const uint2 u = *reinterpret_cast<const uint2 *>(r0 + kk[i]);
+                a[i][0] = h2f(u.x & 0xffff); a[i][1] = h2f(u.x >> 16); a[i][2] = h2f(u.y & 0xffff); a[i][3] = h2f(u.y >> 16);
+            }
+        }
+        if (en.nt == 16) {
+#pragma unroll   // the 15 token loads, then the 15 row loads, each group in flight together
+            for (int j = 1; j < 16; ++j) {
+                const uint16_t *rj = gs.tabs[j] + (size_t)token(j) * en.H;
+#pragma unroll
+                for (int i = 0; i < W; ++i) {
+                    const uint2 u = *reinterpret_cast<const uint2 *>(rj + kk[i]);
+                    a[i][0] += h2f(u.x & 0xffff); a[i][1] += h2f(u.x >> 16); a[i][2] += h2f(u.y & 0xffff); a[i][3] += h2f(u.y >> 16);
+                }
+            }
+            const int fr = gs.frame[b];
+            const float *extra = fr < gs.tr_len[b] ? gs.tr + (size_t)b * gs.tr_ld + (size_t)fr * en.H : gs.pad + (size_t)b * en.H;
+#pragma unroll
+            for (int i = 0; i < W; ++i) {
+                const float4 e = *reinterpret_cast<const float4 *>(extra + kk[i]);
+                a[i][0] += e.x; a[i][1] += e.y; a[i][2] += e.z; a[i][3] += e.w;
+            }
+        }
     }
-    float4 x = ok ? make_float4(a[0], a[1], a[2], a[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const size_t o = (size_t)b * en.H + kk;
-    if (ok) *reinterpret_cast<float4 *>(en.x + o) = x;
-    double ss = (double)(x.x * x.x) + (double)(x.y * x.y) + (double)(x.z * x.z) + (double)(x.w * x.w);
+    float4 x[W];
+    double ss = 0.0;
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        x[i] = ok[i] ? make_float4(a[i][0], a[i][1], a[i][2], a[i][3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok[i]) *reinterpret_cast<float4 *>(en.x + (size_t)b * en.H + kk[i]) = x[i];
+        const float4 v = x[i];
+        const double si = (double)(v.x * v.x) + (double)(v.y * v.y) + (double)(v.z * v.z) + (double)(v.w * v.w);
+        ss = i == 0 ? si : ss + si;
+    }
     ss = wave_sum_d(ss);
     if ((t & 63) == 0) scr[t >> 6] = ss;
     __syncthreads();
     ss = (scr[0] + scr[1]) + (scr[2] + scr[3]);
-    if (!ok) return;
     const float scale = 1.0f / sqrtf((float)(ss / en.H) + en.eps);
-    const float4 w = *reinterpret_cast<const float4 *>(en.nw + k);
-    const float y0 = (x.x * scale) * w.x, y1 = (x.y * scale) * w.y, y2 = (x.z * scale) * w.z, y3 = (x.w * scale) * w.w;
-    uint2 h;
-    h.x = (uint32_t)f2h(y0) | ((uint32_t)f2h(y1) << 16);
-    h.y = (uint32_t)f2h(y2) | ((uint32_t)f2h(y3) << 16);
-    *reinterpret_cast<uint2 *>(en.xn + o) = h;
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        if (!ok[i]) continue;
+        const float4 v = x[i];
+        const float4 w = *reinterpret_cast<const float4 *>(en.nw + 4 * t + 1024 * i);
+        const float y0 = (v.x * scale) * w.x, y1 = (v.y * scale) * w.y, y2 = (v.z * scale) * w.z, y3 = (v.w * scale) * w.w;
+        uint2 h;
+        h.x = (uint32_t)f2h(y0) | ((uint32_t)f2h(y1) << 16);
+        h.y = (uint32_t)f2h(y2) | ((uint32_t)f2h(y3) << 16);
+        *reinterpret_cast<uint2 *>(en.xn + (size_t)b * en.H + kk[i]) = h;
+    }
 }
 bool select_embed_norm(const SelectSpec &sp, const float *logits, const EmbedNorm &en, int S, hipStream_t s) {
     if (sp.V > 256 * SEL_VPT_MAX || sp.V <= 0) { set_error("select: vocab must be in (0, 4096]"); return false; }
-    if (en.H > 1024 || en.H % 4 != 0 || !en.x || !en.xn || !en.nw || (en.nt != 1 && en.nt != 16) ||
-        (en.nt == 1 && !en.gs.tab0) || (en.nt == 16 && !(en.gs.tabs && en.gs.frame && en.gs.tr_len && en.gs.pad)) ||
-        !en.gs.tok) {
+    const bool f32tab = en.ftab != nullptr;
+    if (en.H > (f32tab ? 1024 : 2048) || en.H % 4 != 0 || !en.x || !en.xn || !en.nw || (en.nt != 1 && en.nt != 16) ||
+        (en.nt == 1 && !en.gs.tab0 && !f32tab) || (f32tab && en.nt != 1) ||
+        (en.nt == 16 && !(en.gs.tabs && en.gs.frame && en.gs.tr_len && en.gs.pad)) || !en.gs.tok) {
         set_error("select_embed_norm: bad parameters");
         return false;
     }
     if (S <= 0) return true;
-    hipLaunchKernelGGL(k_select_embed_norm, dim3(S), dim3(256), 0, s, sp, logits, en);
+    if (f32tab) hipLaunchKernelGGL((k_select_embed_norm<1, true>), dim3(S), dim3(256), 0, s, sp, logits, en);
+    else if (en.H > 1024) hipLaunchKernelGGL((k_select_embed_norm<2, false>), dim3(S), dim3(256), 0, s, sp, logits, en);
+    else hipLaunchKernelGGL((k_select_embed_norm<1, false>), dim3(S), dim3(256), 0, s, sp, logits, en);
     Q3T_HIP(hipGetLastError());
     return true;
 }
 
+// out[b] = tab[row0 + tok[b * tok_ld + col]] (f32 rows of H): pass 1 of the 1.7B code predictor on the matrix-core
+// stack, whose CB0 was selected by the talker's launch (every later pass's row comes with its selection hand-off)
+__global__ void __launch_bounds__(256) k_gather_rows_f32(const float *tab, size_t row0, const int *tok, int tok_ld, int col,
+                                                         int H, float *out) {
+    const int b = blockIdx.x;
+    const float *row = tab + (row0 + (size_t)tok[(size_t)b * tok_ld + col]) * H;
+    for (int k = threadIdx.x * 4; k < H; k += 1024)
+        *reinterpret_cast<float4 *>(out + (size_t)b * H + k) = *reinterpret_cast<const float4 *>(row + k);
+}
+bool gather_rows_f32(const float *tab, size_t row0, const int *tok, int tok_ld, int col, int S, int H, float *out, hipStream_t s) {
+    if (H % 4 != 0 || !tab || !tok || !out) { set_error("gather_rows_f32: bad parameters"); return false; }
+    if (S <= 0) return true;
+    hipLaunchKernelGGL(k_gather_rows_f32, dim3(S), dim3(256), 0, s, tab, row0, tok, tok_ld, col, H, out);
+    Q3T_HIP(hipGetLastError());
+    return true;
+}
+
+int resid_norm_chunks(int H) { return H <= 1024 ? 1 : 2; }
+template <int W>
+static void launch_resid_norm(const ResidNorm &r, dim3 grid, hipStream_t s) {
+    switch (r.parts ? r.ksplit : 0) {
+        case 0: hipLaunchKernelGGL((k_resid_norm<0, W>), grid, dim3(256), 0, s, r); break;
+        case 1: hipLaunchKernelGGL((k_resid_norm<1, W>), grid, dim3(256), 0, s, r); break;
+        case 2: hipLaunchKernelGGL((k_resid_norm<2, W>), grid, dim3(256), 0, s, r); break;
+        case 3: hipLaunchKernelGGL((k_resid_norm<3, W>), grid, dim3(256), 0, s, r); break;
+        default: hipLaunchKernelGGL((k_resid_norm<4, W>), grid, dim3(256), 0, s, r); break;
+    }
+}
 bool resid_norm(const ResidNorm &r, hipStream_t s) {
     if (r.S <= 0) return true;
-    if (r.H > 1024 || r.H % 4 != 0 || !r.x || !r.nw || !r.xn || (r.parts && (r.ksplit < 1 || r.ksplit > 4))) {
+    if (r.H > 2048 || r.H % 4 != 0 || !r.x || !r.nw || !r.xn || (r.parts && (r.ksplit < 1 || r.ksplit > 4))) {
         set_error("resid_norm: unsupported shape");
         return false;
     }
     const size_t pf_lines = r.prefetch ? r.prefetch_bytes / 128 : 0;
     const unsigned pf_wgs = (unsigned)std::min<size_t>((pf_lines + 256 * RN_PF_LINES - 1) / (256 * RN_PF_LINES), 1024);
     const dim3 grid((unsigned)r.S + pf_wgs);
-    switch (r.parts ? r.ksplit : 0) {
-        case 0: hipLaunchKernelGGL(k_resid_norm<0>, grid, dim3(256), 0, s, r); break;
-        case 1: hipLaunchKernelGGL(k_resid_norm<1>, grid, dim3(256), 0, s, r); break;
-        case 2: hipLaunchKernelGGL(k_resid_norm<2>, grid, dim3(256), 0, s, r); break;
-        case 3: hipLaunchKernelGGL(k_resid_norm<3>, grid, dim3(256), 0, s, r); break;
-        default: hipLaunchKernelGGL(k_resid_norm<4>, grid, dim3(256), 0, s, r); break;
-    }
+    if (resid_norm_chunks(r.H) == 1) launch_resid_norm<1>(r, grid, s);
+    else launch_resid_norm<2>(r, grid, s);
     Q3T_HIP(hipGetLastError());
     return true;
 }

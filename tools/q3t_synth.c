@@ -85,6 +85,13 @@ static const cfg_t CFG_TINY17 = {
     "tiny17", 1024, 128, 512, 3, 8, 2, 64, 1024, 3072, 16,
     3, 2048, 1e-6f, 1000000.0f, 1001, 1002, 1000,
     2048, 32, 64, 128, 2, 2, 128, 96, 2, 4, {8, 5, 4, 3}, 256, 512, 4, 2};
+// the 1.7B widths and head layouts (talker 2,048 / 6,144, code predictor 1,024 / 3,072 behind mtp_proj, 16 q / 8 kv heads
+// of 128 in both) at 2 + 2 layers, with tiny's text side and vocoder: every kernel shape of a batched 1.7B step in
+// half a gigabyte
+static const cfg_t CFG_WIDE17 = {
+    "wide17", 1024, 128, 2048, 2, 16, 8, 128, 6144, 3072, 16,
+    2, 2048, 1e-6f, 1000000.0f, 1001, 1002, 1000,
+    2048, 32, 64, 128, 2, 2, 128, 96, 2, 4, {8, 5, 4, 3}, 1024, 3072, 16, 8};
 static const cfg_t CFG_TINY = {
     "tiny", 1024, 128, 256, 5, 4, 2, 64, 512, 3072, 16,
     5, 2048, 1e-6f, 1000000.0f, 1001, 1002, 1000,
@@ -630,10 +637,10 @@ static int write_gguf(const char *path, const kv_t *kvs, int nkv, uint64_t seed)
 }
 
 int main(int argc, char **argv) {
-    if (argc < 3) { fprintf(stderr, "usage: %s full|full5|tiny|tiny1|tiny17|full17 <out_dir> [seed]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s full|full5|tiny|tiny1|tiny17|full17|wide17 <out_dir> [seed]\n", argv[0]); return 2; }
     const cfg_t *c = strcmp(argv[1], "full") == 0 ? &CFG_FULL : strcmp(argv[1], "tiny") == 0 ? &CFG_TINY : strcmp(argv[1], "tiny1") == 0 ? &CFG_TINY1
                    : strcmp(argv[1], "tiny17") == 0 ? &CFG_TINY17 : strcmp(argv[1], "full17") == 0 ? &CFG_FULL17
-                   : strcmp(argv[1], "full5") == 0 ? &CFG_FULL5 : NULL;
+                   : strcmp(argv[1], "full5") == 0 ? &CFG_FULL5 : strcmp(argv[1], "wide17") == 0 ? &CFG_WIDE17 : NULL;
     if (!c) { fprintf(stderr, "unknown config %s\n", argv[1]); return 2; }
     uint64_t seed = argc > 3 ? strtoull(argv[3], NULL, 0) : 0x51E3775ull;
     g_usage = argc > 4 && strcmp(argv[4], "usage") == 0;

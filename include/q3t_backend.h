@@ -142,6 +142,39 @@ typedef int (*q3t_queue_cb)(void *user, int32_t n, const int32_t *utt, const int
 int q3t_generate_queue_stream(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens, const int32_t *n_tokens,
                               const float *const *speaker, const q3t_gen_params *p, int32_t *codes /* may be NULL */,
                               int32_t *n_frames, int32_t max_active, q3t_queue_cb cb, void *user, int32_t interval);
+/* ---- per-utterance language, speaker, sampling and max_len.  One record per utterance replaces the call-wide values
+ * of q3t_gen_params, so requests that differ in any of them share one batch or one queue.  What stays per call: the
+ * seed and p->max_len, the stride of `codes` ([n_utt][p->max_len][16]) and the cap of every record's max_len. */
+typedef struct q3t_utt_params {
+    int32_t language_id;        /* as in q3t_gen_params; < 0: the nothink prompt (one row shorter) */
+    int32_t max_len;            /* 1 .. p->max_len; <= 0: p->max_len */
+    float repetition_penalty;
+    float temperature;          /* <= 0: greedy */
+    int32_t top_k;
+    int32_t force_frames;
+} q3t_utt_params;
+/* the call-wide values of p as one record */
+void q3t_utt_params_from(const q3t_gen_params *p, q3t_utt_params *out);
+/* q3t_generate / q3t_generate_stream (on_frames == NULL: no streaming) and q3t_generate_queue / q3t_generate_queue_stream
+ * (cb == NULL: no deliveries; codes may be NULL only with a callback) with up[u] for utterance u.  p gives max_len and
+ * seed only; its other fields are ignored.  speaker[u] may be NULL for any subset of the utterances (speaker == NULL:
+ * none).  Sampling stays keyed by (seed, utterance index or slot, frame, step), so an utterance's codes are those of a
+ * call in which every utterance has its values, and a smaller max_len gives a prefix of the longer run.
+ * n_frames[u] <= up[u].max_len, and no callback hands out a frame at or beyond an utterance's own max_len; rows of
+ * codes at or beyond it are not written by q3t_generate_utt.  Everything else is as stated for the counterparts above
+ * (callback rules, the delivery contract, cancel and abort).
+ * Every record is validated before anything runs; Q3T_ERR with a message naming the utterance, no state changed and
+ * every n_frames[u] = 0: language_id >= codec_vocab, max_len > p->max_len, prompt length + its max_len + 8 > max_ctx,
+ * top_k < 0, repetition_penalty <= 0 or not finite, temperature not finite.
+ * Batches of two or more slots read each slot's sampling values from a device record; a one-slot context bakes them
+ * into its captured graphs and captures again when they change between utterances. */
+int q3t_generate_utt(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens, const int32_t *n_tokens,
+                     const float *const *speaker, const q3t_gen_params *p, const q3t_utt_params *up /* [n_utt] */,
+                     int32_t *codes, int32_t *n_frames, q3t_frame_cb on_frames, void *user, int32_t interval);
+int q3t_generate_queue_utt(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens, const int32_t *n_tokens,
+                           const float *const *speaker, const q3t_gen_params *p, const q3t_utt_params *up /* [n_utt] */,
+                           int32_t *codes, int32_t *n_frames, int32_t max_active, q3t_queue_cb cb, void *user,
+                           int32_t interval);
 /* tuning knob (process-wide): batches of >= min_batch slots run the projections on the matrix cores (MFMA GEMM,
  * gemm_mfma.hip) instead of the weight-streaming GEMV; 0 disables the matrix-core path.  Default 4 (env
  * Q3T_MFMA_MIN_B).  Applies to graphs captured afterwards (create contexts after changing it). */
@@ -284,6 +317,11 @@ int q3t_talker_forward(q3t_ctx *ctx, int n_slots, const float *embd /* [n][H] */
  * equals q3t_talker_forward with that many slots replayed at its position, bit for bit. */
 int q3t_talker_prefill(q3t_ctx *ctx, int n_utt, int n_rows, const float *embd /* [n_utt][n_rows][H] */, int family_slots,
                        float *hidden /* [n_utt][n_rows][H] or NULL */, float *logits /* [n_utt][codec_vocab] or NULL */);
+/* the same over prompts of different lengths in one pass: utterance u has n_rows[u] (1..10) rows, packed one utterance
+ * after the other in embd and hidden; logits [n_utt][codec_vocab].  Row i of utterance u is, bit for bit, what
+ * q3t_talker_prefill(n_utt = 1, n_rows = n_rows[u]) computes for it (hidden, last-row logits, the K/V rows of slot u). */
+int q3t_talker_prefill_ragged(q3t_ctx *ctx, int n_utt, const int32_t *n_rows /* [n_utt] */, const float *embd,
+                              int family_slots, float *hidden /* packed, or NULL */, float *logits /* or NULL */);
 int q3t_codepred_frame(q3t_ctx *ctx, int n_slots, const float *hidden /* [n][H] */, const int32_t *cb0 /* [n] */,
                        float temperature, int32_t top_k, uint64_t seed, int32_t frame,
                        int32_t *codes15 /* [n][15] */, float *logits /* [n][15][cp_vocab] or NULL */);

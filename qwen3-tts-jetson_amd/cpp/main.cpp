@@ -4,6 +4,10 @@
 //   single shot   -m <dir> -t <text> [-o out.wav] [-r ref.wav] [-e speaker.embd] [sampling flags]
 //   --serve       stdin lines "text<TAB>output.wav" -> stdout "OK<TAB>duration_s<TAB>time_ms<TAB>output.wav" or
 //                 "ERR<TAB>message"; "quit" / "exit" ends (main.cpp:109-163)
+//                 MI355X extension: a third TAB field "key=value;..." gives the request values of its own (language,
+//                 temperature, top_k, repetition_penalty, max_tokens, speaker=<embedding file>; serve_request.h), so
+//                 requests that differ in them still share a --batch or a --queue; a bad field fails that request
+//                 alone with an ERR reply
 //   -r without -e caches the embedding in <ref>.embd (raw float32, main.cpp:37-91, 246-255)
 // MI355X extensions (no reference counterpart):
 //   --device <n>         GPU ordinal
@@ -29,6 +33,7 @@
 #include <vector>
 
 #include "qwen3_tts_pipeline.h"
+#include "serve_request.h"
 
 namespace {
 
@@ -64,7 +69,8 @@ void print_usage(const char *program) {
     fprintf(stderr, "\n");
     fprintf(stderr, "Server mode:\n");
     fprintf(stderr, "  %s -m ./models -e speaker.bin --serve\n", program);
-    fprintf(stderr, "  Then send lines: text<TAB>output.wav\n");
+    fprintf(stderr, "  Then send lines: text<TAB>output.wav[<TAB>key=value;...]\n");
+    fprintf(stderr, "    per-request keys: language, temperature, top_k, repetition_penalty, max_tokens, speaker\n");
     fprintf(stderr, "  Responds with:   OK<TAB>duration_s<TAB>time_ms<TAB>output.wav\n");
     fprintf(stderr, "  Send 'quit' to exit.\n");
 }
@@ -121,8 +127,8 @@ qwen3_tts::tts_result synthesize_one(qwen3_tts::Qwen3TTS &tts, const std::string
     return tts.synthesize(text, params);
 }
 
-struct Request {
-    std::string text, output;
+struct Request : qwen3_tts::serve_request {
+    std::string error;   // a bad third field: the request is answered with ERR and not synthesized
 };
 
 // one request line; false on EOF / quit
@@ -134,9 +140,7 @@ bool read_request(Request &r, bool &quit) {
         while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = '\0';
         if (len == 0) continue;
         if (strcmp(line, "quit") == 0 || strcmp(line, "exit") == 0) { quit = true; return false; }
-        const char *tab = strchr(line, '\t');
-        r.text = tab ? std::string(line, tab - line) : std::string(line);
-        r.output = tab ? std::string(tab + 1) : std::string("output.wav");
+        qwen3_tts::parse_serve_line(line, r, r.error);
         return true;
     }
 }
@@ -179,8 +183,63 @@ int run_server(qwen3_tts::Qwen3TTS &tts, const std::vector<float> &speaker_embd,
             if (!read_request(r, quit)) break;
             reqs.push_back(r);
         }
+        // a request with a bad third field gets its ERR reply now; the others go on
+        std::vector<Request> good;
+        bool own_values = false;
+        for (const Request &q : reqs) {
+            if (!q.error.empty()) { fprintf(stdout, "ERR\t%s\n", q.error.c_str()); fflush(stdout); continue; }
+            good.push_back(q);
+            own_values = own_values || q.any();
+        }
+        reqs.swap(good);
         for (const Request &q : reqs) fprintf(stderr, "Synthesizing: \"%s\" -> %s\n", q.text.c_str(), q.output.c_str());
-        if (reqs.size() == 1 || (speaker_embd.empty() && !reference_audio.empty())) {
+        if (own_values) {
+            // requests with values of their own: every request of the set becomes a tts_request (the command line's
+            // values where it gives none) and the set shares one batch or one queue
+            std::vector<qwen3_tts::tts_request> tr;
+            std::vector<Request> run;
+            for (const Request &q : reqs) {
+                qwen3_tts::tts_request t;
+                t.text = q.text;
+                t.params = params;
+                t.speaker_embedding = speaker_embd;
+                if (q.has_language) t.language_id = q.language_id;
+                if (q.has_temperature) t.params.temperature = q.temperature;
+                if (q.has_top_k) t.params.top_k = q.top_k;
+                if (q.has_repetition_penalty) t.params.repetition_penalty = q.repetition_penalty;
+                if (q.has_max_tokens) t.params.max_audio_tokens = q.max_tokens;
+                if (q.has_speaker) {
+                    t.speaker_embedding = load_embedding(q.speaker);
+                    if (t.speaker_embedding.empty()) {
+                        fprintf(stdout, "ERR\tcannot read speaker embedding %s\n", q.speaker.c_str());
+                        fflush(stdout);
+                        continue;
+                    }
+                } else if (speaker_embd.empty() && !reference_audio.empty()) {
+                    // the server's voice exists only as reference audio: a tts_request cannot carry it, and a zero
+                    // speaker row in its place would drop the voice without a word
+                    fprintf(stdout, "ERR\trequest options need the server's voice as an embedding (-e), or speaker=<file>\n");
+                    fflush(stdout);
+                    continue;
+                }
+                // a value the engine would refuse fails this request alone, not the set it was read with
+                std::string why;
+                if (!tts.check_request(t, why)) {
+                    fprintf(stdout, "ERR\t%s\n", why.c_str());
+                    fflush(stdout);
+                    continue;
+                }
+                tr.push_back(t);
+                run.push_back(q);
+            }
+            if (tr.empty()) {   // every request of the set was answered with ERR
+            } else if (queue > 0) {
+                tts.synthesize_queue(tr, [&](int32_t i, const qwen3_tts::tts_result &r) { reply(r, run[i]); });
+            } else {
+                const std::vector<qwen3_tts::tts_result> res = tts.synthesize_batch(tr);
+                for (size_t i = 0; i < run.size(); ++i) reply(res[i], run[i]);
+            }
+        } else if (reqs.size() <= 1 || (speaker_embd.empty() && !reference_audio.empty())) {
             for (const Request &q : reqs) reply(synthesize_one(tts, q.text, speaker_embd, reference_audio, params), q);
         } else if (queue > 0) {   // each reply when its request ends
             std::vector<std::string> texts;

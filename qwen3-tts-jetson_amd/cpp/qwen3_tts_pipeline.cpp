@@ -401,6 +401,7 @@ bool Qwen3TTS::load_models(const std::string &model_dir) {
     q3t_config c;
     q3t_get_config(ctx_, &c);
     hidden_ = c.hidden;
+    codec_vocab_ = c.codec_vocab;
     fprintf(stderr, "  TTS transformer loaded: hidden_size=%d, n_layers=%d (%lld ms)\n", c.hidden, c.n_layers,
             (long long)(now_ms() - t_model));
     if (vocoder_chunk_ > 0)
@@ -588,10 +589,67 @@ tts_result Qwen3TTS::synthesize_internal(const std::string &text, const float *s
     return result;
 }
 
+// the requests of the text / embedding overloads: one tts_params for all
+static std::vector<tts_request> uniform_requests(const std::vector<std::string> &texts,
+                                                 const std::vector<std::vector<float>> &speaker_embeddings,
+                                                 const tts_params &params) {
+    std::vector<tts_request> reqs(texts.size());
+    for (size_t i = 0; i < texts.size(); ++i) {
+        reqs[i].text = texts[i];
+        reqs[i].params = params;
+        if (!speaker_embeddings.empty()) reqs[i].speaker_embedding = speaker_embeddings[i];
+    }
+    return reqs;
+}
+
+// what q3t_generate_utt / q3t_generate_queue_utt would refuse for this request -- and with it every request of the set
+bool Qwen3TTS::check_request(const tts_request &r, std::string &error) const {
+    error.clear();
+    if (!models_loaded_) error = "Models not loaded";
+    else if (r.language_id >= codec_vocab_) error = "language id " + std::to_string(r.language_id) + " out of range";
+    else if (r.params.top_k < 0) error = "top_k must be >= 0";
+    else if (!(r.params.repetition_penalty > 0.0f) || !std::isfinite(r.params.repetition_penalty))
+        error = "repetition_penalty must be finite and > 0";
+    else if (!std::isfinite(r.params.temperature)) error = "temperature must be finite";
+    else if (!r.speaker_embedding.empty() && (int32_t)r.speaker_embedding.size() != hidden_)
+        error = "speaker embedding holds " + std::to_string(r.speaker_embedding.size()) + " values, the model needs " +
+                std::to_string(hidden_);
+    return error.empty();
+}
+
+// one q3t_utt_params per request, and the call's q3t_gen_params (max_len: the longest request's)
+static void request_params(const std::vector<tts_request> &reqs, uint64_t seed, q3t_gen_params &p, std::vector<q3t_utt_params> &up) {
+    q3t_default_params(&p);
+    p.seed = seed;
+    p.max_len = 1;
+    up.resize(reqs.size());
+    for (size_t i = 0; i < reqs.size(); ++i) {
+        const tts_params &tp = reqs[i].params;
+        up[i].language_id = reqs[i].language_id;
+        up[i].max_len = std::max(tp.max_audio_tokens, 1);
+        up[i].repetition_penalty = tp.repetition_penalty;
+        up[i].temperature = tp.temperature;
+        up[i].top_k = tp.top_k;
+        up[i].force_frames = 0;
+        p.max_len = std::max(p.max_len, up[i].max_len);
+    }
+}
+
 std::vector<tts_result> Qwen3TTS::synthesize_batch(const std::vector<std::string> &texts,
                                                    const std::vector<std::vector<float>> &speaker_embeddings,
                                                    const tts_params &params) {
-    const int32_t n = (int32_t)texts.size();
+    const bool bad = !speaker_embeddings.empty() && speaker_embeddings.size() != texts.size();
+    return batch_requests(uniform_requests(texts, bad ? std::vector<std::vector<float>>() : speaker_embeddings, params),
+                          bad ? "speaker_embeddings must be empty or hold one entry per text" : "");
+}
+
+std::vector<tts_result> Qwen3TTS::synthesize_batch(const std::vector<tts_request> &requests) {
+    return batch_requests(requests, "");
+}
+
+// arg_error: what the caller found wrong with its arguments (reported after the "Models not loaded" check, as before)
+std::vector<tts_result> Qwen3TTS::batch_requests(const std::vector<tts_request> &requests, const std::string &arg_error) {
+    const int32_t n = (int32_t)requests.size();
     std::vector<tts_result> out(n);
     auto fail_all = [&](const std::string &m) {
         for (auto &r : out) r.error_msg = m;
@@ -599,32 +657,30 @@ std::vector<tts_result> Qwen3TTS::synthesize_batch(const std::vector<std::string
     };
     if (!models_loaded_) return fail_all("Models not loaded");
     if (n == 0) return out;
-    if (!speaker_embeddings.empty() && (int32_t)speaker_embeddings.size() != n)
-        return fail_all("speaker_embeddings must be empty or hold one entry per text");
+    if (!arg_error.empty()) return fail_all(arg_error);
+    for (const tts_request &r : requests)
+        if (!r.speaker_embedding.empty() && (int32_t)r.speaker_embedding.size() != hidden_)
+            return fail_all("a speaker embedding must be empty or hold one value per hidden channel");
     const int64_t t0 = now_ms();
     std::vector<std::vector<int32_t>> toks(n);
     std::vector<const int32_t *> tp(n);
     std::vector<int32_t> nt(n), nf(n);
-    const std::vector<float> zero(hidden_, 0.0f);
+    const std::vector<float> zero(hidden_, 0.0f);   // no embedding: a zero speaker row, as in every call of this pipeline
     std::vector<const float *> spk(n);
     for (int32_t i = 0; i < n; ++i) {
         const int64_t t = now_ms();
-        toks[i] = tokenizer_.encode_for_tts(texts[i]);
+        toks[i] = tokenizer_.encode_for_tts(requests[i].text);
         out[i].t_tokenize_ms = now_ms() - t;
         if (toks[i].empty()) return fail_all("Failed to tokenize text");
         tp[i] = toks[i].data();
         nt[i] = (int32_t)toks[i].size();
-        spk[i] = speaker_embeddings.empty() || speaker_embeddings[i].empty() ? zero.data() : speaker_embeddings[i].data();
+        spk[i] = requests[i].speaker_embedding.empty() ? zero.data() : requests[i].speaker_embedding.data();
     }
-    const int32_t max_len = std::max(params.max_audio_tokens, 1);
-    if (!ensure_slots(n, max_len)) return fail_all("Failed to generate speech codes: " + error_msg_);
     q3t_gen_params p;
-    q3t_default_params(&p);
-    p.max_len = max_len;
-    p.repetition_penalty = params.repetition_penalty;
-    p.temperature = params.temperature;
-    p.top_k = params.top_k;
-    p.seed = seed_;
+    std::vector<q3t_utt_params> up;
+    request_params(requests, seed_, p, up);
+    const int32_t max_len = p.max_len;
+    if (!ensure_slots(n, max_len)) return fail_all("Failed to generate speech codes: " + error_msg_);
     std::vector<int32_t> codes((size_t)n * max_len * 16);
     // --stream-full: one vocoder stream per utterance, the deliveries of an interval pushed as one batch while the
     // generation runs; the audio is the whole-utterance FULL decode's, sample for sample
@@ -639,10 +695,8 @@ std::vector<tts_result> Qwen3TTS::synthesize_batch(const std::vector<std::string
                 return fail_all("Failed to open the vocoder stream: " + q3t_error());
     }
     const int64_t tg = now_ms();
-    const int rc_gen = stream_full
-        ? q3t_generate_stream(ctx_, n, tp.data(), nt.data(), spk.data(), &p, codes.data(), nf.data(), batch_full_stream_cb,
-                              &bs, stream_full_)
-        : q3t_generate(ctx_, n, tp.data(), nt.data(), spk.data(), &p, codes.data(), nf.data());
+    const int rc_gen = q3t_generate_utt(ctx_, n, tp.data(), nt.data(), spk.data(), &p, up.data(), codes.data(), nf.data(),
+                                        stream_full ? batch_full_stream_cb : nullptr, &bs, stream_full ? stream_full_ : 0);
     if (rc_gen != Q3T_OK) {
         for (auto &r : out) r.audio.clear();
         return fail_all("Failed to generate speech codes: " + q3t_error());
@@ -689,7 +743,20 @@ std::vector<tts_result> Qwen3TTS::synthesize_queue(const std::vector<std::string
                                                    const std::vector<std::vector<float>> &speaker_embeddings,
                                                    const tts_params &params,
                                                    const std::function<void(int32_t, const tts_result &)> &on_result) {
-    const int32_t n = (int32_t)texts.size();
+    const bool bad = !speaker_embeddings.empty() && speaker_embeddings.size() != texts.size();
+    return queue_requests(uniform_requests(texts, bad ? std::vector<std::vector<float>>() : speaker_embeddings, params),
+                          on_result, bad ? "speaker_embeddings must be empty or hold one entry per text" : "");
+}
+
+std::vector<tts_result> Qwen3TTS::synthesize_queue(const std::vector<tts_request> &requests,
+                                                   const std::function<void(int32_t, const tts_result &)> &on_result) {
+    return queue_requests(requests, on_result, "");
+}
+
+std::vector<tts_result> Qwen3TTS::queue_requests(const std::vector<tts_request> &requests,
+                                                 const std::function<void(int32_t, const tts_result &)> &on_result,
+                                                 const std::string &arg_error) {
+    const int32_t n = (int32_t)requests.size();
     std::vector<tts_result> out(n);
     QueueSynthState qs;
     qs.out = &out;
@@ -703,32 +770,30 @@ std::vector<tts_result> Qwen3TTS::synthesize_queue(const std::vector<std::string
     };
     if (!models_loaded_) return fail_rest("Models not loaded");
     if (n == 0) return out;
-    if (!speaker_embeddings.empty() && (int32_t)speaker_embeddings.size() != n)
-        return fail_rest("speaker_embeddings must be empty or hold one entry per text");
+    if (!arg_error.empty()) return fail_rest(arg_error);
+    for (const tts_request &r : requests)
+        if (!r.speaker_embedding.empty() && (int32_t)r.speaker_embedding.size() != hidden_)
+            return fail_rest("a speaker embedding must be empty or hold one value per hidden channel");
     std::vector<std::vector<int32_t>> toks(n);
     std::vector<const int32_t *> tp(n);
     std::vector<int32_t> nt(n), nf(n);
-    const std::vector<float> zero(hidden_, 0.0f);
+    const std::vector<float> zero(hidden_, 0.0f);   // no embedding: a zero speaker row, as in every call of this pipeline
     std::vector<const float *> spk(n);
     for (int32_t i = 0; i < n; ++i) {
         const int64_t t = now_ms();
-        toks[i] = tokenizer_.encode_for_tts(texts[i]);
+        toks[i] = tokenizer_.encode_for_tts(requests[i].text);
         out[i].t_tokenize_ms = now_ms() - t;
         if (toks[i].empty()) return fail_rest("Failed to tokenize text");
         tp[i] = toks[i].data();
         nt[i] = (int32_t)toks[i].size();
-        spk[i] = speaker_embeddings.empty() || speaker_embeddings[i].empty() ? zero.data() : speaker_embeddings[i].data();
+        spk[i] = requests[i].speaker_embedding.empty() ? zero.data() : requests[i].speaker_embedding.data();
     }
-    const int32_t max_len = std::max(params.max_audio_tokens, 1);
+    q3t_gen_params p;
+    std::vector<q3t_utt_params> up;
+    request_params(requests, seed_, p, up);
+    const int32_t max_len = p.max_len;
     const int32_t slots = std::min(n, std::max(queue_slots_, 1));
     if (!ensure_slots(slots, max_len)) return fail_rest("Failed to generate speech codes: " + error_msg_);
-    q3t_gen_params p;
-    q3t_default_params(&p);
-    p.max_len = max_len;
-    p.repetition_penalty = params.repetition_penalty;
-    p.temperature = params.temperature;
-    p.top_k = params.top_k;
-    p.seed = seed_;
     qs.ctx = ctx_;
     qs.stream_full = stream_full_ > 0 && vocoder_chunk_ <= 0;
     qs.vocoder_chunk = vocoder_chunk_;
@@ -739,8 +804,8 @@ std::vector<tts_result> Qwen3TTS::synthesize_queue(const std::vector<std::string
     qs.decode_ms.assign(n, 0.0);
     if (qs.stream_full && !qs.open_pool(slots)) return fail_rest("Failed to open the vocoder stream: " + q3t_error());
     // the context may hold more slots than this queue uses (it only grows): max_active keeps it to `slots`
-    const int rc = q3t_generate_queue_stream(ctx_, n, tp.data(), nt.data(), spk.data(), &p, nullptr, nf.data(), slots,
-                                             queue_synth_cb, &qs, qs.stream_full ? stream_full_ : kQueueTick);
+    const int rc = q3t_generate_queue_utt(ctx_, n, tp.data(), nt.data(), spk.data(), &p, up.data(), nullptr, nf.data(), slots,
+                                          queue_synth_cb, &qs, qs.stream_full ? stream_full_ : kQueueTick);
     if (rc != Q3T_OK) return fail_rest("Failed to generate speech codes: " + q3t_error());
     if (!qs.error_msg.empty()) return fail_rest(qs.error_msg);
     return fail_rest("the queue ended without the utterance's final delivery");   // none is left after a clean run

@@ -41,6 +41,16 @@ struct tts_result {
     uint64_t mem_phys_peak_bytes = 0;
 };
 
+// one utterance of a mixed batch or queue (synthesize_batch / synthesize_queue over requests): its own text, voice
+// (empty: a zero speaker row, as in every call of this pipeline), sampling values, max_audio_tokens and language.  What stays per call: the seed
+// (set_seed) and the reporting switches of tts_params (print_progress / print_timing are not used by these calls).
+struct tts_request {
+    std::string text;
+    std::vector<float> speaker_embedding;
+    tts_params params;
+    int32_t language_id = 2050;   // < 0: the nothink prompt
+};
+
 class Qwen3TTS {
 public:
     Qwen3TTS();
@@ -79,6 +89,16 @@ public:
     std::vector<tts_result> synthesize_batch(const std::vector<std::string> &texts,
                                              const std::vector<std::vector<float>> &speaker_embeddings,
                                              const tts_params &params = tts_params());
+    // the same with every utterance's own voice, language, sampling values and max_audio_tokens (q3t_generate_utt);
+    // the overload above forwards here with one tts_params for all
+    std::vector<tts_result> synthesize_batch(const std::vector<tts_request> &requests);
+
+    // false with the reason when the engine would refuse this request's values (language id at or above the codec
+    // vocabulary, top_k < 0, a repetition penalty that is not finite and > 0, a temperature that is not finite, an
+    // embedding of the wrong length): such a request fails the whole synthesize_batch / synthesize_queue call it is
+    // part of, so a server checks each request first and answers it alone.  max_audio_tokens needs no check: the
+    // context grows to the longest request
+    bool check_request(const tts_request &request, std::string &error) const;
 
     // Continuous batching (q3t_generate_queue_stream): any number of texts through set_queue_slots(n) slots, a slot
     // refilled with the next text when its utterance ends.  on_result(index, result) fires at the utterance's final
@@ -96,17 +116,25 @@ public:
                                              const std::vector<std::vector<float>> &speaker_embeddings,
                                              const tts_params &params = tts_params(),
                                              const std::function<void(int32_t, const tts_result &)> &on_result = nullptr);
+    // the same over requests (q3t_generate_queue_utt): requests that differ in voice, language, sampling values or
+    // max_audio_tokens share the slots.  The overload above forwards here
+    std::vector<tts_result> synthesize_queue(const std::vector<tts_request> &requests,
+                                             const std::function<void(int32_t, const tts_result &)> &on_result = nullptr);
 
 private:
     tts_result synthesize_internal(const std::string &text, const float *speaker_embedding, const tts_params &params,
                                    tts_result &result);
     bool ensure_slots(int32_t slots, int32_t max_len);
+    std::vector<tts_result> batch_requests(const std::vector<tts_request> &requests, const std::string &arg_error);
+    std::vector<tts_result> queue_requests(const std::vector<tts_request> &requests,
+                                           const std::function<void(int32_t, const tts_result &)> &on_result,
+                                           const std::string &arg_error);
 
     TextTokenizer tokenizer_;
     q3t_ctx *ctx_ = nullptr;
     int device_ = 0;
     uint64_t seed_ = 0;
-    int32_t slots_ = 0, n_ctx_ = 0, hidden_ = 1024;
+    int32_t slots_ = 0, n_ctx_ = 0, hidden_ = 1024, codec_vocab_ = 3072;
     int32_t vocoder_chunk_ = 0;
     int32_t stream_full_ = 0;
     int32_t queue_slots_ = 1;

@@ -382,7 +382,10 @@ __global__ void __launch_bounds__(PF_THREADS) k_prefill_attn(const PrefillAttnPa
     __shared__ float q_s[PMAX][R][D];
     __shared__ float k_s[PMAX][D], v_s[PMAX][D];
     const int u = blockIdx.x, g = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int plen = p.plen, QKV = (p.nH + 2 * p.nKV) * D;
+    // ragged form: the workgroup's row count and first row from the per-utterance arrays (the count clamped to the
+    // rows LDS holds); the uniform form is u * plen as before
+    const int plen = p.row_count ? min(p.row_count[u], PMAX) : p.plen, QKV = (p.nH + 2 * p.nKV) * D;
+    const int row0 = p.row_off ? p.row_off[u] : u * plen;
     const size_t head_off = ((size_t)p.slot[u] * p.nKV + g) * p.n_ctx * D;
     // ---- prologue: vectors (row i, v) with v < R the q heads, v == R the k row, v == R + 1 the v row; task
     // wave + NW k.  Every operand of the wave's tasks is loaded first (one memory round trip instead of one per task:
@@ -400,7 +403,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_prefill_attn(const PrefillAttnPa
         for (int e = 0; e < E; ++e) xv[k][e] = 0.0f;
         if (task < ntask) {
             const int i = task / (R + 2), v = task % (R + 2);
-            const float *qkv = p.qkv + (size_t)(u * plen + i) * QKV;
+            const float *qkv = p.qkv + (size_t)(row0 + i) * QKV;
             const float *src = v == R + 1 ? qkv + (size_t)(p.nH + p.nKV + g) * D : v == R ? qkv + (size_t)(p.nH + g) * D : qkv + (size_t)(g * R + v) * D;
 #pragma unroll
             for (int e = 0; e < E; ++e) xv[k][e] = src[lane + 64 * e];
@@ -487,7 +490,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_prefill_attn(const PrefillAttnPa
 #pragma unroll
         for (int j = 0; j < PMAX; ++j) pj[j] = j <= i ? exp_sm(__fsub_rn(sc[j], m)) : 0.0f;
         const float l = tree16(pj);
-        uint16_t *o = p.out + (size_t)(u * plen + i) * p.nH * D + (size_t)(g * R + h) * D + li * 8;
+        uint16_t *o = p.out + (size_t)(row0 + i) * p.nH * D + (size_t)(g * R + h) * D + li * 8;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             float pv[PMAX];
@@ -501,7 +504,9 @@ __global__ void __launch_bounds__(PF_THREADS) k_prefill_attn(const PrefillAttnPa
 
 bool prefill_attn(const PrefillAttnParams &p, hipStream_t s) {
     if (p.n_utt <= 0) return true;
-    if (p.plen < 1 || p.plen > PREFILL_MAX_ROWS || p.nKV <= 0 || p.nH % p.nKV != 0 || !p.qkv || !p.slot || !p.kc || !p.vc ||
+    const bool ragged = p.row_off || p.row_count;
+    if (ragged && !(p.row_off && p.row_count)) { set_error("prefill_attn: row offsets and counts go together"); return false; }
+    if ((!ragged && (p.plen < 1 || p.plen > PREFILL_MAX_ROWS)) || p.nKV <= 0 || p.nH % p.nKV != 0 || !p.qkv || !p.slot || !p.kc || !p.vc ||
         !p.out || !p.rope) {
         set_error("prefill_attn: bad parameters");
         return false;

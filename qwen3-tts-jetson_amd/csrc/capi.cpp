@@ -34,6 +34,18 @@ q3t::GenParams to_gp(const q3t_gen_params *p) {
     g.force_frames = p->force_frames;
     return g;
 }
+std::vector<q3t::UttParams> to_up(const q3t_utt_params *up, int n) {
+    std::vector<q3t::UttParams> v((size_t)std::max(n, 0));
+    for (int u = 0; u < n; ++u) {
+        v[u].language_id = up[u].language_id;
+        v[u].max_len = up[u].max_len;
+        v[u].rep_penalty = up[u].repetition_penalty;
+        v[u].temperature = up[u].temperature;
+        v[u].top_k = up[u].top_k;
+        v[u].force_frames = up[u].force_frames;
+    }
+    return v;
+}
 #define GUARD_BEGIN try {
 #define GUARD_END                                                   \
     }                                                               \
@@ -219,6 +231,43 @@ int q3t_generate_queue_stream(q3t_ctx *ctx, int n_utt, const int32_t *const *tok
     if (n_utt < 0 || (n_utt > 0 && (!tokens || !n_tokens || !n_frames))) { q3t::set_error("null argument"); return Q3T_ERR; }
     return ctx->engine.generate_queue(n_utt, tokens, n_tokens, speaker, to_gp(p), codes, n_frames, max_active, cb, user, interval)
                ? Q3T_OK : Q3T_ERR;
+    GUARD_END
+}
+
+void q3t_utt_params_from(const q3t_gen_params *p, q3t_utt_params *out) {
+    if (!p || !out) return;
+    out->language_id = p->language_id;
+    out->max_len = p->max_len;
+    out->repetition_penalty = p->repetition_penalty;
+    out->temperature = p->temperature;
+    out->top_k = p->top_k;
+    out->force_frames = p->force_frames;
+}
+
+int q3t_generate_utt(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens, const int32_t *n_tokens,
+                     const float *const *speaker, const q3t_gen_params *p, const q3t_utt_params *up, int32_t *codes,
+                     int32_t *n_frames, q3t_frame_cb on_frames, void *user, int32_t interval) {
+    GUARD_BEGIN
+    CHECK_CTX(ctx);
+    CHECK_TALKER(ctx);
+    if (n_utt < 0 || (n_utt > 0 && (!tokens || !n_tokens || !codes || !n_frames || !up))) { q3t::set_error("null argument"); return Q3T_ERR; }
+    const std::vector<q3t::UttParams> v = to_up(up, n_utt);
+    return ctx->engine.generate(n_utt, tokens, n_tokens, speaker, to_gp(p), codes, n_frames, on_frames, user, interval, v.data())
+               ? Q3T_OK : Q3T_ERR;
+    GUARD_END
+}
+
+int q3t_generate_queue_utt(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens, const int32_t *n_tokens,
+                           const float *const *speaker, const q3t_gen_params *p, const q3t_utt_params *up, int32_t *codes,
+                           int32_t *n_frames, int32_t max_active, q3t_queue_cb cb, void *user, int32_t interval) {
+    GUARD_BEGIN
+    CHECK_CTX(ctx);
+    CHECK_TALKER(ctx);
+    if (n_utt < 0 || (n_utt > 0 && (!tokens || !n_tokens || !n_frames || !up))) { q3t::set_error("null argument"); return Q3T_ERR; }
+    if (cb && interval <= 0) { q3t::set_error("q3t_generate_queue_utt: interval must be > 0 with a callback"); return Q3T_ERR; }
+    const std::vector<q3t::UttParams> v = to_up(up, n_utt);
+    return ctx->engine.generate_queue(n_utt, tokens, n_tokens, speaker, to_gp(p), codes, n_frames, max_active, cb, user,
+                                      cb ? interval : 0, v.data()) ? Q3T_OK : Q3T_ERR;
     GUARD_END
 }
 
@@ -542,6 +591,16 @@ int q3t_talker_prefill(q3t_ctx *ctx, int n_utt, int n_rows, const float *embd, i
     CHECK_TALKER(ctx);
     if (!embd) { q3t::set_error("null argument"); return Q3T_ERR; }
     return ctx->engine.talker_prefill(n_utt, n_rows, embd, family_slots, hidden, logits) ? Q3T_OK : Q3T_ERR;
+    GUARD_END
+}
+
+int q3t_talker_prefill_ragged(q3t_ctx *ctx, int n_utt, const int32_t *n_rows, const float *embd, int family_slots,
+                              float *hidden, float *logits) {
+    GUARD_BEGIN
+    CHECK_CTX(ctx);
+    CHECK_TALKER(ctx);
+    if (!embd || !n_rows) { q3t::set_error("null argument"); return Q3T_ERR; }
+    return ctx->engine.talker_prefill_ragged(n_utt, n_rows, embd, family_slots, hidden, logits) ? Q3T_OK : Q3T_ERR;
     GUARD_END
 }
 

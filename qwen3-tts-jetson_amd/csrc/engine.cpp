@@ -86,6 +86,7 @@ Engine::~Engine() {
     for (auto &kv : g_talker_) hipGraphExecDestroy(kv.second);
     for (auto &kv : g_frame_) hipGraphExecDestroy(kv.second);
     for (auto &kv : g_prefill_) hipGraphExecDestroy(kv.second);
+    for (auto &kv : g_prefill_rag_) hipGraphExecDestroy(kv.second);
     for (auto &kv : g_cp_) hipGraphExecDestroy(kv.second);
     voc_.reset();
     for (void *p : allocs_) hipFree(p);
@@ -488,12 +489,14 @@ bool Engine::alloc_state() {
     utt_ = dalloc<uint64_t>(S);
     seed_dev_ = dalloc<uint64_t>(1);
     slot_iota_ = dalloc<int>(S);
+    sel_rec_ = dalloc<SelRec>(S);
+    slot_max_len_ = dalloc<int>(S);
     trailing_ = dalloc<float>((size_t)S * max_trailing_ * H);
     tts_pad_ = dalloc<float>((size_t)S * H);
     codes_max_len_ = max_ctx_;
     codes_ = dalloc<int32_t>((size_t)S * codes_max_len_ * 16);
     if (!alloc_prompt_scratch(main_ps_, cp_in1_)) return false;
-    if (!x_ || !kc_ || !vc_) { set_error("device allocation failed"); return false; }
+    if (!x_ || !kc_ || !vc_ || !sel_rec_ || !slot_max_len_) { set_error("device allocation failed"); return false; }
     std::vector<int> cpp((size_t)16 * S);
     for (int p = 0; p < 16; ++p) for (int s = 0; s < S; ++s) cpp[(size_t)p * S + s] = p;
     Q3T_HIP(hipMemcpyAsync(cp_pos_, cpp.data(), cpp.size() * 4, hipMemcpyHostToDevice, stream_));
@@ -1087,6 +1090,7 @@ SelectSpec Engine::select_spec(int mode, const GenParams &gp, int frame_offset, 
     sp.temperature = gp.temperature; sp.top_k = gp.top_k; sp.seed = gp.seed; sp.seed_dev = seed_dev_; sp.utt = utt_;
     sp.step = step;
     sp.seen = seen_; sp.n_tokens = n_tokens_; sp.force_frames = force_; sp.eos = c_.codec_eos; sp.rep = gp.rep_penalty;
+    if (rec_on_) sp.rec = sel_rec_;   // per-utterance sampling: the slots' records in place of the scalars
     return sp;
 }
 
@@ -1395,20 +1399,24 @@ bool Engine::ensure_prefill() {
     pf_hid_ = dalloc<float>(R * H);
     pf_logits_ = dalloc<float>(R * c_.codec_vocab);
     pf_slot_ = dalloc<int>(max_slots_);
-    if (!pf_x_ || !pf_xn_ || !pf_parts_ || !pf_qkv_ || !pf_attn_ || !pf_hmlp_ || !pf_hid_ || !pf_logits_ || !pf_slot_) {
+    pf_off_ = dalloc<int>(max_slots_);
+    pf_len_ = dalloc<int>(max_slots_);
+    if (!pf_x_ || !pf_xn_ || !pf_parts_ || !pf_qkv_ || !pf_attn_ || !pf_hmlp_ || !pf_hid_ || !pf_logits_ || !pf_slot_ ||
+        !pf_off_ || !pf_len_) {
         set_error("device allocation failed");
         return false;
     }
     return true;
 }
 
-// the captured body: key = (S_main * 1024 + n_utt) * 16 + plen
-bool Engine::enqueue_prefill_rows(int key, hipStream_t s) {
-    const int plen = key % 16, n_utt = key / 16 % 1024, S_main = key / (16 * 1024);
-    const int rows = n_utt * plen;
+// the captured body over `rows` rows: plen > 0 the uniform form (rows = n_utt * plen), plen == 0 the ragged one, whose
+// attention takes each utterance's first row and row count from pf_off_ / pf_len_ (so one body serves every mix of
+// lengths with that total)
+bool Engine::enqueue_prefill_rows(int S_main, int n_utt, int plen, int rows, hipStream_t s) {
     const bool mm = use_mm(S_main);
     PrefillAttnParams pf;
     pf.slot = pf_slot_; pf.n_utt = n_utt; pf.plen = plen;
+    if (plen == 0) { pf.row_off = pf_off_; pf.row_count = pf_len_; }
     StackRun r;
     r.buf = prefill_bufs(); r.kv = talker_cache();
     r.family = S_main; r.pf = &pf;
@@ -1433,11 +1441,41 @@ bool Engine::prefill(int n_utt, int plen, const float *src, int S_main, hipStrea
                              hipMemcpyDeviceToDevice, s));
     const int key = (S_main * 1024 + n_utt) * 16 + plen;
     if (!g_prefill_.count(key)) {
-        hipGraphExec_t exec = capture(s, [&] { return enqueue_prefill_rows(key, s); });
+        hipGraphExec_t exec = capture(s, [&] { return enqueue_prefill_rows(S_main, n_utt, plen, n_utt * plen, s); });
         if (!exec) return false;
         g_prefill_[key] = exec;
     }
     Q3T_HIP(hipGraphLaunch(g_prefill_[key], s));
+    return true;
+}
+
+// src: the packed prompt rows, utterance u's lens[u] rows behind those of u - 1; pf_slot_[0, n_utt) must hold the target
+// slots.  The decoder stack's per-row arithmetic does not depend on the other rows, so every row is what the uniform
+// form computes for it.  Outputs as there, at the packed row offsets.
+bool Engine::prefill_ragged(int n_utt, const int *lens, const float *src, int S_main, hipStream_t s, PromptScratch &ps) {
+    const int H = c_.hidden;
+    if (n_utt <= 0 || n_utt > max_slots_ || n_utt >= 1024 || S_main < 1 || S_main > 4096) { set_error("prefill: bad shape"); return false; }
+    std::vector<int> &rag = ps.rag_host;   // a member: the (pageable) source outlives the copies
+    rag.assign((size_t)2 * n_utt, 0);
+    int total = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        if (lens[u] < 1 || lens[u] > 10) { set_error("prefill: rows per utterance must be in [1, 10]"); return false; }
+        rag[u] = total;
+        rag[n_utt + u] = lens[u];
+        total += lens[u];
+    }
+    if (!ensure_prefill()) return false;
+    if (!mm_ok_) S_main = 1;
+    Q3T_HIP(hipMemcpyAsync(pf_off_, rag.data(), n_utt * 4, hipMemcpyHostToDevice, s));
+    Q3T_HIP(hipMemcpyAsync(pf_len_, rag.data() + n_utt, n_utt * 4, hipMemcpyHostToDevice, s));
+    Q3T_HIP(hipMemcpyAsync(pf_x_, src, (size_t)total * H * 4, hipMemcpyDeviceToDevice, s));
+    const long long key = ((long long)S_main * 1024 + n_utt) * 16384 + total;
+    if (!g_prefill_rag_.count(key)) {
+        hipGraphExec_t exec = capture(s, [&] { return enqueue_prefill_rows(S_main, n_utt, 0, total, s); });
+        if (!exec) return false;
+        g_prefill_rag_[key] = exec;
+    }
+    Q3T_HIP(hipGraphLaunch(g_prefill_rag_[key], s));
     return true;
 }
 
@@ -1514,10 +1552,11 @@ int Engine::prompt_len(int language_id, bool has_spk) {
     return 3 + (language_id < 0 ? 3 : 4) + (has_spk ? 1 : 0) + 2;
 }
 
-bool Engine::assemble_prompts(PromptScratch &ps, hipStream_t s, const std::vector<PromptEntry> &in, int language_id,
-                              int *plen_out, std::vector<int> &trailing_len) {
+bool Engine::assemble_prompts(PromptScratch &ps, hipStream_t s, const std::vector<PromptEntry> &in, std::vector<int> &plen_out,
+                              std::vector<int> &trailing_len) {
     const int H = c_.hidden, n = (int)in.size();
-    if (language_id >= c_.codec_vocab) { set_error("language id out of range"); return false; }
+    for (const PromptEntry &e : in)
+        if (e.language_id >= c_.codec_vocab) { set_error("language id out of range"); return false; }
     std::vector<const int32_t *> tk(n);
     std::vector<int> nt(n), &idx = ps.idx_host;
     for (int j = 0; j < n; ++j) { tk[j] = in[j].tokens; nt[j] = in[j].n_tokens; }
@@ -1528,14 +1567,16 @@ bool Engine::assemble_prompts(PromptScratch &ps, hipStream_t s, const std::vecto
     Q3T_HIP(hipMemcpyAsync(ps.idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, s));
     if (!enqueue_text_projection((int)idx.size(), s, ps)) return false;
     // ---- prompt / trailing / pad rows
-    const int plen = prompt_len(language_id, n > 0 && in[0].speaker);
     std::vector<RowRecipe> &rec = ps.recipe_host;
+    plen_out.resize(n);
     rec.clear();
     auto crow = [&](int id) { return RowTerm{codec_embd_ + (size_t)id * H, 1}; };
     trailing_len.resize(n);
     for (int j = 0; j < n; ++j) {
         const SlotPlan &p = plan[j];
-        const int k = in[j].slot;
+        const int k = in[j].slot, language_id = in[j].language_id;
+        const int plen = prompt_len(language_id, in[j].speaker != nullptr);
+        if (in[j].row < 0 || in[j].row + plen > max_slots_ * 10) { set_error("prompt assembly: row out of range"); return false; }
         float *spk_dev = ps.spk + (size_t)k * H;
         if (in[j].speaker) Q3T_HIP(hipMemcpyAsync(spk_dev, in[j].speaker, H * 4, hipMemcpyHostToDevice, s));
         const float *P = ps.out + (size_t)p.rb * H;
@@ -1549,7 +1590,7 @@ bool Engine::assemble_prompts(PromptScratch &ps, hipStream_t s, const std::vecto
         cin.push_back(crow(c_.codec_bos));
         const int ol = (int)cin.size() - 1;
         if (3 + ol + 1 != plen) { set_error("prompt assembly: prefill length mismatch"); return false; }
-        float *out = ps.rows + (size_t)in[j].row * 10 * H;
+        float *out = ps.rows + (size_t)in[j].row * H;
         for (int r = 0; r < 3; ++r) row(out + (size_t)r * H, prow(3 + r));
         for (int t = 0; t < ol; ++t) row(out + (size_t)(3 + t) * H, t == ol - 1 ? prow(0) : prow(2), cin[t]);
         row(out + (size_t)(plen - 1) * H, prow(6), cin.back());
@@ -1558,10 +1599,10 @@ bool Engine::assemble_prompts(PromptScratch &ps, hipStream_t s, const std::vecto
         row(tr + (size_t)p.tcount * H, prow(1));
         row(tts_pad_ + (size_t)k * H, prow(2));
         trailing_len[j] = p.tcount + 1;
+        plen_out[j] = plen;
     }
     if ((int)rec.size() > ps.cap) { set_error("recipe overflow"); return false; }
     Q3T_HIP(hipMemcpyAsync(ps.recipe, rec.data(), rec.size() * sizeof(RowRecipe), hipMemcpyHostToDevice, s));
-    *plen_out = plen;
     return rows_recipe(ps.recipe, (int)rec.size(), H, s);
 }
 
@@ -1570,9 +1611,9 @@ bool Engine::prefill_embd(const int32_t *toks, int n, const float *spk, int lang
     // host entry for the parity tests: run the same device assembly as generate() on slot 0
     DeviceLock lk(false, device_);
     const int H = c_.hidden;
-    int plen = 0;
-    std::vector<int> tl;
-    if (!assemble_prompts(main_ps_, stream_, {PromptEntry{toks, n, spk, 0, 0}}, language_id, &plen, tl)) return false;
+    std::vector<int> tl, pl;
+    if (!assemble_prompts(main_ps_, stream_, {PromptEntry{toks, n, spk, 0, 0, language_id}}, pl, tl)) return false;
+    const int plen = pl[0];
     Q3T_HIP(hipMemcpyAsync(prefill, main_ps_.rows, (size_t)plen * H * 4, hipMemcpyDeviceToHost, stream_));
     Q3T_HIP(hipMemcpyAsync(trailing, trailing_, (size_t)tl[0] * H * 4, hipMemcpyDeviceToHost, stream_));
     Q3T_HIP(hipMemcpyAsync(tts_pad, tts_pad_, (size_t)H * 4, hipMemcpyDeviceToHost, stream_));
@@ -1601,25 +1642,6 @@ bool Engine::copy_weights_from(Engine &src) {
     return build_persist_tables();   // the tables derived from the weights, now that they are in place
 }
 
-bool Engine::generate(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
-                      const GenParams &gp, int32_t *codes, int *n_frames, FrameCb on_frames, void *user, int interval) {
-    if (n_utt <= 0) return true;
-    if (n_utt > max_slots_) { set_error("n_utt exceeds max_slots"); return false; }
-    // a run that launches a persistent grid holds the device alone (persist_exclusive); the others share it
-    DeviceLock lk(persist_exclusive(n_utt), device_);
-    StreamState st;
-    st.delivered.assign(n_utt, 0);
-    st.stop_at.assign(n_utt, -1);
-    bool fault = false;
-    if (generate_once(n_utt, tokens, n_tokens, speaker, gp, codes, n_frames, on_frames, user, interval, st, &fault))
-        return true;
-    if (!fault) return false;
-    // a persistent launch gave up on a hand-off: nothing it produced was delivered (every chunk is checked before it
-    // is handed out); re-run on the launch-per-op graphs, which are bit-identical, skipping the delivered chunks
-    if (!persist_recover()) return false;
-    return generate_once(n_utt, tokens, n_tokens, speaker, gp, codes, n_frames, on_frames, user, interval, st, &fault);
-}
-
 namespace {
 // a HIP event for the length of a scope
 struct Event {
@@ -1641,6 +1663,28 @@ struct ScopeExit {
 };
 }  // namespace
 
+bool Engine::generate(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
+                      const GenParams &gp, int32_t *codes, int *n_frames, FrameCb on_frames, void *user, int interval,
+                      const UttParams *up) {
+    if (n_utt <= 0) return true;
+    for (int u = 0; u < n_utt; ++u) n_frames[u] = 0;
+    if (n_utt > max_slots_) { set_error("n_utt exceeds max_slots"); return false; }
+    // a run that launches a persistent grid holds the device alone (persist_exclusive); the others share it
+    DeviceLock lk(persist_exclusive(n_utt), device_);
+    StreamState st;
+    st.delivered.assign(n_utt, 0);
+    st.stop_at.assign(n_utt, -1);
+    bool fault = false;
+    ScopeExit rec_off([&] { rec_on_ = false; });   // the stage entry points and the call-wide paths read the scalars
+    if (generate_once(n_utt, tokens, n_tokens, speaker, gp, up, codes, n_frames, on_frames, user, interval, st, &fault))
+        return true;
+    if (!fault) return false;
+    // a persistent launch gave up on a hand-off: nothing it produced was delivered (every chunk is checked before it
+    // is handed out); re-run on the launch-per-op graphs, which are bit-identical, skipping the delivered chunks
+    if (!persist_recover()) return false;
+    return generate_once(n_utt, tokens, n_tokens, speaker, gp, up, codes, n_frames, on_frames, user, interval, st, &fault);
+}
+
 bool Engine::check_gen_args(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                             const GenParams &gp, int *plen) {
     if (gp.language_id >= c_.codec_vocab) { set_error("language id out of range"); return false; }
@@ -1655,10 +1699,35 @@ bool Engine::check_gen_args(int n_utt, const int32_t *const *tokens, const int *
     return true;
 }
 
+bool Engine::check_utt_args(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
+                            const GenParams &gp, const UttParams *up, std::vector<UttParams> &ups, std::vector<int> &plen) {
+    ups.assign(up, up + n_utt);
+    plen.assign(n_utt, 0);
+    for (int u = 0; u < n_utt; ++u) {
+        UttParams &r = ups[u];
+        const std::string who = "utterance " + std::to_string(u) + ": ";
+        if (r.max_len <= 0) r.max_len = gp.max_len;
+        if (r.language_id >= c_.codec_vocab) { set_error(who + "language id out of range"); return false; }
+        if (r.max_len > gp.max_len) { set_error(who + "max_len exceeds the call's max_len"); return false; }
+        plen[u] = prompt_len(r.language_id, speaker && speaker[u]);
+        if (plen[u] + r.max_len + 8 > max_ctx_) { set_error(who + "max_len exceeds the context reserved at ctx creation"); return false; }
+        if (r.top_k < 0) { set_error(who + "top_k must be >= 0"); return false; }
+        if (!(r.rep_penalty > 0.0f) || !std::isfinite(r.rep_penalty)) { set_error(who + "repetition_penalty must be finite and > 0"); return false; }
+        if (!std::isfinite(r.temperature)) { set_error(who + "temperature must be finite"); return false; }
+    }
+    std::vector<int> idx;
+    std::vector<SlotPlan> plan;
+    return plan_rows(c_, n_utt, tokens, n_tokens, max_trailing_, idx, plan);
+}
+
 void Engine::set_gen_params(const GenParams &gp) {
     if (!(gp.temperature == gp_.temperature && gp.top_k == gp_.top_k && gp.rep_penalty == gp_.rep_penalty)) {
-        for (auto &kv : g_frame_) hipGraphExecDestroy(kv.second);
-        g_frame_.clear();
+        // (the graphs captured with the record pointer bake none of the three: they stay)
+        for (auto it = g_frame_.begin(); it != g_frame_.end();) {
+            if (it->first & (1 << 30)) { ++it; continue; }
+            hipGraphExecDestroy(it->second);
+            it = g_frame_.erase(it);
+        }
     }
     gp_ = gp;
 }
@@ -1668,8 +1737,11 @@ void Engine::set_gen_params(const GenParams &gp) {
 // meanwhile.  The pinned chunks are the context's (chunk_pool_), reused across calls.
 class Engine::ChunkStreamer {
 public:
-    ChunkStreamer(Engine &e, int S, int max_len, FrameCb cb, void *user, int interval, StreamState &st, bool *fault)
-        : e_(e), S_(S), max_len_(max_len), interval_(interval), cb_(cb), user_(user), st_(st), fault_(fault), n_live_(S) {}
+    // max_len: the stride of the caller's codes; cap[s]: slot s's own max_len
+    ChunkStreamer(Engine &e, int S, int max_len, std::vector<int> cap, FrameCb cb, void *user, int interval, StreamState &st,
+                  bool *fault)
+        : e_(e), S_(S), max_len_(max_len), cap_(std::move(cap)), interval_(interval), cb_(cb), user_(user), st_(st),
+          fault_(fault), n_live_(S) {}
     bool active() const { return cb_ && interval_ > 0; }
     // utterances the callback has not stopped (a fallback re-run regenerates utterances stopped earlier too: their
     // frames are returned)
@@ -1735,7 +1807,7 @@ private:
         if (e_.persist_error()) { *fault_ = true; return false; }
         for (int s = 0; s < S_; ++s) {
             if (st_.stop_at[s] >= 0) continue;
-            const int nf = c.done[s] >= 0 ? c.done[s] : max_len_;
+            const int nf = c.done[s] >= 0 ? std::min(c.done[s], cap_[s]) : cap_[s];
             if (nf < c.start + interval_) continue;   // partial chunks go to the final flush, as in the reference
             if (c.start + interval_ <= st_.delivered[s]) continue;   // delivered before a fallback re-run
             st_.delivered[s] = c.start + interval_;
@@ -1749,7 +1821,9 @@ private:
         return true;
     }
     Engine &e_;
-    const int S_, max_len_, interval_;
+    const int S_, max_len_;
+    const std::vector<int> cap_;
+    const int interval_;
     const FrameCb cb_;
     void *const user_;
     StreamState &st_;
@@ -1760,24 +1834,52 @@ private:
 };
 
 bool Engine::generate_once(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
-                           const GenParams &gp, int32_t *codes, int *n_frames, FrameCb on_frames, void *user,
-                           int interval, StreamState &st, bool *fault) {
+                           const GenParams &gp, const UttParams *up, int32_t *codes, int *n_frames, FrameCb on_frames,
+                           void *user, int interval, StreamState &st, bool *fault) {
     *fault = false;
     const int S = n_utt, H = c_.hidden, NCB = 16;
     for (int s = 0; s < S; ++s) n_frames[s] = 0;
     if (gp.max_len <= 0) return true;
-    int plen = 0;
-    if (!check_gen_args(S, tokens, n_tokens, speaker, gp, &plen)) return false;
-    set_gen_params(gp);
+    // the call-wide form: one record for every slot, one prompt length, the uniform prefill.  With records (up): each
+    // slot's own, the prompt rows packed and the ragged prefill
+    std::vector<UttParams> ups;
+    std::vector<int> posv;
+    if (up) {
+        if (!check_utt_args(S, tokens, n_tokens, speaker, gp, up, ups, posv)) return false;
+    } else {
+        int plen = 0;
+        if (!check_gen_args(S, tokens, n_tokens, speaker, gp, &plen)) return false;
+        ups.assign(S, UttParams{gp.language_id, gp.max_len, gp.rep_penalty, gp.temperature, gp.top_k, gp.force_frames});
+        posv.assign(S, plen);
+    }
+    const int plen = posv[0];   // (the call-wide form's)
+    int loop_len = 0;           // the longest record: a slot past its own max_len runs on, its frames are not returned
+    for (int s = 0; s < S; ++s) loop_len = std::max(loop_len, ups[s].max_len);
+    rec_on_ = up && S > 1;
+    if (!up) set_gen_params(gp);
+    else if (S == 1) {   // one slot: its utterance's values into the scalars the one-slot kernels read
+        GenParams g1 = gp;
+        g1.temperature = ups[0].temperature; g1.top_k = ups[0].top_k; g1.rep_penalty = ups[0].rep_penalty;
+        set_gen_params(g1);
+    }
     if (!set_seed(gp.seed, stream_)) return false;
     if (!ensure_prefill()) return false;
     Event e0, e1, e2;
     Q3T_HIP(hipEventRecord(e0, stream_));
     // ---- prompt, trailing and pad rows of every slot
     std::vector<PromptEntry> in(S);
-    for (int s = 0; s < S; ++s) in[s] = PromptEntry{tokens[s], n_tokens[s], speaker ? speaker[s] : nullptr, s, s};
-    std::vector<int> tl, ntok(n_tokens, n_tokens + S), force(S, gp.force_frames), posv(S, plen), frame0(S, 0), done0(S, -1);
-    if (!assemble_prompts(main_ps_, stream_, in, gp.language_id, &plen, tl)) return false;
+    for (int s = 0, row = 0; s < S; row += posv[s], ++s)
+        in[s] = PromptEntry{tokens[s], n_tokens[s], speaker ? speaker[s] : nullptr, s, up ? row : s * 10, ups[s].language_id};
+    std::vector<int> tl, pl, ntok(n_tokens, n_tokens + S), force(S), frame0(S, 0), done0(S, -1);
+    for (int s = 0; s < S; ++s) force[s] = ups[s].force_frames;
+    if (!assemble_prompts(main_ps_, stream_, in, pl, tl)) return false;
+    if (pl != posv) { set_error("generate: prefill length mismatch"); return false; }
+    if (rec_on_) {
+        std::vector<SelRec> &recs = main_ps_.rec_host;   // a member: the (pageable) source outlives the copy
+        recs.resize(S);
+        for (int s = 0; s < S; ++s) recs[s] = sel_rec(ups[s]);
+        Q3T_HIP(hipMemcpyAsync(sel_rec_, recs.data(), S * sizeof(SelRec), hipMemcpyHostToDevice, stream_));
+    }
     Q3T_HIP(hipMemcpyAsync(trailing_len_, tl.data(), S * 4, hipMemcpyHostToDevice, stream_));
     Q3T_HIP(hipMemcpyAsync(n_tokens_, ntok.data(), S * 4, hipMemcpyHostToDevice, stream_));
     Q3T_HIP(hipMemcpyAsync(force_, force.data(), S * 4, hipMemcpyHostToDevice, stream_));
@@ -1786,11 +1888,22 @@ bool Engine::generate_once(int n_utt, const int32_t *const *tokens, const int *n
     Q3T_HIP(hipMemsetAsync(codes_, 0, (size_t)S * codes_max_len_ * NCB * 4, stream_));
     // ---- prefill: one causal pass over the plen rows of every slot; the last row's hidden state / logits per slot
     Q3T_HIP(hipMemcpyAsync(pf_slot_, slot_iota_, S * 4, hipMemcpyDeviceToDevice, stream_));
-    if (!prefill(S, plen, main_ps_.rows, policy_slots_ > 0 ? policy_slots_ : S, stream_)) return false;
-    Q3T_HIP(hipMemcpy2DAsync(hidden_, H * 4, pf_hid_ + (size_t)(plen - 1) * H, (size_t)plen * H * 4, H * 4, S,
-                             hipMemcpyDeviceToDevice, stream_));
-    Q3T_HIP(hipMemcpy2DAsync(logits_, (size_t)c_.codec_vocab * 4, pf_logits_ + (size_t)(plen - 1) * c_.codec_vocab,
-                             (size_t)plen * c_.codec_vocab * 4, (size_t)c_.codec_vocab * 4, S, hipMemcpyDeviceToDevice, stream_));
+    const int S_main = policy_slots_ > 0 ? policy_slots_ : S;
+    if (up) {
+        if (!prefill_ragged(S, posv.data(), main_ps_.rows, S_main, stream_, main_ps_)) return false;
+        const size_t V = c_.codec_vocab;
+        for (int s = 0; s < S; ++s) {   // each slot's last row, by its packed offset
+            const size_t r = (size_t)in[s].row + posv[s] - 1;
+            Q3T_HIP(hipMemcpyAsync(hidden_ + (size_t)s * H, pf_hid_ + r * H, H * 4, hipMemcpyDeviceToDevice, stream_));
+            Q3T_HIP(hipMemcpyAsync(logits_ + s * V, pf_logits_ + r * V, V * 4, hipMemcpyDeviceToDevice, stream_));
+        }
+    } else {
+        if (!prefill(S, plen, main_ps_.rows, S_main, stream_)) return false;
+        Q3T_HIP(hipMemcpy2DAsync(hidden_, H * 4, pf_hid_ + (size_t)(plen - 1) * H, (size_t)plen * H * 4, H * 4, S,
+                                 hipMemcpyDeviceToDevice, stream_));
+        Q3T_HIP(hipMemcpy2DAsync(logits_, (size_t)c_.codec_vocab * 4, pf_logits_ + (size_t)(plen - 1) * c_.codec_vocab,
+                                 (size_t)plen * c_.codec_vocab * 4, (size_t)c_.codec_vocab * 4, S, hipMemcpyDeviceToDevice, stream_));
+    }
     if (!set_slot_state(S, posv, frame0)) return false;
     if (fused_select_ && !select_tokens(select_spec(SEL_CB0, gp_, 0, 0), logits_, S, stream_)) return false;
 #ifdef Q3T_DEV
@@ -1801,21 +1914,24 @@ bool Engine::generate_once(int n_utt, const int32_t *const *tokens, const int *n
     if (dbg) { fprintf(stderr, "[q3t] prefill enqueued (plen %d)\n", plen); fflush(stderr); }
     Q3T_HIP(hipEventRecord(e1, stream_));
     // ---- frame loop: one graph per frame; done flags polled every 16 frames
-    if (!graph_for(g_frame_, S, &Engine::enqueue_frame)) return false;
+    const int fkey = frame_key(S);
+    if (!graph_for_key(g_frame_, fkey, S, &Engine::enqueue_frame)) return false;
     if (!ensure_pinned((size_t)S * 4)) return false;
     int *done_h = static_cast<int *>(pin_);
-    ChunkStreamer streamer(*this, S, gp.max_len, on_frames, user, interval, st, fault);
+    std::vector<int> cap(S);
+    for (int s = 0; s < S; ++s) cap[s] = ups[s].max_len;
+    ChunkStreamer streamer(*this, S, gp.max_len, cap, on_frames, user, interval, st, fault);
     bool all_done = false;
-    for (int f = 0; f < gp.max_len && !all_done && streamer.n_live() > 0; ++f) {
+    for (int f = 0; f < loop_len && !all_done && streamer.n_live() > 0; ++f) {
         if (!persist_fault_hook(S, (persist_ ? 1 : 0) + (persist_cp_ ? 1 : 0))) return false;
-        Q3T_HIP(hipGraphLaunch(g_frame_[S], stream_));
+        Q3T_HIP(hipGraphLaunch(g_frame_[fkey], stream_));
         if (dbg) { fprintf(stderr, "[q3t] frame %d launched\n", f); fflush(stderr); }
         if (!streamer.after_frame(f)) return false;
-        if ((f + 1) % poll_every_ == 0 && f + 1 < gp.max_len) {
+        if ((f + 1) % poll_every_ == 0 && f + 1 < loop_len) {
             Q3T_HIP(hipMemcpyAsync(done_h, done_, S * 4, hipMemcpyDeviceToHost, stream_));
             Q3T_HIP(hipStreamSynchronize(stream_));
             all_done = true;
-            for (int s = 0; s < S; ++s) all_done = all_done && done_h[s] >= 0;
+            for (int s = 0; s < S; ++s) all_done = all_done && (done_h[s] >= 0 || f + 1 >= cap[s]);
         }
     }
     Q3T_HIP(hipEventRecord(e2, stream_));
@@ -1823,9 +1939,10 @@ bool Engine::generate_once(int n_utt, const int32_t *const *tokens, const int *n
     Q3T_HIP(hipMemcpyAsync(done_h, done_, S * 4, hipMemcpyDeviceToHost, stream_));
     // one 1-D copy per slot into the caller's [n_utt][max_len][16] buffer (a pitched 2-D copy into pageable host memory
     // was observed to overrun the destination under rocprofv3 on ROCm 7.2)
+    // (a slot's rows up to its own max_len: the rest of its stride stays as the caller passed it)
     for (int s = 0; s < S; ++s)
         Q3T_HIP(hipMemcpyAsync(codes + (size_t)s * gp.max_len * NCB, codes_ + (size_t)s * codes_max_len_ * NCB,
-                               (size_t)gp.max_len * NCB * 4, hipMemcpyDeviceToHost, stream_));
+                               (size_t)cap[s] * NCB * 4, hipMemcpyDeviceToHost, stream_));
     Q3T_HIP(hipStreamSynchronize(stream_));
     if (dbg) { fprintf(stderr, "[q3t] frame loop done\n"); fflush(stderr); }
     if (persist_error()) {
@@ -1833,7 +1950,7 @@ bool Engine::generate_once(int n_utt, const int32_t *const *tokens, const int *n
         *fault = true;
         return false;
     }
-    for (int s = 0; s < S; ++s) n_frames[s] = done_h[s] >= 0 ? std::min(done_h[s], gp.max_len) : gp.max_len;
+    for (int s = 0; s < S; ++s) n_frames[s] = done_h[s] >= 0 ? std::min(done_h[s], cap[s]) : cap[s];
     if (!streamer.flush(codes, n_frames)) return false;
     float ms1 = 0, ms2 = 0;
     hipEventElapsedTime(&ms1, e0, e1);
@@ -1872,23 +1989,28 @@ bool Engine::alloc_admission() {
 // rows, the causal prefill into the target slots, hidden / logits rows per target slot).  tgt_h: pinned
 // copy of tgt (alive until the batch has run); trailing_len[j]: the slot's trailing-text length
 bool Engine::admit_batch(const std::vector<int> &tgt, const std::vector<int> &utt, const int32_t *const *tokens,
-                         const int *n_tokens, const float *const *speaker, const GenParams &gp, int plen, hipStream_t as,
-                         int *tgt_h, std::vector<int> &trailing_len) {
+                         const int *n_tokens, const float *const *speaker, const std::vector<UttParams> &ups,
+                         const std::vector<int> &plen, bool ragged, hipStream_t as, int *tgt_h,
+                         std::vector<int> &trailing_len) {
     const int H = c_.hidden, a = (int)tgt.size();
     std::vector<PromptEntry> in(a);
-    for (int j = 0; j < a; ++j)
-        in[j] = PromptEntry{tokens[utt[j]], n_tokens[utt[j]], speaker ? speaker[utt[j]] : nullptr, tgt[j], j};
-    int got = 0;
-    if (!assemble_prompts(adm_ps_, as, in, gp.language_id, &got, trailing_len)) return false;
-    if (got != plen) { set_error("admit_batch: prefill length mismatch"); return false; }
+    std::vector<int> lens(a), got;
+    for (int j = 0, row = 0; j < a; row += lens[j], ++j) {
+        lens[j] = plen[utt[j]];
+        in[j] = PromptEntry{tokens[utt[j]], n_tokens[utt[j]], speaker ? speaker[utt[j]] : nullptr, tgt[j], ragged ? row : j * 10,
+                            ups[utt[j]].language_id};
+    }
+    if (!assemble_prompts(adm_ps_, as, in, got, trailing_len)) return false;
+    if (got != lens) { set_error("admit_batch: prefill length mismatch"); return false; }
     // the causal prefill of the batch with the running batch's kernels (S_main = q_slots_), K/V straight into the
     // target slots' rows [0, plen)
     for (int j = 0; j < a; ++j) tgt_h[j] = tgt[j];
     Q3T_HIP(hipMemcpyAsync(pf_slot_, tgt_h, a * 4, hipMemcpyHostToDevice, as));
-    if (!prefill(a, plen, adm_ps_.rows, q_slots_, as)) return false;
+    if (ragged ? !prefill_ragged(a, lens.data(), adm_ps_.rows, q_slots_, as, adm_ps_) : !prefill(a, lens[0], adm_ps_.rows, q_slots_, as))
+        return false;
     const int V = c_.codec_vocab;
     for (int j = 0; j < a; ++j) {
-        const size_t r = (size_t)j * plen + plen - 1;
+        const size_t r = (ragged ? (size_t)in[j].row : (size_t)j * lens[0]) + lens[j] - 1;
         Q3T_HIP(hipMemcpyAsync(ahidden_ + (size_t)tgt[j] * H, pf_hid_ + r * H, H * 4, hipMemcpyDeviceToDevice, as));
         Q3T_HIP(hipMemcpyAsync(alogits_ + (size_t)tgt[j] * V, pf_logits_ + r * V, (size_t)V * 4, hipMemcpyDeviceToDevice, as));
     }
@@ -1897,13 +2019,18 @@ bool Engine::admit_batch(const std::vector<int> &tgt, const std::vector<int> &ut
 
 // slot k joins the frame loop (main stream, between two frames, after its admission batch): per-slot state, the
 // last prefill step's hidden state, and the CB0 of its first frame selected from the last prefill logits.
-// state_h: pinned [8]
-bool Engine::activate_slot(int k, uint64_t utt, int trailing_len, int n_tok, const GenParams &gp, int plen, int *state_h,
+// state_h: pinned [16]
+bool Engine::activate_slot(int k, uint64_t utt, int trailing_len, int n_tok, const UttParams &up, int plen, int *state_h,
                            bool deliveries) {
     const int H = c_.hidden, NCB = 16;
-    state_h[0] = trailing_len; state_h[1] = n_tok; state_h[2] = gp.force_frames; state_h[3] = -1;
+    state_h[0] = trailing_len; state_h[1] = n_tok; state_h[2] = up.force_frames; state_h[3] = -1;
     state_h[4] = plen; state_h[5] = 0;
     std::memcpy(state_h + 6, &utt, 8);
+    state_h[8] = up.max_len;
+    const SelRec rec = sel_rec(up);
+    std::memcpy(state_h + 12, &rec, sizeof rec);
+    if (own_max_len_) Q3T_HIP(hipMemcpyAsync(slot_max_len_ + k, state_h + 8, 4, hipMemcpyHostToDevice, stream_));
+    if (rec_on_) Q3T_HIP(hipMemcpyAsync(sel_rec_ + k, state_h + 12, sizeof rec, hipMemcpyHostToDevice, stream_));
     Q3T_HIP(hipMemcpyAsync(trailing_len_ + k, state_h + 0, 4, hipMemcpyHostToDevice, stream_));
     Q3T_HIP(hipMemcpyAsync(n_tokens_ + k, state_h + 1, 4, hipMemcpyHostToDevice, stream_));
     Q3T_HIP(hipMemcpyAsync(force_ + k, state_h + 2, 4, hipMemcpyHostToDevice, stream_));
@@ -1919,6 +2046,7 @@ bool Engine::activate_slot(int k, uint64_t utt, int trailing_len, int n_tok, con
     sp.tokens += (size_t)k * 16; sp.codes += (size_t)k * codes_max_len_ * NCB; sp.frame += k; sp.done += k; sp.utt += k;
     sp.seen += (size_t)k * c_.codec_vocab; sp.n_tokens += k; sp.force_frames += k;
     if (sp.ticket) sp.ticket += k;
+    if (sp.rec) sp.rec += k;
     return select_tokens(sp, alogits_ + (size_t)k * c_.codec_vocab, 1, stream_);
 }
 
@@ -1930,9 +2058,11 @@ bool Engine::activate_slot(int k, uint64_t utt, int trailing_len, int n_tok, con
 // are known to be fault-free.
 class Engine::QueueStreamer {
 public:
-    QueueStreamer(Engine &e, int S, int n_utt, int max_len, QueueCb cb, void *user, int interval, QueueState &st, bool *fault)
-        : e_(e), S_(S), max_len_(max_len), interval_(interval), cb_(cb), user_(user), st_(st), fault_(fault),
-          run_(n_utt) {}
+    // own_max_len: a collection clamps each slot's frames to its own max_len (slot_max_len_) as well
+    QueueStreamer(Engine &e, int S, int n_utt, int max_len, bool own_max_len, QueueCb cb, void *user, int interval,
+                  QueueState &st, bool *fault)
+        : e_(e), S_(S), max_len_(max_len), interval_(interval), own_max_len_(own_max_len), cb_(cb), user_(user), st_(st),
+          fault_(fault), run_(n_utt) {}
     bool active() const { return cb_ != nullptr; }
     int interval() const { return interval_; }
     bool begin() {   // the staging chunk with a clear error word
@@ -1968,6 +2098,7 @@ public:
         q.header = stage + (size_t)S_ * interval_ * NCB;
         q.error = stage + stage_ints() - 1;
         q.interval = interval_; q.codes_max_len = e_.codes_max_len_; q.max_len = max_len_;
+        if (own_max_len_) q.slot_max_len = e_.slot_max_len_;
         if (!queue_collect(q, S_, e_.stream_)) return false;
         Q3T_HIP(hipMemcpyAsync(c.rows, stage, stage_ints() * 4, hipMemcpyDeviceToHost, e_.stream_));
         Q3T_HIP(hipEventRecord(c.ev, e_.stream_));
@@ -2017,6 +2148,7 @@ private:
     }
     Engine &e_;
     const int S_, max_len_, interval_;
+    const bool own_max_len_;
     const QueueCb cb_;
     void *const user_;
     QueueState &st_;
@@ -2028,37 +2160,64 @@ private:
 };
 
 bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
-                                 const GenParams &gp, int32_t *codes, int *n_frames, int max_active, bool *faulted,
-                                 QueueCb on_batch, void *user, int interval, QueueState &qst) {
+                                 const GenParams &gp, const UttParams *up, int32_t *codes, int *n_frames, int max_active,
+                                 bool *faulted, QueueCb on_batch, void *user, int interval, QueueState &qst) {
     *faulted = false;
     if (n_utt <= 0) return true;
     const int S = std::min(max_slots_, n_utt), NCB = 16;
     if (max_active <= 0 || max_active > S) max_active = S;
     for (int u = 0; u < n_utt; ++u) n_frames[u] = 0;
     if (gp.max_len <= 0) return true;
-    int plen = 0;
-    if (!check_gen_args(n_utt, tokens, n_tokens, speaker, gp, &plen)) return false;
+    // the call-wide form: one record and one prompt length for every utterance.  With records (up): each utterance's own;
+    // admission batches then pack their prompt rows and run the ragged prefill
+    std::vector<UttParams> ups;
+    std::vector<int> plens;
+    if (up) {
+        if (!check_utt_args(n_utt, tokens, n_tokens, speaker, gp, up, ups, plens)) return false;
+    } else {
+        int plen0 = 0;
+        if (!check_gen_args(n_utt, tokens, n_tokens, speaker, gp, &plen0)) return false;
+        ups.assign(n_utt, UttParams{gp.language_id, gp.max_len, gp.rep_penalty, gp.temperature, gp.top_k, gp.force_frames});
+        plens.assign(n_utt, plen0);
+    }
+    bool mixed_plen = false;
+    for (int u = 0; u < n_utt; ++u) mixed_plen = mixed_plen || plens[u] != plens[0];
+    // where a free slot waits: above the rows any prefill of the call writes
+    const int plen = mixed_plen ? 10 : plens[0];
     if (gp.max_len > codes_max_len_) { set_error("max_len exceeds the code buffer"); return false; }
     if (!alloc_admission()) return false;
     q_slots_ = S;
     // the single-slot context runs persistent kernels, which need the whole device: admissions go on the main stream
     hipStream_t as = (S == 1 && persist_enabled()) ? stream_ : astream_;
-    set_gen_params(gp);
+    rec_on_ = up && S > 1;
+    own_max_len_ = up != nullptr;
+    // one slot with records: each utterance's values go into the scalars when it takes the slot (activate below)
+    GenParams g1 = gp;
+    auto one_slot_params = [&](const UttParams &r) {
+        if (r.temperature == gp_.temperature && r.top_k == gp_.top_k && r.rep_penalty == gp_.rep_penalty) return;
+        hipStreamSynchronize(stream_);   // the frame graphs about to be dropped may still run
+        g1.temperature = r.temperature; g1.top_k = r.top_k; g1.rep_penalty = r.rep_penalty;
+        set_gen_params(g1);
+    };
+    if (!up) set_gen_params(gp);
     if (!set_seed(gp.seed, stream_)) return false;
     // the finished utterances' codes, copied to the caller once at the end (device scratch kept by the context)
     // (a caller that takes deliveries may pass no codes buffer: nothing is parked then)
     if (codes && !ensure_qout((size_t)n_utt * gp.max_len * NCB * 4)) return false;
     int32_t *out_dev = codes ? static_cast<int32_t *>(qout_) : nullptr;
-    QueueStreamer qs(*this, S, n_utt, gp.max_len, on_batch, user, interval, qst, faulted);
+    QueueStreamer qs(*this, S, n_utt, gp.max_len, up != nullptr, on_batch, user, interval, qst, faulted);
     if (qs.active() && !qs.begin()) return false;
-    if (qs.active() && out_dev)   // an aborted call copies out rows of utterances that never ran
+    if ((qs.active() || up) && out_dev)   // an aborted call copies out rows of utterances that never ran (and with records
+                                          // a release parks only the utterance's own max_len rows)
         Q3T_HIP(hipMemsetAsync(out_dev, 0, (size_t)n_utt * gp.max_len * NCB * 4, stream_));
-    // [S][8] activation staging, [S] done flags, [S] admission targets, one constant 0 (parking): pinned, kept
-    if (!ensure_pinned(((size_t)S * 10 + 1) * 4)) return false;
+    // [S][16] activation staging, [S] done flags, [S] admission targets, the constants 0 (parking) and the waiting
+    // position: pinned, kept
+    if (!ensure_pinned(((size_t)S * 18 + 2) * 4)) return false;
     int *pin = static_cast<int *>(pin_);
-    int *done_h = pin + (size_t)S * 8, *tgt_h = pin + (size_t)S * 9, *park = pin + (size_t)S * 10;
-    *park = 0;
-    Event aev(hipEventDisableTiming), pev(hipEventDisableTiming);
+    int *done_h = pin + (size_t)S * 16, *tgt_h = pin + (size_t)S * 17, *park = pin + (size_t)S * 18;
+    park[0] = 0;
+    park[1] = plen;
+    Event aev(hipEventDisableTiming), pev(hipEventDisableTiming), rev(hipEventDisableTiming);
     // every exit drains both streams and leaves the context as generate() expects it: kernels chosen by the call's
     // own slot count, sampling keyed by slot index
     ScopeExit restore([&] {
@@ -2090,7 +2249,13 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         for (int k = 0; k < S && next + (int)tgt.size() < n_utt && n_busy + (int)tgt.size() < max_active; ++k)
             if (state[k] == FREE) { tgt.push_back(k); utt.push_back(next + (int)tgt.size() - 1); }
         if (tgt.empty()) return true;
-        if (!admit_batch(tgt, utt, tokens, n_tokens, speaker, gp, plen, as, tgt_h, batch_tl)) return false;
+        if (mixed_plen && as != stream_) {
+            // a released slot was moved to the waiting position on the main stream (release): the batch's prefill, which
+            // may write more rows than the slot's last utterance had, starts behind that
+            Q3T_HIP(hipEventRecord(rev, stream_));
+            Q3T_HIP(hipStreamWaitEvent(as, rev, 0));
+        }
+        if (!admit_batch(tgt, utt, tokens, n_tokens, speaker, ups, plens, up != nullptr, as, tgt_h, batch_tl)) return false;
         Q3T_HIP(hipEventRecord(aev, as));
         for (size_t j = 0; j < tgt.size(); ++j) {
             state[tgt[j]] = PENDING;
@@ -2106,7 +2271,8 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         if (as != stream_) Q3T_HIP(hipStreamWaitEvent(stream_, aev, 0));
         for (int k : batch_tgt) {
             const int u = slot_utt[k];
-            if (!activate_slot(k, (uint64_t)u, tl[k], n_tokens[u], gp, plen, pin + (size_t)k * 8, qs.active())) return false;
+            if (up && S == 1) one_slot_params(ups[u]);
+            if (!activate_slot(k, (uint64_t)u, tl[k], n_tokens[u], ups[u], plens[u], pin + (size_t)k * 16, qs.active())) return false;
             state[k] = ACTIVE;
             started[k] = f;
         }
@@ -2123,8 +2289,9 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         int hi = 0;
         for (int k = 0; k < S; ++k) if (state[k] != FREE) hi = k + 1;
         int se = fam < S ? std::max(fam, std::min(S, (hi + 7) / 8 * 8)) : S;
-        if (!graph_for_key(g_frame_, se + 65536 * S, se, &Engine::enqueue_frame)) return false;
-        *g = g_frame_[se + 65536 * S];
+        const int key = frame_key(se + 65536 * S);
+        if (!graph_for_key(g_frame_, key, se, &Engine::enqueue_frame)) return false;
+        *g = g_frame_[key];
         return true;
     };
     // an utterance leaves its slot (ended, or cancelled by the delivery callback): its codes are parked for the
@@ -2133,9 +2300,11 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         const int u = slot_utt[k];
         if (out_dev)
             Q3T_HIP(hipMemcpyAsync(out_dev + (size_t)u * gp.max_len * NCB, codes_ + (size_t)k * codes_max_len_ * NCB,
-                                   (size_t)gp.max_len * NCB * 4, hipMemcpyDeviceToDevice, stream_));
+                                   (size_t)ups[u].max_len * NCB * 4, hipMemcpyDeviceToDevice, stream_));
         if (park_slot)   // still running: park the slot (no selection, no advance)
             Q3T_HIP(hipMemcpyAsync(done_ + k, park, 4, hipMemcpyHostToDevice, stream_));
+        if (mixed_plen)   // its successor's prompt may be longer than the position it stopped at: back to the waiting one
+            Q3T_HIP(hipMemcpyAsync(pos_ + k, park + 1, 4, hipMemcpyHostToDevice, stream_));
         state[k] = FREE;
         slot_utt[k] = -1;
         --n_busy;
@@ -2188,7 +2357,7 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
             bool any = false;
             for (int k = 0; k < S; ++k) {   // done_h: after frame f-1
                 const int ran = f - 1 - started[k];
-                sel[k] = state[k] == ACTIVE && !(done_h[k] < 0 && ran < gp.max_len);
+                sel[k] = state[k] == ACTIVE && !(done_h[k] < 0 && ran < ups[slot_utt[k]].max_len);
                 any = any || sel[k];
             }
             // the rest of the finished slots' frames, before a slot is parked or handed to a successor
@@ -2196,7 +2365,8 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
             for (int k = 0; k < S; ++k) {
                 if (!sel[k]) continue;
                 const int d = done_h[k];
-                n_frames[slot_utt[k]] = d >= 0 ? std::min(d, gp.max_len) : gp.max_len;
+                const int cap = ups[slot_utt[k]].max_len;
+                n_frames[slot_utt[k]] = d >= 0 ? std::min(d, cap) : cap;
                 if (!release(k, d < 0)) return false;   // d < 0: stopped at max_len
             }
         }
@@ -2235,21 +2405,23 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
 
 bool Engine::generate_queue(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                             const GenParams &gp, int32_t *codes, int *n_frames, int max_active, QueueCb on_batch, void *user,
-                            int interval) {
+                            int interval, const UttParams *up) {
+    for (int u = 0; u < n_utt; ++u) n_frames[u] = 0;
     if (!on_batch && !codes && n_utt > 0) { set_error("generate_queue: no codes buffer and no callback"); return false; }
     if (on_batch && interval <= 0) { set_error("generate_queue: the delivery interval must be > 0"); return false; }
     const int S = std::min(max_slots_, std::max(n_utt, 1));
     DeviceLock lk(persist_exclusive(S), device_);
     QueueState qst(std::max(n_utt, 0));
     bool fault = false;
-    if (generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, codes, n_frames, max_active, &fault, on_batch, user, interval, qst))
+    ScopeExit rec_off([&] { rec_on_ = false; });
+    if (generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, up, codes, n_frames, max_active, &fault, on_batch, user, interval, qst))
         return true;
     if (!fault) return false;
     // a single-slot persistent launch gave up on a hand-off: continue on the launch-per-op graphs, which are
     // bit-identical, and re-run the queue (sampling is keyed by utterance, so the re-run gives the same codes; what
     // was delivered, cancelled or finished before the fault is kept in qst and not delivered again)
     if (!persist_recover()) return false;
-    return generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, codes, n_frames, max_active, &fault, on_batch, user, interval, qst);
+    return generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, up, codes, n_frames, max_active, &fault, on_batch, user, interval, qst);
 }
 
 bool Engine::time_stage(int stage, int S, int pos, int iters, double *ms) {
@@ -2302,6 +2474,30 @@ bool Engine::talker_prefill(int n_utt, int n_rows, const float *embd, int family
     if (logits)
         Q3T_HIP(hipMemcpy2DAsync(logits, (size_t)V * 4, pf_logits_ + (size_t)(n_rows - 1) * V, (size_t)n_rows * V * 4,
                                  (size_t)V * 4, n_utt, hipMemcpyDeviceToHost, stream_));
+    Q3T_HIP(hipStreamSynchronize(stream_));
+    return true;
+}
+
+bool Engine::talker_prefill_ragged(int n_utt, const int *n_rows, const float *embd, int family_slots, float *hidden,
+                                   float *logits) {
+    if (n_utt <= 0 || n_utt > max_slots_) { set_error("bad utterance count"); return false; }
+    if (family_slots < 0 || family_slots > 4096) { set_error("bad family slot count"); return false; }
+    int total = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        if (n_rows[u] <= 0 || n_rows[u] > 10 || n_rows[u] > max_ctx_) { set_error("prefill rows must be in [1, 10]"); return false; }
+        total += n_rows[u];
+    }
+    const int H = c_.hidden, V = c_.codec_vocab;
+    DeviceLock lk(false, device_);
+    if (!ensure_prefill()) return false;
+    Q3T_HIP(hipMemcpyAsync(main_ps_.rows, embd, (size_t)total * H * 4, hipMemcpyHostToDevice, stream_));
+    Q3T_HIP(hipMemcpyAsync(pf_slot_, slot_iota_, n_utt * 4, hipMemcpyDeviceToDevice, stream_));
+    if (!prefill_ragged(n_utt, n_rows, main_ps_.rows, family_slots > 0 ? family_slots : n_utt, stream_, main_ps_)) return false;
+    if (hidden) Q3T_HIP(hipMemcpyAsync(hidden, pf_hid_, (size_t)total * H * 4, hipMemcpyDeviceToHost, stream_));
+    if (logits)
+        for (int u = 0, row = 0; u < n_utt; row += n_rows[u], ++u)   // each utterance's last row
+            Q3T_HIP(hipMemcpyAsync(logits + (size_t)u * V, pf_logits_ + (size_t)(row + n_rows[u] - 1) * V, (size_t)V * 4,
+                                   hipMemcpyDeviceToHost, stream_));
     Q3T_HIP(hipStreamSynchronize(stream_));
     return true;
 }

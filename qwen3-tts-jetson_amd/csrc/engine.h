@@ -39,6 +39,16 @@ struct GenParams {
     int force_frames = 0;      // bench: mask EOS until this many frames are produced
 };
 
+// one utterance's own values (q3t_utt_params): what GenParams holds for the whole call, except the seed
+struct UttParams {
+    int language_id = 2050;    // < 0: the nothink prompt (one row shorter)
+    int max_len = 0;           // 1 .. GenParams::max_len
+    float rep_penalty = 1.05f;
+    float temperature = 0.9f;
+    int top_k = 50;
+    int force_frames = 0;
+};
+
 struct DevLayer {
     uint16_t *qkv = nullptr, *o = nullptr, *gu = nullptr, *down = nullptr;
     float *attn_norm = nullptr, *ffn_norm = nullptr, *qn = nullptr, *kn = nullptr;
@@ -55,18 +65,22 @@ struct PromptScratch {
     uint16_t *h = nullptr;         // fc1 output (f16)
     float *out = nullptr;          // projected text rows
     RowRecipe *recipe = nullptr;
-    float *rows = nullptr;         // prompt rows [max_slots][10][H]
+    float *rows = nullptr;         // prompt rows [max_slots][10][H] (ragged assemblies pack them: PromptEntry::row)
     float *spk = nullptr;          // speaker rows [max_slots][H], by target slot
     std::vector<int> idx_host;     // the (pageable) sources of the idx / recipe uploads: they outlive the copies
     std::vector<RowRecipe> recipe_host;
+    std::vector<int> rag_host;     // ragged prefill: [n] row offsets, then [n] row counts
+    std::vector<SelRec> rec_host;  // per-utterance sampling: the slots' records of a lock-step call
 };
-// one utterance of an assembly: its speaker row (or null), the slot whose trailing / pad rows it fills, and the
-// index of its prompt rows in PromptScratch::rows
+// one utterance of an assembly: its speaker row (or null), the slot whose trailing / pad rows it fills, the first
+// row of its prompt in PromptScratch::rows (10 x its index in the uniform layout, the running sum of the lengths in
+// the packed one) and its language
 struct PromptEntry {
     const int32_t *tokens;
     int n_tokens;
     const float *speaker;
     int slot, row;
+    int language_id;
 };
 
 // Path-selection knobs, read once from the environment when a context is created (the reference's own pattern:
@@ -148,9 +162,11 @@ public:
     // newest `interval` frames, plus one final flush of the remainder; returning 0 stops that utterance
     // (src/tts_transformer.cpp:2517-2523, 2563-2570)
     typedef int (*FrameCb)(void *user, int slot, const int32_t *codes, int n_frames, int n_codebooks);
+    // up (q3t_generate_utt / q3t_generate_queue_utt): [n_utt] records; gp then gives only max_len (the stride of codes and
+    // the cap of every record) and the seed, and speaker[u] may be null for any subset.  Null: the call-wide gp.
     bool generate(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                   const GenParams &gp, int32_t *codes, int *n_frames, FrameCb on_frames = nullptr,
-                  void *user = nullptr, int interval = 40);
+                  void *user = nullptr, int interval = 40, const UttParams *up = nullptr);
     // continuous batching: n_utt utterances (any number) through min(max_slots, n_utt) slots, at
     // most max_active of them at a time.  A slot whose utterance ended (EOS or max_len) is refilled with the next
     // queued utterance between two frames: its text rows are projected, its prefill rows assembled and replayed
@@ -170,7 +186,7 @@ public:
                            const int32_t *final, int32_t *stop);
     bool generate_queue(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                         const GenParams &gp, int32_t *codes, int *n_frames, int max_active, QueueCb on_batch = nullptr,
-                        void *user = nullptr, int interval = 0);
+                        void *user = nullptr, int interval = 0, const UttParams *up = nullptr);
     // fill this context's weight arenas (laid out with recv_weights) from another context's, device to device
     bool copy_weights_from(Engine &src);
     // after the weight arenas of a receiving context were filled by a broadcast: build what is derived from the weights
@@ -179,6 +195,8 @@ public:
 
     // ---- stage entry points (host buffers) used by the parity tests
     bool talker_prefill(int n_utt, int n_rows, const float *embd, int family_slots, float *hidden, float *logits);
+    // n_rows[u] in [1, 10] packed rows per utterance: the ragged form of the prefill (hidden packed, logits [n_utt][V])
+    bool talker_prefill_ragged(int n_utt, const int *n_rows, const float *embd, int family_slots, float *hidden, float *logits);
     bool talker_forward(int S, const float *embd, const int *pos, float *hidden, float *logits);
     bool codepred_frame(int S, const float *hidden, const int *cb0, float temperature, int top_k, uint64_t seed,
                         int frame, int32_t *codes15, float *logits_all);
@@ -235,12 +253,12 @@ private:
     };
     class ChunkStreamer;   // the frame callback's chunk copies and deliveries (engine.cpp)
     bool generate_once(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
-                       const GenParams &gp, int32_t *codes, int *n_frames, FrameCb on_frames, void *user, int interval,
-                       StreamState &st, bool *fault);
+                       const GenParams &gp, const UttParams *up, int32_t *codes, int *n_frames, FrameCb on_frames, void *user,
+                       int interval, StreamState &st, bool *fault);
     class QueueStreamer;   // the queue callback's collections and deliveries (engine.cpp)
     bool generate_queue_once(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
-                             const GenParams &gp, int32_t *codes, int *n_frames, int max_active, bool *faulted,
-                             QueueCb on_batch, void *user, int interval, QueueState &qst);
+                             const GenParams &gp, const UttParams *up, int32_t *codes, int *n_frames, int max_active,
+                             bool *faulted, QueueCb on_batch, void *user, int interval, QueueState &qst);
     // host scratch kept across calls (a per-call hipFree / hipHostFree synchronises the whole device)
     struct PinnedChunk { size_t cap = 0; int32_t *codes = nullptr; hipEvent_t ev = nullptr; };
     std::vector<PinnedChunk> chunk_pool_;   // streaming chunks of generate() and of the queue's deliveries
@@ -278,15 +296,28 @@ private:
     bool enqueue_frame(int S, hipStream_t s);
     bool enqueue_text_projection(int n_rows, hipStream_t s, const PromptScratch &ps);
     // the prompt rows (PromptScratch::rows), trailing-text rows and pad row of every entry, assembled on stream s;
-    // plen: the prompt length in rows (prompt_len), trailing_len: per entry
-    bool assemble_prompts(PromptScratch &ps, hipStream_t s, const std::vector<PromptEntry> &in, int language_id,
-                          int *plen, std::vector<int> &trailing_len);
+    // plen: each entry's prompt length in rows (prompt_len), trailing_len: per entry
+    bool assemble_prompts(PromptScratch &ps, hipStream_t s, const std::vector<PromptEntry> &in, std::vector<int> &plen,
+                          std::vector<int> &trailing_len);
     static int prompt_len(int language_id, bool has_spk);
     bool alloc_prompt_scratch(PromptScratch &ps, float *spk);
     // the checks shared by generate() and generate_queue(); plen: the prompt length
     bool check_gen_args(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                         const GenParams &gp, int *plen);
+    // the same with a record per utterance: every record is validated before anything runs; ups: the records with
+    // max_len resolved, plen: per utterance
+    bool check_utt_args(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
+                        const GenParams &gp, const UttParams *up, std::vector<UttParams> &ups, std::vector<int> &plen);
     void set_gen_params(const GenParams &gp);   // gp_ = gp; drops the frame graphs that baked other sampling values
+    // per-utterance sampling: the [max_slots] records the batched selections read while rec_on_ (select_spec); a one-slot
+    // run leaves it off and bakes its utterance's values into the scalars (set_gen_params)
+    SelRec *sel_rec_ = nullptr;
+    bool rec_on_ = false;
+    int *slot_max_len_ = nullptr;   // [max_slots] each slot's own max_len (queue deliveries), written while own_max_len_
+    bool own_max_len_ = false;      // the running queue has a record per utterance
+    static SelRec sel_rec(const UttParams &u) { return SelRec{u.temperature, u.top_k, u.rep_penalty, 0}; }
+    // frame-graph cache key: graphs captured with and without the record pointer are both kept
+    int frame_key(int key) const { return key + (rec_on_ ? (1 << 30) : 0); }
     template <class F> hipGraphExec_t capture(hipStream_t s, F &&enqueue);   // null with the error set
     bool graph_for(std::map<int, hipGraphExec_t> &cache, int S, bool (Engine::*fn)(int, hipStream_t));
     bool graph_for_key(std::map<int, hipGraphExec_t> &cache, int key, int S, bool (Engine::*fn)(int, hipStream_t));
@@ -294,9 +325,13 @@ private:
     bool set_slot_state(int S, const std::vector<int> &pos, const std::vector<int> &frame);
     // causal prefill (one pass over the prompt rows of n_utt utterances, K/V written into slots pf_slot_[u])
     bool ensure_prefill();
-    bool enqueue_prefill_rows(int key, hipStream_t s);
+    bool enqueue_prefill_rows(int S_main, int n_utt, int plen, int rows, hipStream_t s);   // plen 0: the ragged form
     bool prefill(int n_utt, int plen, const float *src, int S_main, hipStream_t s);
+    // ragged form: src holds the packed rows; lens[u] in [1, 10].  pf_off_ / pf_len_ are filled from ps.rag_host
+    bool prefill_ragged(int n_utt, const int *lens, const float *src, int S_main, hipStream_t s, PromptScratch &ps);
     std::map<int, hipGraphExec_t> g_prefill_;
+    std::map<long long, hipGraphExec_t> g_prefill_rag_;   // key: (family, n_utt, total rows)
+    int *pf_off_ = nullptr, *pf_len_ = nullptr;           // [max_slots] beside pf_slot_
     float *pf_x_ = nullptr, *pf_qkv_ = nullptr, *pf_parts_ = nullptr, *pf_hid_ = nullptr, *pf_logits_ = nullptr;
     uint16_t *pf_xn_ = nullptr, *pf_attn_ = nullptr, *pf_hmlp_ = nullptr;
     int *pf_slot_ = nullptr, *slot_iota_ = nullptr;
@@ -304,9 +339,9 @@ private:
     // activation of each slot on the main stream between two frames
     bool alloc_admission();
     bool admit_batch(const std::vector<int> &tgt, const std::vector<int> &utt, const int32_t *const *tokens,
-                     const int *n_tokens, const float *const *speaker, const GenParams &gp, int plen, hipStream_t as,
-                     int *tgt_h, std::vector<int> &trailing_len);
-    bool activate_slot(int slot, uint64_t utt, int trailing_len, int n_tok, const GenParams &gp, int plen, int *state_h,
+                     const int *n_tokens, const float *const *speaker, const std::vector<UttParams> &ups,
+                     const std::vector<int> &plen, bool ragged, hipStream_t as, int *tgt_h, std::vector<int> &trailing_len);
+    bool activate_slot(int slot, uint64_t utt, int trailing_len, int n_tok, const UttParams &up, int plen, int *state_h,
                        bool deliveries = false);
     hipStream_t astream_ = nullptr;
     int *delivered_ = nullptr, *qmask_ = nullptr;   // queue deliveries: per-slot frames collected so far; a collection's slot mask

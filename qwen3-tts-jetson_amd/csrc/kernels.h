@@ -19,6 +19,13 @@ enum Act { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_SWIGLU = 3 };
 // Used by the standalone select launch (one 256-thread workgroup per slot) and fused into the head GEMV, where
 // the last head workgroup to finish (arrival ticket) selects in the same launch.
 enum SelMode { SEL_NONE = 0, SEL_CP = 1, SEL_CB0 = 2 };
+// one slot's sampling values (per-utterance sampling): what the scalars of SelectSpec hold for a homogeneous call
+struct alignas(16) SelRec {
+    float temperature;
+    int top_k;
+    float rep;
+    int reserved;
+};
 struct SelectSpec {
     int mode = SEL_NONE;
     int V = 0;
@@ -42,6 +49,9 @@ struct SelectSpec {
     const int *force_frames = nullptr;  // [S] (bench: EOS masked while frame < force)
     int eos = 2150;
     float rep = 1.05f;
+    // optional [S] per-slot {temperature, top_k, rep}; null: the scalars above.  Read by the batched families only
+    // (select.h REC); the one-slot persistent kernels always take the scalars
+    const SelRec *rec = nullptr;
 };
 // standalone: logits [S][V] -> one workgroup per slot
 bool select_tokens(const SelectSpec &sp, const float *logits, int S, hipStream_t s);
@@ -176,6 +186,9 @@ struct PrefillAttnParams {
     const int *slot = nullptr;    // [n_utt] cache slot of each utterance
     int n_ctx = 0, n_utt = 0, plen = 0, nH = 0, nKV = 0, D = 0;
     uint16_t *out = nullptr;      // [n_utt * plen][nH * D] f16 (the O-projection input)
+    // ragged form (both set, or both null: the uniform plen above): utterance u holds row_count[u] <= 16 rows, its
+    // first at row row_off[u] of qkv / out (packed rows)
+    const int *row_off = nullptr, *row_count = nullptr;
 };
 bool prefill_attn(const PrefillAttnParams &p, hipStream_t s);
 constexpr int ATTN_MAX_SPLITS = 160;   // n_ctx <= 10240
@@ -197,6 +210,7 @@ struct QueueCollect {
     int32_t *rows;
     int *header, *error;
     int interval, codes_max_len, max_len;
+    const int *slot_max_len = nullptr;   // optional [S]: each slot's own max_len in place of max_len
 };
 bool queue_collect(const QueueCollect &q, int S, hipStream_t s);
 

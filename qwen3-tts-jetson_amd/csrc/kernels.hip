@@ -11,14 +11,17 @@
 namespace q3t {
 
 // ======================================================================================= token selection
+// REC: the slots' sampling records (sp.rec, per-utterance sampling); launched without it when sp.rec is null
+template <bool REC>
 __global__ void __launch_bounds__(256) k_select(const SelectSpec sp, const float *logits) {
     __shared__ SelLds S;
-    select_slot<false>(sp, logits + (size_t)blockIdx.x * sp.V, blockIdx.x, S);
+    select_slot<false, REC>(sp, logits + (size_t)blockIdx.x * sp.V, blockIdx.x, S);
 }
 bool select_tokens(const SelectSpec &sp, const float *logits, int S, hipStream_t s) {
     if (sp.V > 256 * SEL_VPT_MAX || sp.V <= 0) { set_error("select: vocab must be in (0, 4096]"); return false; }
     if (S <= 0) return true;
-    hipLaunchKernelGGL(k_select, dim3(S), dim3(256), 0, s, sp, logits);
+    if (sp.rec) hipLaunchKernelGGL(k_select<true>, dim3(S), dim3(256), 0, s, sp, logits);
+    else hipLaunchKernelGGL(k_select<false>, dim3(S), dim3(256), 0, s, sp, logits);
     Q3T_HIP(hipGetLastError());
     return true;
 }
@@ -86,7 +89,8 @@ __global__ void __launch_bounds__(64) k_queue_collect(const QueueCollect q) {
     const int k = blockIdx.x;
     if (!q.mask[k]) return;
     const int done = q.done[k], delivered = q.delivered[k];
-    const int avail = min(done >= 0 ? done : q.frame[k], q.max_len);
+    const int cap = q.slot_max_len ? min(q.slot_max_len[k], q.max_len) : q.max_len;   // (<= codes_max_len: the rows read)
+    const int avail = min(done >= 0 ? done : q.frame[k], cap);
     const int n = avail - delivered;
     if (delivered < 0 || n < 0 || n > q.interval) {   // never expected: nothing is copied, the host sees the word
         if (threadIdx.x == 0) { *q.error = 1; q.header[k] = 0; }
@@ -263,13 +267,13 @@ __global__ void __launch_bounds__(256) k_resid_norm(const ResidNorm r) {
 }
 // W as k_resid_norm's.  F32TAB: the nt = 1 source is an f32 row of EmbedNorm::ftab (the 1.7B code predictor's
 // projected pass inputs) instead of an f16 table row.
-template <int W, bool F32TAB>
+template <int W, bool F32TAB, bool REC>
 __global__ void __launch_bounds__(256) k_select_embed_norm(const SelectSpec sp, const float *logits, const EmbedNorm en) {
     __shared__ SelLds S;
     __shared__ double scr[4];
     __shared__ int stok;
     const int b = blockIdx.x, t = threadIdx.x;
-    const int tok = select_token<false>(sp, logits + (size_t)b * sp.V, b, S);
+    const int tok = select_token<false, REC>(sp, logits + (size_t)b * sp.V, b, S);
     if (t == 0) {
         if (tok >= 0) select_commit(sp, b, tok);
         stok = tok;
@@ -362,9 +366,15 @@ bool select_embed_norm(const SelectSpec &sp, const float *logits, const EmbedNor
         return false;
     }
     if (S <= 0) return true;
-    if (f32tab) hipLaunchKernelGGL((k_select_embed_norm<1, true>), dim3(S), dim3(256), 0, s, sp, logits, en);
-    else if (en.H > 1024) hipLaunchKernelGGL((k_select_embed_norm<2, false>), dim3(S), dim3(256), 0, s, sp, logits, en);
-    else hipLaunchKernelGGL((k_select_embed_norm<1, false>), dim3(S), dim3(256), 0, s, sp, logits, en);
+#define Q3T_SEN_LAUNCH(WW, FF)                                                                                       \
+    do {                                                                                                            \
+        if (sp.rec) hipLaunchKernelGGL((k_select_embed_norm<WW, FF, true>), dim3(S), dim3(256), 0, s, sp, logits, en);   \
+        else hipLaunchKernelGGL((k_select_embed_norm<WW, FF, false>), dim3(S), dim3(256), 0, s, sp, logits, en);         \
+    } while (0)
+    if (f32tab) Q3T_SEN_LAUNCH(1, true);
+    else if (en.H > 1024) Q3T_SEN_LAUNCH(2, false);
+    else Q3T_SEN_LAUNCH(1, false);
+#undef Q3T_SEN_LAUNCH
     Q3T_HIP(hipGetLastError());
     return true;
 }

@@ -57,7 +57,9 @@ struct BLds {
 };
 
 // ---------------------------------------------------------------- the kernel
-template <int NT>
+// REC: the selections read the slots' sampling records (p.sel.rec, per-utterance sampling); launched without it when
+// p.sel.rec is null, so a call without records runs the code it ran before there were any
+template <int NT, bool REC>
 __global__ void __launch_bounds__(256, 1) k_cpb(const CpbParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     BLds &S = *reinterpret_cast<BLds *>(smem);
@@ -206,11 +208,11 @@ __global__ void __launch_bounds__(256, 1) k_cpb(const CpbParams p) {
             SelectSpec sp = p.sel;
             sp.step = pass - 1;
             SelPre pre;   // the selection's per-slot inputs (done, frame, seed, utterance) before the poll, off the chain
-            sel_prefetch<SEL_CP>(sp, b, pre);
+            sel_prefetch<SEL_CP, REC>(sp, b, pre);
             float v[SEL_VPT_MAX];
             poll_logits<CPV / 256>(X, SL.lg, b, X.tag(ph_of(lh, K_HEAD)), v);
             CPROF(ph_of(lh, K_HEAD), 1);
-            const int tok = select_token_pre<SEL_CP>(sp, pre, v, S.sel);   // -1: slot done
+            const int tok = select_token_pre<SEL_CP, REC>(sp, pre, v, S.sel);   // -1: slot done
             if (t == 0 && tok >= 0) {
                 if (rn) select_commit(sp, b, tok);
                 S.toks[pass] = tok;
@@ -262,7 +264,9 @@ constexpr size_t LDS = lds_bytes<BLds>();
 size_t cpb_state_bytes() { return SL.total; }
 bool cpb_error(const uint8_t *state, hipStream_t s, bool *err) { return state_error(SL, state, s, err); }
 bool cpb_clear(uint8_t *state, hipStream_t s) { return state_clear(SL, state, s); }
-bool cpb_resident(int device) { return resident<&k_cpb<1>, &k_cpb<2>>(device, LDS); }
+bool cpb_resident(int device) {
+    return resident<&k_cpb<1, false>, &k_cpb<2, false>>(device, LDS) && resident<&k_cpb<1, true>, &k_cpb<2, true>>(device, LDS);
+}
 
 bool persist_cp_batched(const CpbParams &p, hipStream_t s) {
     if (!p.L || !p.heads || !p.tabs || !p.out_norm || !p.qkvtab || !p.x_in || !p.rope || !p.pos || !p.kc || !p.vc || !p.logits ||
@@ -271,7 +275,8 @@ bool persist_cp_batched(const CpbParams &p, hipStream_t s) {
         set_error("persist_cp_batched: bad parameters");
         return false;
     }
-    return launch_by_tile_count<&k_cpb<1>, &k_cpb<2>>(p, LDS, s);
+    if (p.sel.rec) return launch_by_tile_count<&k_cpb<1, true>, &k_cpb<2, true>>(p, LDS, s);
+    return launch_by_tile_count<&k_cpb<1, false>, &k_cpb<2, false>>(p, LDS, s);
 }
 
 }  // namespace q3t

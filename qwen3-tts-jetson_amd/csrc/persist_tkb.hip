@@ -48,7 +48,9 @@ struct BLds {
     PLayerW layers[NL];
 };
 
-template <int NT>
+// REC: the CB0 selection reads the slots' sampling records (p.sel.rec, per-utterance sampling); launched without it
+// when p.sel.rec is null, so a call without records runs the code it ran before there were any
+template <int NT, bool REC>
 __global__ void __launch_bounds__(256, 1) k_tkb(const TkbParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     BLds &S = *reinterpret_cast<BLds *>(smem);
@@ -167,7 +169,7 @@ __global__ void __launch_bounds__(256, 1) k_tkb(const TkbParams p) {
     if (rn) {
         CPROF(ph_of(NL, K_HEAD), 0);
         SelPre pre;   // the selection's per-slot inputs (done, frame, seed, seen bytes) before the poll, off the chain
-        if (p.select) sel_prefetch<SEL_CB0>(p.sel, b, pre);
+        if (p.select) sel_prefetch<SEL_CB0, REC>(p.sel, b, pre);
         float v[SEL_VPT_MAX];
         poll_logits<VPT>(X, SL.lg, b, X.tag(ph_of(NL, K_HEAD)), v);
         CPROF(ph_of(NL, K_HEAD), 1);
@@ -177,7 +179,7 @@ __global__ void __launch_bounds__(256, 1) k_tkb(const TkbParams p) {
             for (int k = 0; k < VPT / 4; ++k) *reinterpret_cast<float4 *>(row + 4 * k) = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
         }
         if (p.select) {
-            const int tok = select_token_pre<SEL_CB0>(p.sel, pre, v, S.sel);   // -1: slot done
+            const int tok = select_token_pre<SEL_CB0, REC>(p.sel, pre, v, S.sel);   // -1: slot done
             if (t == 0 && tok >= 0) select_commit(p.sel, b, tok);
         }
         CPROF(ph_of(NL, K_HEAD), 3);
@@ -192,7 +194,9 @@ constexpr size_t LDS = lds_bytes<BLds>();
 size_t tkb_state_bytes() { return SL.total; }
 bool tkb_error(const uint8_t *state, hipStream_t s, bool *err) { return state_error(SL, state, s, err); }
 bool tkb_clear(uint8_t *state, hipStream_t s) { return state_clear(SL, state, s); }
-bool tkb_resident(int device) { return resident<&k_tkb<1>, &k_tkb<2>>(device, LDS); }
+bool tkb_resident(int device) {
+    return resident<&k_tkb<1, false>, &k_tkb<2, false>>(device, LDS) && resident<&k_tkb<1, true>, &k_tkb<2, true>>(device, LDS);
+}
 
 bool persist_talker_batched(const TkbParams &p, hipStream_t s) {
     if (!p.L || p.n_layers != NL || !p.head || !p.out_norm || !p.x_in || !p.hidden || !p.rope || !p.pos || !p.kc || !p.vc ||
@@ -200,7 +204,8 @@ bool persist_talker_batched(const TkbParams &p, hipStream_t s) {
         set_error("persist_talker_batched: bad parameters");
         return false;
     }
-    return launch_by_tile_count<&k_tkb<1>, &k_tkb<2>>(p, LDS, s);
+    if (p.select && p.sel.rec) return launch_by_tile_count<&k_tkb<1, true>, &k_tkb<2, true>>(p, LDS, s);
+    return launch_by_tile_count<&k_tkb<1, false>, &k_tkb<2, false>>(p, LDS, s);
 }
 
 }  // namespace q3t

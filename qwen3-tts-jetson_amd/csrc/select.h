@@ -578,11 +578,25 @@ __device__ __forceinline__ void sel_load_exact(const float *row, float (&v)[SEL_
 struct SelPre {
     int done, frame, n_tokens, force;
     uint64_t seed, utt;
+    float temperature, rep;   // REC: the slot's sampling record (SelectSpec::rec), else unused
+    int top_k;
     uint32_t seen[SEL_VPT_MAX / 4];   // CB0 seen flags of this thread's indices, byte e of the thread in byte e % 4 of word e / 4
 };
-template <int MODE>
+// REC (compile time): the sampling triple comes from the slot's record sp.rec[s] when sp.rec is set (per-utterance
+// sampling of the batched families); without REC, or with a null sp.rec, the scalars of sp are used term for term.
+// The one-slot persistent kernels instantiate without REC: they read nothing new.
+template <bool REC>
+__device__ __forceinline__ float sel_rep(const SelectSpec &sp, const SelPre &q) { if constexpr (REC) return q.rep; else return sp.rep; }
+template <int MODE, bool REC = false>
 __device__ __forceinline__ void sel_prefetch(const SelectSpec &sp, int s, SelPre &q) {
     const int t = threadIdx.x, V = sp.V, vpt = (V + 255) / 256;
+    if constexpr (REC) {
+        q.temperature = sp.temperature; q.top_k = sp.top_k; q.rep = sp.rep;
+        if (sp.rec) {   // uniform over the workgroup: one 16-byte load
+            const SelRec r = sp.rec[s];
+            q.temperature = r.temperature; q.top_k = r.top_k; q.rep = r.rep;
+        }
+    }
     q.done = sp.done[s];
     q.frame = sp.frame[s] + sp.frame_offset;
     q.seed = sp.seed_dev ? *sp.seed_dev : sp.seed;
@@ -594,7 +608,7 @@ __device__ __forceinline__ void sel_prefetch(const SelectSpec &sp, int s, SelPre
     if constexpr (MODE == SEL_CB0) {
         q.n_tokens = sp.n_tokens[s];
         q.force = sp.force_frames[s];
-        if (sp.rep != 1.0f) {
+        if (sel_rep<REC>(sp, q) != 1.0f) {
             const uint8_t *seen = sp.seen + (size_t)s * V;
             if (V % 1024 == 0) {   // vpt % 4 == 0 and every index in range: whole words (the row is 4-byte aligned)
                 const uint32_t *sw = reinterpret_cast<const uint32_t *>(seen + (size_t)t * vpt);
@@ -619,11 +633,15 @@ __device__ __forceinline__ void sel_prefetch(const SelectSpec &sp, int s, SelPre
 // kSel / kSelG loops, kernels.hip, k_tk_roles, k_cp_roles, k_persist) keep the rule.
 // the token of a slot from its prefetched inputs (uniform over the workgroup), or -1 if the slot is done; no side
 // effects.  MODE: SEL_CB0 / SEL_CP at compile time (the code-predictor path carries none of the CB0 rules)
-template <int MODE>
+template <int MODE, bool REC = false>
 __device__ __forceinline__ int select_token_pre(const SelectSpec &sp, const SelPre &q, float (&v)[SEL_VPT_MAX], SelLds &S) {
     if (q.done >= 0) return -1;   // uniform over the workgroup
     const int t = threadIdx.x, V = sp.V, vpt = (V + 255) / 256;
     const int frame = q.frame;
+    const float rep = sel_rep<REC>(sp, q);
+    float temperature = sp.temperature;
+    int top_k = sp.top_k;
+    if constexpr (REC) { temperature = q.temperature; top_k = q.top_k; }
     int keep = -1;
     float u;
     if constexpr (MODE == SEL_CB0) {
@@ -635,7 +653,7 @@ __device__ __forceinline__ int select_token_pre(const SelectSpec &sp, const SelP
             if (e >= vpt || i >= V) continue;
             float x = v[e];
             if (i >= V - 1024 && i != EOS) x = -INFINITY;                          // :2418-2422
-            if (sp.rep != 1.0f && ((q.seen[e >> 2] >> (8 * (e & 3))) & 0xffu)) x = x > 0.0f ? x / sp.rep : x * sp.rep;  // :2425-2435
+            if (rep != 1.0f && ((q.seen[e >> 2] >> (8 * (e & 3))) & 0xffu)) x = x > 0.0f ? x / rep : x * rep;  // :2425-2435
             v[e] = x;
             m = fmaxf(m, x);
         }
@@ -656,21 +674,23 @@ __device__ __forceinline__ int select_token_pre(const SelectSpec &sp, const SelP
     } else {
         u = uniform24(q.seed, q.utt, (uint64_t)frame, (uint64_t)sp.step + 1);
     }
-    return sp.temperature <= 0.0f ? sel_argmax(v, V, vpt, S) : sel_sample(v, V, vpt, sp.temperature, sp.top_k, u, keep, S);
+    return temperature <= 0.0f ? sel_argmax(v, V, vpt, S) : sel_sample(v, V, vpt, temperature, top_k, u, keep, S);
 }
 
 // the token of slot s (uniform over the workgroup), or -1 if the slot is done; no side effects
 // select_token on a row already loaded into the owner registers (sel_load): lets a kernel issue the logits loads
 // ahead of its weight stream
-// MODE: SEL_CB0 / SEL_CP at compile time, or SEL_NONE to dispatch on sp.mode
-template <int MODE = SEL_NONE>
+// MODE: SEL_CB0 / SEL_CP at compile time, or SEL_NONE to dispatch on sp.mode.  REC: read the slot's record (the fused
+// selections of gemv_kernel.h always do; the standalone launches, like k_tkb / k_cpb, are instantiated both ways and
+// launched by sp.rec, so a call without records runs the code it ran before there were any)
+template <int MODE = SEL_NONE, bool REC = true>
 __device__ __forceinline__ int select_token_regs(const SelectSpec &sp, float (&v)[SEL_VPT_MAX], int s, SelLds &S) {
     if constexpr (MODE == SEL_NONE) {
-        return sp.mode == SEL_CB0 ? select_token_regs<SEL_CB0>(sp, v, s, S) : select_token_regs<SEL_CP>(sp, v, s, S);
+        return sp.mode == SEL_CB0 ? select_token_regs<SEL_CB0, REC>(sp, v, s, S) : select_token_regs<SEL_CP, REC>(sp, v, s, S);
     } else {
         SelPre q;
-        sel_prefetch<MODE>(sp, s, q);
-        return select_token_pre<MODE>(sp, q, v, S);
+        sel_prefetch<MODE, REC>(sp, s, q);
+        return select_token_pre<MODE, REC>(sp, q, v, S);
     }
 }
 
@@ -684,7 +704,7 @@ __device__ __forceinline__ void sel_load_exact_sc1(const float *row, float (&v)[
     for (int e = VPT; e < SEL_VPT_MAX; ++e) v[e] = -INFINITY;
 }
 
-template <bool SC1>
+template <bool SC1, bool REC = true>
 __device__ __forceinline__ int select_token(const SelectSpec &sp, const float *row, int s, SelLds &S) {
     float v[SEL_VPT_MAX];
     if (sp.V == 2048) {
@@ -696,7 +716,7 @@ __device__ __forceinline__ int select_token(const SelectSpec &sp, const float *r
     } else {
         sel_load<SC1>(row, sp.V, (sp.V + 255) / 256, v);
     }
-    return select_token_regs(sp, v, s, S);
+    return select_token_regs<SEL_NONE, REC>(sp, v, s, S);
 }
 
 // the side effects of a selected token (thread 0 of ONE workgroup per slot): frame codes, EOS, seen set
@@ -714,9 +734,9 @@ __device__ __forceinline__ void select_commit(const SelectSpec &sp, int s, int t
 }
 
 // select the token of slot s from its logits row and record it (SelectSpec semantics, kernels.h)
-template <bool SC1>
+template <bool SC1, bool REC = true>
 __device__ __forceinline__ void select_slot(const SelectSpec &sp, const float *row, int s, SelLds &S) {
-    const int tok = select_token<SC1>(sp, row, s, S);
+    const int tok = select_token<SC1, REC>(sp, row, s, S);
     if (tok >= 0 && threadIdx.x == 0) select_commit(sp, s, tok);
 }
 

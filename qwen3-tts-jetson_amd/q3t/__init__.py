@@ -43,6 +43,12 @@ class GenParams(C.Structure):
                 ("temperature", C.c_float), ("top_k", C.c_int32), ("seed", C.c_uint64), ("force_frames", C.c_int32)]
 
 
+class UttParams(C.Structure):
+    """q3t_utt_params: one utterance's own language, max_len and sampling values"""
+    _fields_ = [("language_id", C.c_int32), ("max_len", C.c_int32), ("repetition_penalty", C.c_float),
+                ("temperature", C.c_float), ("top_k", C.c_int32), ("force_frames", C.c_int32)]
+
+
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 _fp = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _ip = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
@@ -62,6 +68,14 @@ QUEUE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.P
                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32))
 _lib.q3t_generate_queue_stream.argtypes = [_P, _I, C.POINTER(C.POINTER(C.c_int32)), _ip, C.POINTER(C.POINTER(C.c_float)),
                                            C.POINTER(GenParams), _P, _ip, C.c_int32, QUEUE_CB, C.c_void_p, C.c_int32]
+_lib.q3t_utt_params_from.argtypes = [C.POINTER(GenParams), C.POINTER(UttParams)]
+_lib.q3t_utt_params_from.restype = None
+_lib.q3t_generate_utt.argtypes = [_P, _I, C.POINTER(C.POINTER(C.c_int32)), _ip, C.POINTER(C.POINTER(C.c_float)),
+                                  C.POINTER(GenParams), C.POINTER(UttParams), _ip, _ip, _P, C.c_void_p, C.c_int32]
+_lib.q3t_generate_queue_utt.argtypes = [_P, _I, C.POINTER(C.POINTER(C.c_int32)), _ip, C.POINTER(C.POINTER(C.c_float)),
+                                        C.POINTER(GenParams), C.POINTER(UttParams), _P, _ip, C.c_int32, _P, C.c_void_p,
+                                        C.c_int32]
+_lib.q3t_talker_prefill_ragged.argtypes = [_P, _I, _ip, _fp, _I, _P, _P]
 COMM_ID_BYTES = 128
 _lib.q3t_comm_unique_id.argtypes = [C.c_char_p]
 _lib.q3t_ctx_create_shared.argtypes = [C.c_char_p, C.c_char_p, _I, _I, _I, _I, _I, C.c_char_p, C.POINTER(_P)]
@@ -126,7 +140,8 @@ EXPORTS = ["q3t_last_error", "q3t_default_params", "q3t_ctx_create", "q3t_ctx_de
            "q3t_vocoder_stream_last_groups", "q3t_vocoder_stream_samples",
            "q3t_vocoder_stream_frames", "q3t_vocoder_stream_halo", "q3t_vocoder_stream_close", "q3t_vocoder_stream_reset", "q3t_speaker_dim", "q3t_ctx_create_speaker", "q3t_speaker_encode", "q3t_speaker_mel",
            "q3t_tokenizer_load", "q3t_tokenizer_free", "q3t_tokenizer_info", "q3t_tokenizer_encode",
-           "q3t_tokenizer_decode", "q3t_talker_forward", "q3t_talker_prefill",
+           "q3t_tokenizer_decode", "q3t_talker_forward", "q3t_talker_prefill", "q3t_talker_prefill_ragged",
+           "q3t_utt_params_from", "q3t_generate_utt", "q3t_generate_queue_utt",
            "q3t_codepred_frame", "q3t_cb0_select", "q3t_project_text", "q3t_prefill_embd", "gpu_fp32_to_fp16",
            "gpu_argmax_f32", "gpu_embedding_lookup_by_gpu_id", "gpu_sample_topk_f32"]
 
@@ -146,6 +161,45 @@ def default_params(**kw):
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+_UTT_KEYS = ("language_id", "max_len", "repetition_penalty", "temperature", "top_k", "force_frames")
+
+
+def utt_params(p, per_utt, n):
+    """The q3t_utt_params array of a call: the call's values (GenParams p) with each utterance's overrides
+    (per_utt[u]: a dict over language_id / max_len / repetition_penalty / temperature / top_k / force_frames, or None)."""
+    if len(per_utt) != n:
+        raise ValueError("per_utt: one entry (a dict or None) per prompt")
+    up = (UttParams * n)()
+    for u in range(n):
+        _lib.q3t_utt_params_from(C.byref(p), C.byref(up[u]))
+        for k, v in (per_utt[u] or {}).items():
+            if k not in _UTT_KEYS:
+                raise ValueError(f"per_utt[{u}]: unknown key {k!r} (per utterance: {', '.join(_UTT_KEYS)})")
+            setattr(up[u], k, v)
+    return up
+
+
+def _speaker_array(speakers, n, optional):
+    """(pointer array or None, the arrays it points into); optional: entries may be None (per-utterance calls)"""
+    if speakers is None:
+        return None, []
+    if len(speakers) != n:
+        raise ValueError("one speaker embedding per prompt, or none")
+    if not optional and any(s is None for s in speakers):
+        raise ValueError("a speaker entry may be None only with per_utt")
+    sp = [None if s is None else np.ascontiguousarray(s, np.float32) for s in speakers]
+    null = C.POINTER(C.c_float)()
+    return (C.POINTER(C.c_float) * n)(*[null if s is None else s.ctypes.data_as(C.POINTER(C.c_float)) for s in sp]), sp
+
+
+def _check_frames(rc, nf):
+    """_check whose error carries the call's n_frames (all zero after a validation failure)"""
+    if rc != 0:
+        e = Q3TError(_lib.q3t_last_error().decode(errors="replace"))
+        e.n_frames = [int(x) for x in nf]
+        raise e
 
 
 def _addr(a):
@@ -338,10 +392,15 @@ class Engine:
             pass
 
     # ---- hot path
-    def generate(self, prompts, speakers=None, **params):
-        """prompts: list of token-id lists.  Returns list of [n_frames][16] int32 arrays."""
+    def generate(self, prompts, speakers=None, per_utt=None, **params):
+        """prompts: list of token-id lists.  Returns list of [n_frames][16] int32 arrays.
+        per_utt: one dict (or None) per prompt overriding the call's language_id / max_len / repetition_penalty /
+        temperature / top_k / force_frames for that utterance (q3t_generate_utt); speakers may then hold None entries.
+        The seed and the call's max_len (the cap of every per-utterance max_len) stay per call."""
         p = default_params(**params)
         n = len(prompts)
+        if per_utt is not None:
+            return self._generate_utt(prompts, speakers, per_utt, p, None, 0)
         toks = [np.ascontiguousarray(t, np.int32) for t in prompts]
         tarr = (C.POINTER(C.c_int32) * n)(*[t.ctypes.data_as(C.POINTER(C.c_int32)) for t in toks])
         ntok = np.array([len(t) for t in toks], np.int32)
@@ -357,11 +416,45 @@ class Engine:
         del keep
         return [codes[i, :nf[i]].copy() for i in range(n)]
 
-    def generate_queue(self, prompts, speakers=None, max_active=0, **params):
+    def _generate_utt(self, prompts, speakers, per_utt, p, cb, interval):
+        n = len(prompts)
+        up = utt_params(p, per_utt, n)
+        toks = [np.ascontiguousarray(t, np.int32) for t in prompts]
+        tarr = (C.POINTER(C.c_int32) * n)(*[t.ctypes.data_as(C.POINTER(C.c_int32)) for t in toks])
+        ntok = np.array([len(t) for t in toks], np.int32)
+        sarr, keep = _speaker_array(speakers, n, True)
+        codes = np.zeros((n, p.max_len, 16), np.int32)
+        nf = np.zeros(n, np.int32)
+        _check_frames(_lib.q3t_generate_utt(self.h, n, tarr, ntok, sarr, C.byref(p), up, codes, nf,
+                                            C.cast(cb, C.c_void_p) if cb else None, None, int(interval)), nf)
+        del keep
+        return [codes[i, :nf[i]].copy() for i in range(n)]
+
+    def _generate_queue_utt(self, prompts, speakers, per_utt, p, max_active, cb, interval, want_codes):
+        n = len(prompts)
+        up = utt_params(p, per_utt, n)
+        toks = [np.ascontiguousarray(t, np.int32) for t in prompts]
+        tarr = (C.POINTER(C.c_int32) * n)(*[t.ctypes.data_as(C.POINTER(C.c_int32)) for t in toks])
+        ntok = np.array([len(t) for t in toks], np.int32)
+        sarr, keep = _speaker_array(speakers, n, True)
+        codes = np.zeros((n, p.max_len, 16), np.int32) if want_codes else None
+        nf = np.zeros(n, np.int32)
+        _check_frames(_lib.q3t_generate_queue_utt(self.h, n, tarr, ntok, sarr, C.byref(p), up, _addr(codes), nf,
+                                                  int(max_active), C.cast(cb, C.c_void_p) if cb else None, None,
+                                                  int(interval)), nf)
+        del keep
+        if not want_codes:
+            return [int(x) for x in nf]
+        return [codes[i, :nf[i]].copy() for i in range(n)]
+
+    def generate_queue(self, prompts, speakers=None, max_active=0, per_utt=None, **params):
         """continuous batching (q3t_generate_queue): any number of prompts through the context's slots, a finished
-        utterance's slot refilled with the next prompt.  Returns list of [n_frames][16] int32 arrays."""
+        utterance's slot refilled with the next prompt.  Returns list of [n_frames][16] int32 arrays.
+        per_utt: as in generate() (q3t_generate_queue_utt)."""
         p = default_params(**params)
         n = len(prompts)
+        if per_utt is not None:
+            return self._generate_queue_utt(prompts, speakers, per_utt, p, max_active, None, 0, True)
         toks = [np.ascontiguousarray(t, np.int32) for t in prompts]
         tarr = (C.POINTER(C.c_int32) * n)(*[t.ctypes.data_as(C.POINTER(C.c_int32)) for t in toks])
         ntok = np.array([len(t) for t in toks], np.int32)
@@ -377,21 +470,12 @@ class Engine:
         del keep
         return [codes[i, :nf[i]].copy() for i in range(n)]
 
-    def generate_stream(self, prompts, on_frames, interval=40, speakers=None, **params):
+    def generate_stream(self, prompts, on_frames, interval=40, speakers=None, per_utt=None, **params):
         """generate() with the reference's frame callback: on_frames(utt, codes [n][16]) -> bool, every `interval`
-        frames plus a final flush; returning False stops that utterance.  Returns the codes like generate()."""
+        frames plus a final flush; returning False stops that utterance.  Returns the codes like generate().
+        per_utt: as in generate()."""
         p = default_params(**params)
         n = len(prompts)
-        toks = [np.ascontiguousarray(t, np.int32) for t in prompts]
-        tarr = (C.POINTER(C.c_int32) * n)(*[t.ctypes.data_as(C.POINTER(C.c_int32)) for t in toks])
-        ntok = np.array([len(t) for t in toks], np.int32)
-        sarr = None
-        sp = []
-        if speakers is not None:
-            sp = [np.ascontiguousarray(s, np.float32) for s in speakers]
-            sarr = (C.POINTER(C.c_float) * n)(*[s.ctypes.data_as(C.POINTER(C.c_float)) for s in sp])
-        codes = np.zeros((n, p.max_len, 16), np.int32)
-        nf = np.zeros(n, np.int32)
         errors = []
 
         def _cb(_user, utt, ptr, nfr, ncb):
@@ -403,28 +487,11 @@ class Engine:
                 return 0
 
         cb = FRAME_CB(_cb)
-        _check(_lib.q3t_generate_stream(self.h, n, tarr, ntok, sarr, C.byref(p), codes, nf, cb, None, int(interval)))
-        del sp
-        if errors:
-            raise errors[0]
-        return [codes[i, :nf[i]].copy() for i in range(n)]
-
-    def generate_queue_stream(self, prompts, on_batch, interval=12, speakers=None, max_active=0, want_codes=True,
-                              **params):
-        """generate_queue() that hands frames out while it runs (q3t_generate_queue_stream).  on_batch(entries) is
-        called once per tick (every `interval` frames of the queue's loop) or finish with a list of
-        (utt, codes [n][16] int32, final); it returns None or True to continue, an iterable of utterance indices to
-        cancel, or False to abort the call.  Per utterance the pieces arrive in order, concatenate to generate_queue's
-        codes, and exactly one is final.  Returns the codes like generate_queue() (a cancelled utterance: the frames
-        it was handed), or with want_codes=False (no code buffers kept) the list of frame counts."""
-        if not callable(on_batch):
-            raise TypeError("generate_queue_stream: on_batch must be callable (use generate_queue without one)")
-        if isinstance(interval, bool) or not isinstance(interval, (int, np.integer)) or interval <= 0:
-            raise ValueError("generate_queue_stream: interval must be an integer > 0")
-        if speakers is not None and len(speakers) != len(prompts):
-            raise ValueError("generate_queue_stream: one speaker embedding per prompt, or none")
-        p = default_params(**params)
-        n = len(prompts)
+        if per_utt is not None:
+            out = self._generate_utt(prompts, speakers, per_utt, p, cb, interval)
+            if errors:
+                raise errors[0]
+            return out
         toks = [np.ascontiguousarray(t, np.int32) for t in prompts]
         tarr = (C.POINTER(C.c_int32) * n)(*[t.ctypes.data_as(C.POINTER(C.c_int32)) for t in toks])
         ntok = np.array([len(t) for t in toks], np.int32)
@@ -433,8 +500,31 @@ class Engine:
         if speakers is not None:
             sp = [np.ascontiguousarray(s, np.float32) for s in speakers]
             sarr = (C.POINTER(C.c_float) * n)(*[s.ctypes.data_as(C.POINTER(C.c_float)) for s in sp])
-        codes = np.zeros((n, p.max_len, 16), np.int32) if want_codes else None
+        codes = np.zeros((n, p.max_len, 16), np.int32)
         nf = np.zeros(n, np.int32)
+        _check(_lib.q3t_generate_stream(self.h, n, tarr, ntok, sarr, C.byref(p), codes, nf, cb, None, int(interval)))
+        del sp
+        if errors:
+            raise errors[0]
+        return [codes[i, :nf[i]].copy() for i in range(n)]
+
+    def generate_queue_stream(self, prompts, on_batch, interval=12, speakers=None, max_active=0, want_codes=True,
+                              per_utt=None, **params):
+        """generate_queue() that hands frames out while it runs (q3t_generate_queue_stream).  on_batch(entries) is
+        called once per tick (every `interval` frames of the queue's loop) or finish with a list of
+        (utt, codes [n][16] int32, final); it returns None or True to continue, an iterable of utterance indices to
+        cancel, or False to abort the call.  Per utterance the pieces arrive in order, concatenate to generate_queue's
+        codes, and exactly one is final.  Returns the codes like generate_queue() (a cancelled utterance: the frames
+        it was handed), or with want_codes=False (no code buffers kept) the list of frame counts.
+        per_utt: as in generate(); no piece reaches beyond an utterance's own max_len."""
+        if not callable(on_batch):
+            raise TypeError("generate_queue_stream: on_batch must be callable (use generate_queue without one)")
+        if isinstance(interval, bool) or not isinstance(interval, (int, np.integer)) or interval <= 0:
+            raise ValueError("generate_queue_stream: interval must be an integer > 0")
+        if speakers is not None and len(speakers) != len(prompts):
+            raise ValueError("generate_queue_stream: one speaker embedding per prompt, or none")
+        p = default_params(**params)
+        n = len(prompts)
         errors = []
 
         def _cb(_user, m, utt, cptr, nfr, fin, stop):
@@ -459,6 +549,21 @@ class Engine:
                 return 0
 
         cb = QUEUE_CB(_cb)
+        if per_utt is not None:
+            out = self._generate_queue_utt(prompts, speakers, per_utt, p, max_active, cb, interval, want_codes)
+            if errors:
+                raise errors[0]
+            return out
+        toks = [np.ascontiguousarray(t, np.int32) for t in prompts]
+        tarr = (C.POINTER(C.c_int32) * n)(*[t.ctypes.data_as(C.POINTER(C.c_int32)) for t in toks])
+        ntok = np.array([len(t) for t in toks], np.int32)
+        sarr = None
+        sp = []
+        if speakers is not None:
+            sp = [np.ascontiguousarray(s, np.float32) for s in speakers]
+            sarr = (C.POINTER(C.c_float) * n)(*[s.ctypes.data_as(C.POINTER(C.c_float)) for s in sp])
+        codes = np.zeros((n, p.max_len, 16), np.int32) if want_codes else None
+        nf = np.zeros(n, np.int32)
         _check(_lib.q3t_generate_queue_stream(self.h, n, tarr, ntok, sarr, C.byref(p), _addr(codes) if want_codes else None,
                                               nf, int(max_active), cb, None, int(interval)))
         del sp
@@ -621,6 +726,19 @@ class Engine:
         lg = np.zeros((n_utt, self.cfg["codec_vocab"]), np.float32)
         _check(_lib.q3t_talker_prefill(self.h, n_utt, n_rows, embd.reshape(-1), int(family_slots), _addr(hid), _addr(lg)))
         return hid, lg
+
+    def talker_prefill_ragged(self, embd_list, family_slots=0):
+        """the same over prompts of different lengths in one pass (q3t_talker_prefill_ragged): embd_list[u] is
+        [n_rows_u][H] with 1 <= n_rows_u <= 10 -> (list of hidden [n_rows_u][H], last-row logits [n_utt][V])"""
+        H = self.cfg["hidden"]
+        rows = [np.ascontiguousarray(e, np.float32).reshape(-1, H) for e in embd_list]
+        n_rows = np.array([r.shape[0] for r in rows], np.int32)
+        packed = np.ascontiguousarray(np.concatenate(rows, axis=0)).reshape(-1)
+        hid = np.zeros((int(n_rows.sum()), H), np.float32)
+        lg = np.zeros((len(rows), self.cfg["codec_vocab"]), np.float32)
+        _check(_lib.q3t_talker_prefill_ragged(self.h, len(rows), n_rows, packed, int(family_slots), _addr(hid), _addr(lg)))
+        off = np.concatenate([[0], np.cumsum(n_rows)])
+        return [hid[off[u]:off[u + 1]].copy() for u in range(len(rows))], lg
 
     def codepred_frame(self, hidden, cb0, temperature=0.0, top_k=50, seed=0, frame=0, want_logits=False):
         hidden = np.ascontiguousarray(hidden, np.float32).reshape(-1, self.cfg["hidden"])

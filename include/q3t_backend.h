@@ -175,6 +175,47 @@ int q3t_generate_queue_utt(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens
                            const float *const *speaker, const q3t_gen_params *p, const q3t_utt_params *up /* [n_utt] */,
                            int32_t *codes, int32_t *n_frames, int32_t max_active, q3t_queue_cb cb, void *user,
                            int32_t interval);
+/* ---- incremental text input: feed an utterance's text while it speaks.  The prefill holds only the role ids and the
+ * first text id; every later text id is consumed one per frame, so frame f needs text row f and nothing beyond it.
+ * An utterance with open[u] != 0 is given as a head: tokens[u] = the three role ids, then >= 1 text id (n_tokens[u] >= 4),
+ * WITHOUT the five-id suffix of a whole prompt.  Its further text ids come from text_cb.  With K = the text ids known
+ * beyond the first (n_tokens[u] - 4 plus the ids fed so far) it may run frame f only while f < K; a slot that has
+ * consumed every row it knows is put on hold (no selection, no advance, its state kept) until text_cb gives more or
+ * ends the text.  The codes and n_frames of an open utterance are, bit for bit, those q3t_generate_queue_utt gives for
+ * the prompt head || fed ids || five valid ids (same seed, utterance index, slot count and record), however the ids
+ * were cut into feeds and however long the slot was starved; closed utterances of the call are not affected.
+ *
+ * asked for more text of open utterance `utt`: frames = frames it has generated, rows_ahead = frames it can still
+ * run before it is held.  *ids -> *n_ids text ids (valid until return; may be 0), *end != 0: the text ends after them.
+ * Return 0 to abort the whole queue (as q3t_queue_cb). */
+typedef int (*q3t_text_cb)(void *user, int32_t utt, int32_t frames, int32_t rows_ahead,
+                           const int32_t **ids, int32_t *n_ids, int32_t *end);
+/* q3t_generate_queue_utt (up == NULL: q3t_generate_queue / q3t_generate_queue_stream) with open utterances.  text_cb
+ * runs on the caller's thread under the rules stated for q3t_queue_cb, for every open utterance that holds a slot: once
+ * when it is activated (before its first frame), at every tick (every `interval` frames of the loop clock) and on every
+ * loop iteration on which it has no row for its next frame.  interval > 0 is required also with cb == NULL.  While every
+ * busy slot is held and no admission is in flight the loop launches nothing, hands out the pending deliveries and keeps
+ * asking: blocking until text exists is the callback's job.  On a fallback re-run (a persistent hand-off fault) the ids
+ * already given are replayed, not asked for again; held[u] may then differ, the codes may not.
+ * Deliveries of an open utterance (also after its text ended): a delivery that is neither first nor last has
+ * 1..interval frames, and a tick that finds no new frame makes none; every other clause of the delivery contract holds,
+ * and closed utterances keep all of it.  text_cb returning 0 with cb == NULL: utterances that had ended keep their
+ * frames, the others have n_frames 0.
+ * Q3T_ERR before anything runs: open != NULL with an open utterance and text_cb == NULL, interval <= 0, a head shorter
+ * than 4 ids, a head id out of range.  Q3T_ERR naming the utterance, after both streams are drained: a fed id out of
+ * range, a feed that takes K + 1 past the trailing-text buffer (512 rows).
+ * open == NULL or all zero: the call is q3t_generate_queue_utt, launch for launch. */
+int q3t_generate_queue_text(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens, const int32_t *n_tokens,
+                            const float *const *speaker, const q3t_gen_params *p, const q3t_utt_params *up /* may be NULL */,
+                            const uint8_t *open /* [n_utt]: 1 = tokens[u] is a head, text continues through text_cb */,
+                            int32_t *codes, int32_t *n_frames, int32_t *held /* [n_utt] or NULL: times u was put on hold */,
+                            int32_t max_active, q3t_queue_cb cb, void *user, int32_t interval,
+                            q3t_text_cb text_cb, void *text_user);
+/* counters of the context's last q3t_generate_queue_text with an open utterance (any pointer may be NULL): frame graphs
+ * launched, loop rounds that launched none because every busy slot was held, feed rounds (one copy, the text projection
+ * and the append / hold / release launches of one loop iteration) and their summed device time in ms */
+int q3t_text_feed_stats(const q3t_ctx *ctx, int32_t *graph_launches, int32_t *idle_rounds, int32_t *feed_rounds,
+                        double *feed_ms);
 /* tuning knob (process-wide): batches of >= min_batch slots run the projections on the matrix cores (MFMA GEMM,
  * gemm_mfma.hip) instead of the weight-streaming GEMV; 0 disables the matrix-core path.  Default 4 (env
  * Q3T_MFMA_MIN_B).  Applies to graphs captured afterwards (create contexts after changing it). */

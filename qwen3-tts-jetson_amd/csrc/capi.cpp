@@ -271,6 +271,38 @@ int q3t_generate_queue_utt(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens
     GUARD_END
 }
 
+int q3t_generate_queue_text(q3t_ctx *ctx, int n_utt, const int32_t *const *tokens, const int32_t *n_tokens,
+                            const float *const *speaker, const q3t_gen_params *p, const q3t_utt_params *up,
+                            const uint8_t *open, int32_t *codes, int32_t *n_frames, int32_t *held, int32_t max_active,
+                            q3t_queue_cb cb, void *user, int32_t interval, q3t_text_cb text_cb, void *text_user) {
+    GUARD_BEGIN
+    CHECK_CTX(ctx);
+    CHECK_TALKER(ctx);
+    if (n_utt < 0 || (n_utt > 0 && (!tokens || !n_tokens || !n_frames))) { q3t::set_error("null argument"); return Q3T_ERR; }
+    if (cb && interval <= 0) { q3t::set_error("q3t_generate_queue_text: interval must be > 0 with a callback"); return Q3T_ERR; }
+    std::vector<q3t::UttParams> v;
+    if (up) v = to_up(up, n_utt);
+    q3t::Engine::TextFeed tf;
+    tf.open = open; tf.cb = text_cb; tf.user = text_user; tf.held = held;
+    bool any_open = false;
+    for (int u = 0; open && u < n_utt; ++u) any_open = any_open || open[u];
+    // (the clock of the asks is the interval also without a delivery callback)
+    return ctx->engine.generate_queue(n_utt, tokens, n_tokens, speaker, to_gp(p), codes, n_frames, max_active, cb, user,
+                                      cb || any_open ? interval : 0, up ? v.data() : nullptr, &tf) ? Q3T_OK : Q3T_ERR;
+    GUARD_END
+}
+
+int q3t_text_feed_stats(const q3t_ctx *ctx, int32_t *graph_launches, int32_t *idle_rounds, int32_t *feed_rounds,
+                        double *feed_ms) {
+    CHECK_CTX(ctx);
+    const q3t::Engine::TextStats &s = ctx->engine.text_stats;
+    if (graph_launches) *graph_launches = s.graph_launches;
+    if (idle_rounds) *idle_rounds = s.idle_rounds;
+    if (feed_rounds) *feed_rounds = s.feed_rounds;
+    if (feed_ms) *feed_ms = s.feed_ms;
+    return Q3T_OK;
+}
+
 int q3t_synchronize(q3t_ctx *ctx) {
     GUARD_BEGIN
     CHECK_CTX(ctx);

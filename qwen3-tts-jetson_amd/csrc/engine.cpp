@@ -94,6 +94,11 @@ Engine::~Engine() {
     if (qstage_) hipFree(qstage_);
     if (pin_) hipHostFree(pin_);
     for (PinnedChunk &c : chunk_pool_) { hipHostFree(c.codes); hipEventDestroy(c.ev); }
+    for (int b = 0; b < FeedScratch::NBUF; ++b) {
+        if (feed_.pin[b]) hipHostFree(feed_.pin[b]);
+        if (feed_.e0[b]) hipEventDestroy(feed_.e0[b]);
+        if (feed_.e1[b]) hipEventDestroy(feed_.e1[b]);
+    }
     if (stream_) hipStreamDestroy(stream_);
     if (astream_) hipStreamDestroy(astream_);
 }
@@ -1494,16 +1499,25 @@ bool Engine::alloc_prompt_scratch(PromptScratch &ps, float *spk) {
 }
 
 bool Engine::enqueue_text_projection(int n_rows, hipStream_t s, const PromptScratch &ps) {
+    return enqueue_text_projection(n_rows, s, ps.idx, ps.h, ps.out, false);
+}
+
+bool Engine::enqueue_text_projection(int n_rows, hipStream_t s, const int *idx, uint16_t *h, float *out, bool as_admission) {
     // text_embd row gather -> fc1 + b -> SiLU -> fc2 + b   (tts_transformer.cpp:1050-1055)
+    // as_admission: the smallest admission projects 7 rows (plan_rows), so with the matrix-core GEMM on from <= 7 rows
+    // every admission runs it, and its per-row arithmetic does not depend on the rows beside it
+    const bool mm = as_admission && gemm_mfma_min_batch() <= 7;
     GemvParams a;
     a.W = fc1_; a.N = c_.text_dim; a.K = c_.text_dim; a.B = n_rows;
-    a.pro = PRO_F16; a.x = text_embd_; a.ldx = c_.text_dim; a.x_idx = ps.idx;
-    a.bias = fc1_b_; a.act = ACT_SILU; a.out_f16 = ps.h; a.ldo = c_.text_dim;
+    a.pro = PRO_F16; a.x = text_embd_; a.ldx = c_.text_dim; a.x_idx = idx;
+    a.bias = fc1_b_; a.act = ACT_SILU; a.out_f16 = h; a.ldo = c_.text_dim;
+    a.force_mm = mm;
     if (!gemv(a, s)) return false;
     GemvParams b;
     b.W = fc2_; b.N = c_.hidden; b.K = c_.text_dim; b.B = n_rows;
-    b.pro = PRO_F16; b.x = ps.h; b.ldx = c_.text_dim;
-    b.bias = fc2_b_; b.out_f32 = ps.out; b.ldo = c_.hidden;
+    b.pro = PRO_F16; b.x = h; b.ldx = c_.text_dim;
+    b.bias = fc2_b_; b.out_f32 = out; b.ldo = c_.hidden;
+    b.force_mm = mm;
     return gemv(b, s);
 }
 
@@ -1514,7 +1528,8 @@ bool Engine::project_text(int n, const int32_t *toks, float *out) {
     for (int i = 0; i < n; ++i)
         if (toks[i] < 0 || toks[i] >= c_.text_vocab) { set_error("text token out of range"); return false; }
     Q3T_HIP(hipMemcpyAsync(main_ps_.idx, toks, n * 4, hipMemcpyHostToDevice, stream_));
-    if (!enqueue_text_projection(n, stream_, main_ps_)) return false;
+    // a row is what an admission (and a text feed) computes for its id, however many ids share the call
+    if (!enqueue_text_projection(n, stream_, main_ps_.idx, main_ps_.h, main_ps_.out, true)) return false;
     Q3T_HIP(hipMemcpyAsync(out, main_ps_.out, (size_t)n * c_.hidden * 4, hipMemcpyDeviceToHost, stream_));
     Q3T_HIP(hipStreamSynchronize(stream_));
     return true;
@@ -2159,15 +2174,130 @@ private:
     std::vector<Chunk> pend_, pool_;  // collections in flight, oldest first; chunks delivered and free for reuse
 };
 
-bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
+// Text feeds (DESIGN 2f "Text feeds").  A round is what the asks of one loop iteration produced: new text ids of some
+// slots (feed_.ids, with one trailing tts_eos id if an utterance closed), where their projected rows go (feed_.rows),
+// the counters they publish (feed_.commit) and the slots to hold / release (feed_.hold / feed_.rel).  It travels as
+// ONE pinned blob -> ONE device blob [hold S | release S | commit 3 n | rows 3 n | ids n] on the main stream, followed
+// by the text projection over all ids, one k_text_append and at most one hold and one release launch.
+bool Engine::ensure_text_feed() {
+    FeedScratch &F = feed_;
+    if (F.dev) return true;
+    const int S = max_slots_;
+    F.cap_rows = S * max_trailing_ + 1;
+    F.cap_ints = (size_t)5 * S + (size_t)4 * F.cap_rows;
+    if (F.cap_rows > main_ps_.cap) { set_error("text feeds: projection scratch too small"); return false; }
+    int *dev = dalloc<int>(F.cap_ints + 1);
+    hold_save_ = dalloc<float>((size_t)S * c_.hidden);
+    held_flag_ = dalloc<int>(S);
+    if (!dev || !hold_save_ || !held_flag_) { set_error("device allocation failed"); return false; }
+    for (int b = 0; b < FeedScratch::NBUF; ++b) {
+        Q3T_HIP(hipHostMalloc(reinterpret_cast<void **>(&F.pin[b]), F.cap_ints * 4, hipHostMallocDefault));
+        Q3T_HIP(hipEventCreate(&F.e0[b]));
+        Q3T_HIP(hipEventCreate(&F.e1[b]));
+    }
+    F.ids.reserve(F.cap_rows); F.rows.reserve((size_t)3 * F.cap_rows); F.commit.reserve((size_t)3 * S);
+    F.hold.reserve(S); F.rel.reserve(S);
+    F.error = dev + F.cap_ints;   // zeroed by dalloc
+    F.dev = dev;
+    return true;
+}
+
+bool Engine::drain_text_rounds() {
+    FeedScratch &F = feed_;
+    for (int i = 0; i < FeedScratch::NBUF; ++i) {
+        const int b = (F.next + i) % FeedScratch::NBUF;   // oldest first
+        if (!F.used[b]) continue;
+        F.used[b] = false;
+        Q3T_HIP(hipEventSynchronize(F.e1[b]));
+        float ms = 0;
+        Q3T_HIP(hipEventElapsedTime(&ms, F.e0[b], F.e1[b]));
+        text_stats.feed_ms += ms;
+    }
+    return true;
+}
+
+bool Engine::enqueue_text_round(int S, bool any_hold, bool any_rel) {
+    FeedScratch &F = feed_;
+    const int b = F.next;
+    F.next = (b + 1) % FeedScratch::NBUF;
+    if (F.used[b]) {   // the round that last used this blob: long since run, unless the host is NBUF rounds ahead
+        F.used[b] = false;
+        Q3T_HIP(hipEventSynchronize(F.e1[b]));
+        float ms = 0;
+        Q3T_HIP(hipEventElapsedTime(&ms, F.e0[b], F.e1[b]));
+        text_stats.feed_ms += ms;
+    }
+    const int n_ids = (int)F.ids.size(), n_rows = (int)F.rows.size() / 3, n_commit = (int)F.commit.size() / 3;
+    if (n_ids > F.cap_rows || n_rows > F.cap_rows || n_commit > S || (int)F.hold.size() != S || (int)F.rel.size() != S) {
+        set_error("text feeds: round larger than its scratch");
+        return false;
+    }
+    int *p = F.pin[b];
+    const size_t o_rel = S, o_commit = (size_t)2 * S, o_rows = (size_t)5 * S, o_ids = o_rows + (size_t)3 * n_rows;
+    std::memcpy(p, F.hold.data(), (size_t)S * 4);
+    std::memcpy(p + o_rel, F.rel.data(), (size_t)S * 4);
+    std::memset(p + o_commit, 0, (size_t)3 * S * 4);
+    if (n_commit) std::memcpy(p + o_commit, F.commit.data(), (size_t)3 * n_commit * 4);
+    if (n_rows) std::memcpy(p + o_rows, F.rows.data(), (size_t)3 * n_rows * 4);
+    if (n_ids) std::memcpy(p + o_ids, F.ids.data(), (size_t)n_ids * 4);
+    Q3T_HIP(hipEventRecord(F.e0[b], stream_));
+    Q3T_HIP(hipMemcpyAsync(F.dev, p, (o_ids + n_ids) * 4, hipMemcpyHostToDevice, stream_));
+    if (n_ids && !enqueue_text_projection(n_ids, stream_, F.dev + o_ids, main_ps_.h, main_ps_.out, true)) return false;
+    TextAppend t;
+    t.src = main_ps_.out; t.trailing = trailing_; t.rows = F.dev + o_rows; t.commit = F.dev + o_commit;
+    t.trailing_len = trailing_len_; t.n_tokens = n_tokens_; t.error = F.error;
+    t.n_rows = n_rows; t.n_commit = n_commit; t.src_rows = n_ids; t.S = S; t.max_trailing = max_trailing_; t.H = c_.hidden;
+    if (!text_append(t, stream_)) return false;
+    SlotHold h;
+    h.hidden = hidden_; h.save = hold_save_; h.done = done_; h.held = held_flag_; h.frame = frame_; h.H = c_.hidden;
+    h.mask = F.dev + o_rel;
+    if (any_rel && !slot_release(h, S, stream_)) return false;
+    h.mask = F.dev;
+    if (any_hold && !slot_hold(h, S, stream_)) return false;
+    Q3T_HIP(hipEventRecord(F.e1[b], stream_));
+    F.used[b] = true;
+    ++text_stats.feed_rounds;
+    return true;
+}
+
+bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens_in, const int *n_tokens_in, const float *const *speaker,
                                  const GenParams &gp, const UttParams *up, int32_t *codes, int *n_frames, int max_active,
-                                 bool *faulted, QueueCb on_batch, void *user, int interval, QueueState &qst) {
+                                 bool *faulted, QueueCb on_batch, void *user, int interval, QueueState &qst,
+                                 const TextFeed *text, TextLog *tlog) {
     *faulted = false;
     if (n_utt <= 0) return true;
     const int S = std::min(max_slots_, n_utt), NCB = 16;
     if (max_active <= 0 || max_active > S) max_active = S;
     for (int u = 0; u < n_utt; ++u) n_frames[u] = 0;
     if (gp.max_len <= 0) return true;
+    // open utterances (text feeds): a head [3 role ids, >= 1 text id] runs as the prompt head || five ids, whose rows
+    // are exactly the head's (the five are dropped by plan_rows); its trailing row K0 = n_head - 4, the tts_eos row of
+    // that prompt, is not counted while the text is open and is overwritten by the first feed
+    const int32_t *const *tokens = tokens_in;
+    const int *n_tokens = n_tokens_in;
+    std::vector<std::vector<int32_t>> head_pad;
+    std::vector<const int32_t *> tok_eff;
+    std::vector<int> nt_eff;
+    if (text) {
+        tok_eff.assign(tokens_in, tokens_in + n_utt);
+        nt_eff.assign(n_tokens_in, n_tokens_in + n_utt);
+        head_pad.resize(n_utt);
+        for (int u = 0; u < n_utt; ++u) {
+            if (!text->open[u]) continue;
+            const std::string who = "utterance " + std::to_string(u) + ": ";
+            if (n_tokens_in[u] < 4) { set_error(who + "an open utterance needs a head of at least 4 ids"); return false; }
+            if (n_tokens_in[u] - 4 + 1 > max_trailing_) { set_error(who + "head too long for the trailing-text buffer"); return false; }
+            for (int i = 0; i < n_tokens_in[u]; ++i)
+                if (tokens_in[u][i] < 0 || tokens_in[u][i] >= c_.text_vocab) { set_error(who + "text token out of range"); return false; }
+            head_pad[u].assign(tokens_in[u], tokens_in[u] + n_tokens_in[u]);
+            head_pad[u].insert(head_pad[u].end(), 5, c_.tts_pad);
+            tok_eff[u] = head_pad[u].data();
+            nt_eff[u] = n_tokens_in[u] + 5;
+        }
+        tokens = tok_eff.data();
+        n_tokens = nt_eff.data();
+        if (!ensure_text_feed()) return false;
+    }
     // the call-wide form: one record and one prompt length for every utterance.  With records (up): each utterance's own;
     // admission batches then pack their prompt rows and run the ragged prefill
     std::vector<UttParams> ups;
@@ -2207,14 +2337,17 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
     int32_t *out_dev = codes ? static_cast<int32_t *>(qout_) : nullptr;
     QueueStreamer qs(*this, S, n_utt, gp.max_len, up != nullptr, on_batch, user, interval, qst, faulted);
     if (qs.active() && !qs.begin()) return false;
-    if ((qs.active() || up) && out_dev)   // an aborted call copies out rows of utterances that never ran (and with records
+    if ((qs.active() || up || text) && out_dev)   // an aborted call copies out rows of utterances that never ran (and with records
                                           // a release parks only the utterance's own max_len rows)
         Q3T_HIP(hipMemsetAsync(out_dev, 0, (size_t)n_utt * gp.max_len * NCB * 4, stream_));
     // [S][16] activation staging, [S] done flags, [S] admission targets, the constants 0 (parking) and the waiting
     // position: pinned, kept
-    if (!ensure_pinned(((size_t)S * 18 + 2) * 4)) return false;
+    // (text feeds: [S] held flags behind them, polled beside the done flags)
+    if (!ensure_pinned(((size_t)S * 19 + 2) * 4)) return false;
     int *pin = static_cast<int *>(pin_);
     int *done_h = pin + (size_t)S * 16, *tgt_h = pin + (size_t)S * 17, *park = pin + (size_t)S * 18;
+    int *held_h = pin + (size_t)S * 18 + 2;
+    for (int k = 0; k < S; ++k) held_h[k] = 0;
     park[0] = 0;
     park[1] = plen;
     Event aev(hipEventDisableTiming), pev(hipEventDisableTiming), rev(hipEventDisableTiming);
@@ -2238,12 +2371,35 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         Q3T_HIP(hipMemsetAsync(frame_, 0, S * 4, stream_));
         Q3T_HIP(hipMemsetAsync(tokens_, 0, (size_t)S * 16 * 4, stream_));
         Q3T_HIP(hipMemsetAsync(trailing_len_, 0, S * 4, stream_));
+        if (text) Q3T_HIP(hipMemsetAsync(held_flag_, 0, S * 4, stream_));
         Q3T_HIP(hipStreamSynchronize(stream_));
     }
     enum { FREE, PENDING, ACTIVE };
-    std::vector<int> state(S, FREE), slot_utt(S, -1), started(S, 0), tl(S, 0);
+    std::vector<int> state(S, FREE), slot_utt(S, -1), tl(S, 0);
+    // ran[k]: the frames launched for slot k's utterance (while it was active and not held); ran_polled[k]: the same when
+    // the done flags now in done_h were copied.  Without text feeds a slot runs every frame of the loop: ran[k] is the
+    // loop clock less the slot's activation frame.
+    std::vector<int> ran(S, 0), ran_polled(S, 0);
     std::vector<int> batch_tgt, batch_tl;   // the admission batch in flight (at most one)
     int next = 0, f = 0, n_fin = 0, n_busy = 0;
+    // ---- text feeds: per utterance the known trailing rows K and whether its text has ended, per slot whether the host
+    // holds it and whether its utterance was activated since the last asks.  A one-slot context holds by not launching
+    // (its persistent kernels own the device; nothing else would run): the device-side hold is for slots that share a
+    // frame graph with running ones.
+    const bool dev_hold = text && S > 1;
+    std::vector<int> rows_known(text ? n_utt : 0, 0), replay_piece(text ? n_utt : 0, 0), replay_id(text ? n_utt : 0, 0);
+    std::vector<char> is_open(n_utt, 0), closed(n_utt, 1), hheld(S, 0), fresh(S, 0);
+    bool tick_ask = false;
+    if (text) {
+        text_stats = TextStats{};
+        for (int u = 0; u < n_utt; ++u) {
+            is_open[u] = text->open[u] != 0;
+            closed[u] = !is_open[u];
+            rows_known[u] = n_tokens_in[u] - 4;
+        }
+        feed_.next = 0;
+    }
+    ScopeExit feed_drain([&] { if (text) drain_text_rounds(); });
     auto admit = [&]() -> bool {   // every free slot, up to max_active busy, one batch
         std::vector<int> tgt, utt;
         for (int k = 0; k < S && next + (int)tgt.size() < n_utt && n_busy + (int)tgt.size() < max_active; ++k)
@@ -2272,9 +2428,13 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         for (int k : batch_tgt) {
             const int u = slot_utt[k];
             if (up && S == 1) one_slot_params(ups[u]);
-            if (!activate_slot(k, (uint64_t)u, tl[k], n_tokens[u], ups[u], plens[u], pin + (size_t)k * 16, qs.active())) return false;
+            // an open utterance: its rows without the tts_eos row, n_tokens = K + 9 (what the padded head counts)
+            if (!activate_slot(k, (uint64_t)u, tl[k] - (is_open[u] ? 1 : 0), n_tokens[u], ups[u], plens[u], pin + (size_t)k * 16, qs.active())) return false;
+            if (dev_hold) Q3T_HIP(hipMemsetAsync(held_flag_ + k, 0, 4, stream_));
             state[k] = ACTIVE;
-            started[k] = f;
+            ran[k] = 0;
+            hheld[k] = 0;
+            fresh[k] = 1;
         }
         batch_tgt.clear();
         return true;
@@ -2303,6 +2463,8 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
                                    (size_t)ups[u].max_len * NCB * 4, hipMemcpyDeviceToDevice, stream_));
         if (park_slot)   // still running: park the slot (no selection, no advance)
             Q3T_HIP(hipMemcpyAsync(done_ + k, park, 4, hipMemcpyHostToDevice, stream_));
+        if (dev_hold && hheld[k]) Q3T_HIP(hipMemsetAsync(held_flag_ + k, 0, 4, stream_));   // (cancelled while held)
+        hheld[k] = 0;
         if (mixed_plen)   // its successor's prompt may be longer than the position it stopped at: back to the waiting one
             Q3T_HIP(hipMemcpyAsync(pos_ + k, park + 1, 4, hipMemcpyHostToDevice, stream_));
         state[k] = FREE;
@@ -2325,9 +2487,133 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
     };
     std::vector<char> sel(S, 0);
     bool polled = false;   // one frame in flight: frame f is launched before frame f-1's done flags are read
+    // the slots whose utterance ended by the polled flags (done_h / held_h, copied when slot k had run ran_polled[k]
+    // frames): a held slot's done flag is its hold, not an end, and a slot the host holds may have ended before
+    // k_slot_hold ran (its real EOS stays and it is not flagged held)
+    auto reap = [&]() -> bool {
+        Q3T_HIP(hipEventSynchronize(pev));
+        bool any = false;
+        for (int k = 0; k < S; ++k) {
+            if (held_h[k]) done_h[k] = -1;
+            sel[k] = state[k] == ACTIVE && !(done_h[k] < 0 && ran_polled[k] < ups[slot_utt[k]].max_len);
+            any = any || sel[k];
+        }
+        // the rest of the finished slots' frames, before a slot is parked or handed to a successor
+        if (qs.active() && any && !qs.collect(slot_utt, sel, true, f + 1)) return false;
+        for (int k = 0; k < S; ++k) {
+            if (!sel[k]) continue;
+            const int d = done_h[k];
+            const int cap = ups[slot_utt[k]].max_len;
+            n_frames[slot_utt[k]] = d >= 0 ? std::min(d, cap) : cap;
+            if (!release(k, d < 0)) return false;   // d < 0: stopped at max_len
+        }
+        return true;
+    };
+    // ---- text feeds: the asks of this iteration and the round they make.  An open utterance that holds a slot is asked
+    // when it was activated (before its first frame), at every tick, and on every iteration on which it has no row for
+    // its next frame.  Each answer is validated, logged (a fallback re-run replays the log instead of asking) and added to
+    // the round; then every open slot is held or released by `frames >= K && !closed`.
+    // n_tokens_ is published as K + 9 with every feed, so CB0's EOS ramp (expected = max(20, 4 * n_tokens)) sees a
+    // count that grows.  That never changes a selection: while the text is open the slot only runs frames f < K, and the
+    // selection at the end of frame f uses frame = f + 1 <= K < 4 * (K + 9) <= 4 * (K_final + 9), so the ramp is off under
+    // the running count and under the final one alike; after the close the two are equal.
+    auto feed_piece = [&](int u, int k, const int32_t *ids, int n, bool end) -> bool {
+        const std::string who = "utterance " + std::to_string(u) + ": ";
+        if (n < 0 || (n > 0 && !ids)) { set_error(who + "bad text feed"); return false; }
+        for (int i = 0; i < n; ++i)
+            if (ids[i] < 0 || ids[i] >= c_.text_vocab) { set_error(who + "fed text token out of range"); return false; }
+        if (rows_known[u] + n + 1 > max_trailing_) { set_error(who + "text feed exceeds the trailing-text buffer"); return false; }
+        FeedScratch &F = feed_;
+        for (int i = 0; i < n; ++i) {
+            F.rows.push_back((int)F.ids.size()); F.rows.push_back(k); F.rows.push_back(rows_known[u] + i);
+            F.ids.push_back(ids[i]);
+        }
+        rows_known[u] += n;
+        if (end) {   // row K becomes the tts_eos row (its source row is fixed up when the round is closed)
+            closed[u] = 1;
+            F.rows.push_back(-1); F.rows.push_back(k); F.rows.push_back(rows_known[u]);
+        }
+        if (n > 0 || end) {
+            F.commit.push_back(k); F.commit.push_back(rows_known[u] + (end ? 1 : 0)); F.commit.push_back(rows_known[u] + 9);
+        }
+        return true;
+    };
+    auto text_round = [&]() -> bool {
+        FeedScratch &F = feed_;
+        F.ids.clear(); F.rows.clear(); F.commit.clear();
+        F.hold.assign(S, 0); F.rel.assign(S, 0);
+        for (int k = 0; k < S && !qst.aborted; ++k) {
+            const int u = slot_utt[k];
+            if (state[k] != ACTIVE || !is_open[u] || closed[u]) { fresh[k] = 0; continue; }
+            if (!(fresh[k] || tick_ask || ran[k] >= rows_known[u])) continue;
+            fresh[k] = 0;
+            // a re-run: the pieces the first run was given by now, without asking again
+            std::vector<TextLog::Piece> &pieces = tlog->pieces[u];
+            bool replayed = false;
+            while (replay_piece[u] < (int)pieces.size() && pieces[replay_piece[u]].frames <= ran[k] && !closed[u]) {
+                const TextLog::Piece pc = pieces[replay_piece[u]++];
+                if (!feed_piece(u, k, tlog->ids[u].data() + replay_id[u], pc.n, pc.end)) return false;
+                replay_id[u] += pc.n;
+                replayed = true;
+            }
+            if (replayed || replay_piece[u] < (int)pieces.size()) continue;
+            const int32_t *ids = nullptr;
+            int32_t n = 0, end = 0;
+            if (!text->cb(text->user, u, ran[k], std::max(0, rows_known[u] - ran[k]), &ids, &n, &end)) { qst.aborted = true; break; }
+            if (n == 0 && !end) continue;
+            if (!feed_piece(u, k, ids, n, end != 0)) return false;
+            if (n > 0) tlog->ids[u].insert(tlog->ids[u].end(), ids, ids + n);
+            pieces.push_back(TextLog::Piece{ran[k], n, end != 0});
+            replay_piece[u] = (int)pieces.size();
+            replay_id[u] = (int)tlog->ids[u].size();
+        }
+        tick_ask = false;
+        if (qst.aborted) return true;
+        bool any_hold = false, any_rel = false, any_eos = false;
+        for (size_t i = 0; i < F.rows.size(); i += 3)
+            if (F.rows[i] < 0) { F.rows[i] = (int)F.ids.size(); any_eos = true; }
+        if (any_eos) F.ids.push_back(c_.tts_eos);
+        for (int k = 0; k < S; ++k) {
+            const int u = slot_utt[k];
+            if (state[k] != ACTIVE || !is_open[u]) continue;
+            const bool want = !closed[u] && ran[k] >= rows_known[u] && ran[k] < ups[u].max_len;
+            if (want && !hheld[k]) {
+                if (text->held) ++text->held[u];
+                if (dev_hold) { F.hold[k] = 1; any_hold = true; }
+            } else if (!want && hheld[k] && dev_hold) {
+                F.rel[k] = 1; any_rel = true;
+            }
+            hheld[k] = want;
+        }
+        if (F.ids.empty() && F.commit.empty() && !any_hold && !any_rel) return true;
+        return enqueue_text_round(S, any_hold, any_rel);
+    };
     while (n_fin < n_utt && !qst.aborted) {
-        int n_active = 0;
-        for (int k = 0; k < S; ++k) n_active += state[k] == ACTIVE;
+        if (text) {
+            if (!text_round()) return false;
+            if (qst.aborted) break;
+        }
+        int n_active = 0, n_run = 0;
+        for (int k = 0; k < S; ++k) {
+            n_active += state[k] == ACTIVE;
+            n_run += state[k] == ACTIVE && !hheld[k];
+        }
+        if (n_active > 0 && n_run == 0) {
+            // every busy slot is held: launch nothing.  What the last poll shows, the pending deliveries (nothing runs
+            // behind them), an admission if one is in flight or possible, then ask again: waiting for text is the
+            // callback's job
+            ++text_stats.idle_rounds;
+            if (polled && !reap()) return false;
+            polled = false;
+            if (qs.active() && !deliver(INT_MAX)) return false;
+            if (qst.aborted) break;
+            if (batch_tgt.empty() && next < n_utt && !admit()) return false;
+            if (!batch_tgt.empty()) {
+                Q3T_HIP(hipEventSynchronize(aev));
+                if (!activate()) return false;
+            }
+            continue;
+        }
         if (n_active == 0) {   // only an admission in flight: wait for it instead of running empty frames
             if (qs.active() && !deliver(INT_MAX)) return false;   // nothing runs behind them: hand out what is pending
             if (qst.aborted) break;
@@ -2342,6 +2628,11 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
         if (!persist_fault_hook(S, (persist_ ? 1 : 0) + (persist_cp_ ? 1 : 0))) return false;
         Q3T_HIP(hipGraphLaunch(fg, stream_));
         ++f;
+        for (int k = 0; k < S; ++k) ran[k] += state[k] == ACTIVE && !hheld[k];
+        if (text) {
+            ++text_stats.graph_launches;
+            tick_ask = f % interval == 0;
+        }
         if (qs.active()) {
             // a tick: the new frames of every active slot, behind this frame's graph; then the chunks due by now (the
             // previous tick's, and the finish chunks of the previous frame)
@@ -2352,28 +2643,13 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
             if (!deliver(f)) return false;
             if (qst.aborted) break;
         }
-        if (polled) {
-            Q3T_HIP(hipEventSynchronize(pev));
-            bool any = false;
-            for (int k = 0; k < S; ++k) {   // done_h: after frame f-1
-                const int ran = f - 1 - started[k];
-                sel[k] = state[k] == ACTIVE && !(done_h[k] < 0 && ran < ups[slot_utt[k]].max_len);
-                any = any || sel[k];
-            }
-            // the rest of the finished slots' frames, before a slot is parked or handed to a successor
-            if (qs.active() && any && !qs.collect(slot_utt, sel, true, f + 1)) return false;
-            for (int k = 0; k < S; ++k) {
-                if (!sel[k]) continue;
-                const int d = done_h[k];
-                const int cap = ups[slot_utt[k]].max_len;
-                n_frames[slot_utt[k]] = d >= 0 ? std::min(d, cap) : cap;
-                if (!release(k, d < 0)) return false;   // d < 0: stopped at max_len
-            }
-        }
+        if (polled && !reap()) return false;   // done_h: after frame f-1
         if (!batch_tgt.empty() && (as == stream_ || hipEventQuery(aev) == hipSuccess) && !activate()) return false;
         if (batch_tgt.empty() && next < n_utt && !admit()) return false;
         if (as == stream_ && !batch_tgt.empty() && !activate()) return false;
         Q3T_HIP(hipMemcpyAsync(done_h, done_, S * 4, hipMemcpyDeviceToHost, stream_));
+        if (dev_hold) Q3T_HIP(hipMemcpyAsync(held_h, held_flag_, S * 4, hipMemcpyDeviceToHost, stream_));
+        ran_polled = ran;
         Q3T_HIP(hipEventRecord(pev, stream_));
         polled = true;
         if (f > (n_utt + 1) * (gp.max_len + plen + 2)) { set_error("generate_queue: no progress"); return false; }
@@ -2393,6 +2669,19 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
                     return false;
                 }
         }
+    } else if (qst.aborted) {   // the text callback ended a call without deliveries: the utterances that had ended keep
+                                // their frames, the others have none
+        for (int k = 0; k < S; ++k)
+            if (state[k] == ACTIVE && !release(k, false)) return false;
+    }
+    if (text) {   // the error word of the rounds' descriptors (never expected: the host validated every feed)
+        Q3T_HIP(hipMemcpyAsync(held_h, feed_.error, 4, hipMemcpyDeviceToHost, stream_));
+        Q3T_HIP(hipStreamSynchronize(stream_));
+        if (held_h[0]) {
+            Q3T_HIP(hipMemsetAsync(feed_.error, 0, 4, stream_));
+            set_error("generate_queue: a text feed named a row outside its buffers");
+            return false;
+        }
     }
     if (codes)
         for (int u = 0; u < n_utt; ++u)
@@ -2405,23 +2694,34 @@ bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens, const 
 
 bool Engine::generate_queue(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                             const GenParams &gp, int32_t *codes, int *n_frames, int max_active, QueueCb on_batch, void *user,
-                            int interval, const UttParams *up) {
+                            int interval, const UttParams *up, const TextFeed *text) {
     for (int u = 0; u < n_utt; ++u) n_frames[u] = 0;
     if (!on_batch && !codes && n_utt > 0) { set_error("generate_queue: no codes buffer and no callback"); return false; }
     if (on_batch && interval <= 0) { set_error("generate_queue: the delivery interval must be > 0"); return false; }
+    // text feeds only with an open utterance: a call without one is the queue as it was, launch for launch
+    int first_open = -1;
+    for (int u = n_utt - 1; text && text->open && u >= 0; --u)
+        if (text->open[u]) first_open = u;
+    if (text && text->held)
+        for (int u = 0; u < n_utt; ++u) text->held[u] = 0;
+    if (first_open < 0) text = nullptr;
+    if (text && !text->cb) { set_error("utterance " + std::to_string(first_open) + ": open without a text callback"); return false; }
+    if (text && interval <= 0) { set_error("generate_queue: text feeds need an interval > 0"); return false; }
+    TextLog tlog;
+    if (text) { tlog.ids.resize(n_utt); tlog.pieces.resize(n_utt); }
     const int S = std::min(max_slots_, std::max(n_utt, 1));
     DeviceLock lk(persist_exclusive(S), device_);
     QueueState qst(std::max(n_utt, 0));
     bool fault = false;
     ScopeExit rec_off([&] { rec_on_ = false; });
-    if (generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, up, codes, n_frames, max_active, &fault, on_batch, user, interval, qst))
+    if (generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, up, codes, n_frames, max_active, &fault, on_batch, user, interval, qst, text, &tlog))
         return true;
     if (!fault) return false;
     // a single-slot persistent launch gave up on a hand-off: continue on the launch-per-op graphs, which are
     // bit-identical, and re-run the queue (sampling is keyed by utterance, so the re-run gives the same codes; what
     // was delivered, cancelled or finished before the fault is kept in qst and not delivered again)
     if (!persist_recover()) return false;
-    return generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, up, codes, n_frames, max_active, &fault, on_batch, user, interval, qst);
+    return generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, up, codes, n_frames, max_active, &fault, on_batch, user, interval, qst, text, &tlog);
 }
 
 bool Engine::time_stage(int stage, int S, int pos, int iters, double *ms) {

@@ -131,6 +131,14 @@ struct StackCache {
     float *part; unsigned *ticket;   // split attention: partials and arrival counters
 };
 
+// what the open utterances of a queue were fed (text feeds), kept across a fallback re-run: the re-run replays it
+// against the same `frames` schedule instead of asking the callback again
+struct TextLog {
+    struct Piece { int frames, n; bool end; };
+    std::vector<std::vector<int32_t>> ids;     // per utterance, every fed id
+    std::vector<std::vector<Piece>> pieces;    // per utterance: at `frames` generated frames, n ids (and the end)
+};
+
 class Engine {
 public:
     Engine();
@@ -184,9 +192,27 @@ public:
     // (n_frames = the frames delivered).  With a callback codes may be null: no per-utterance device copy is kept.
     typedef int (*QueueCb)(void *user, int32_t n, const int32_t *utt, const int32_t *const *codes, const int32_t *n_frames,
                            const int32_t *final, int32_t *stop);
+    // text (q3t_generate_queue_text; DESIGN 2f "Text feeds"): utterances with open[u] != 0 are given as a head (three
+    // role ids and >= 1 text id, no five-id suffix) and their further text ids come from cb, asked on the caller's thread
+    // between two frames; a slot that has consumed every row it knows is held until more text (or its end) arrives.
+    // interval > 0 is then required with or without on_batch (the clock of the asks).  held[u] (may be null): how often
+    // utterance u was put on hold.
+    typedef int (*TextCb)(void *user, int32_t utt, int32_t frames, int32_t rows_ahead, const int32_t **ids, int32_t *n_ids,
+                          int32_t *end);
+    struct TextFeed {
+        const uint8_t *open = nullptr;   // [n_utt]
+        TextCb cb = nullptr;
+        void *user = nullptr;
+        int32_t *held = nullptr;         // [n_utt]
+    };
     bool generate_queue(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                         const GenParams &gp, int32_t *codes, int *n_frames, int max_active, QueueCb on_batch = nullptr,
-                        void *user = nullptr, int interval = 0, const UttParams *up = nullptr);
+                        void *user = nullptr, int interval = 0, const UttParams *up = nullptr, const TextFeed *text = nullptr);
+    // counters of the last generate_queue with text feeds (q3t_text_feed_stats): frame graphs launched, loop rounds that
+    // launched none because every busy slot was held, feed rounds (one copy + projection + k_text_append / hold /
+    // release launches each) and the device time of those rounds (an event pair around each)
+    struct TextStats { int graph_launches = 0, idle_rounds = 0, feed_rounds = 0; double feed_ms = 0; };
+    TextStats text_stats;
     // fill this context's weight arenas (laid out with recv_weights) from another context's, device to device
     bool copy_weights_from(Engine &src);
     // after the weight arenas of a receiving context were filled by a broadcast: build what is derived from the weights
@@ -258,7 +284,8 @@ private:
     class QueueStreamer;   // the queue callback's collections and deliveries (engine.cpp)
     bool generate_queue_once(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                              const GenParams &gp, const UttParams *up, int32_t *codes, int *n_frames, int max_active,
-                             bool *faulted, QueueCb on_batch, void *user, int interval, QueueState &qst);
+                             bool *faulted, QueueCb on_batch, void *user, int interval, QueueState &qst,
+                             const TextFeed *text, TextLog *tlog);
     // host scratch kept across calls (a per-call hipFree / hipHostFree synchronises the whole device)
     struct PinnedChunk { size_t cap = 0; int32_t *codes = nullptr; hipEvent_t ev = nullptr; };
     std::vector<PinnedChunk> chunk_pool_;   // streaming chunks of generate() and of the queue's deliveries
@@ -295,6 +322,9 @@ private:
     size_t cp_table_row0(int p) const { return p == 1 ? 0 : (size_t)c_.codec_vocab + (size_t)(p - 2) * c_.cp_vocab; }
     bool enqueue_frame(int S, hipStream_t s);
     bool enqueue_text_projection(int n_rows, hipStream_t s, const PromptScratch &ps);
+    // the same over ids / scratch named one by one.  as_admission: the rows of an admission batch, whatever n_rows is (an
+    // admission projects >= 7 rows, so it runs the matrix-core GEMM whenever that is on; a feed of one row must too)
+    bool enqueue_text_projection(int n_rows, hipStream_t s, const int *idx, uint16_t *h, float *out, bool as_admission);
     // the prompt rows (PromptScratch::rows), trailing-text rows and pad row of every entry, assembled on stream s;
     // plen: each entry's prompt length in rows (prompt_len), trailing_len: per entry
     bool assemble_prompts(PromptScratch &ps, hipStream_t s, const std::vector<PromptEntry> &in, std::vector<int> &plen,
@@ -343,6 +373,23 @@ private:
                      const std::vector<int> &plen, bool ragged, hipStream_t as, int *tgt_h, std::vector<int> &trailing_len);
     bool activate_slot(int slot, uint64_t utt, int trailing_len, int n_tok, const UttParams &up, int plen, int *state_h,
                        bool deliveries = false);
+    // text feeds: the round's descriptors travel in one pinned blob (a ring: a blob is rewritten only after the copy
+    // that read it has run) to one device blob; hold_save_ keeps the hidden rows of held slots
+    struct FeedScratch {
+        static constexpr int NBUF = 4;
+        int *pin[NBUF] = {};
+        hipEvent_t e0[NBUF] = {}, e1[NBUF] = {};
+        bool used[NBUF] = {};
+        int *dev = nullptr, *error = nullptr;
+        size_t cap_ints = 0;
+        int cap_rows = 0, next = 0;
+        std::vector<int> ids, rows, commit, hold, rel;   // the round being built (reserved once)
+    } feed_;
+    float *hold_save_ = nullptr;   // [max_slots][H]
+    int *held_flag_ = nullptr;     // [max_slots] device: the slot is held (k_slot_hold)
+    bool ensure_text_feed();
+    bool enqueue_text_round(int S, bool any_hold, bool any_rel);   // feed_'s round, on the main stream
+    bool drain_text_rounds();                       // wait for the rounds in flight; their times into text_stats
     hipStream_t astream_ = nullptr;
     int *delivered_ = nullptr, *qmask_ = nullptr;   // queue deliveries: per-slot frames collected so far; a collection's slot mask
     float *ahidden_ = nullptr, *alogits_ = nullptr;

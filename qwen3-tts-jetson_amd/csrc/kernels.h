@@ -214,6 +214,37 @@ struct QueueCollect {
 };
 bool queue_collect(const QueueCollect &q, int S, hipStream_t s);
 
+// Text feeds (DESIGN 2f "Text feeds"): one launch between two frames of the queue.  Row descriptor i = {src row, slot,
+// dst row}: trailing[slot][dst row] = src[src row] (H floats, 16-byte accesses).  Commit descriptor j = {slot,
+// trailing_len, n_tokens}: the slot's two counters.  A descriptor that names a row or a slot outside the buffers
+// (src_rows, S, max_trailing) is skipped and sets *error.
+struct TextAppend {
+    const float *src = nullptr;    // [src_rows][H] projected text rows
+    float *trailing = nullptr;     // [S][max_trailing][H]
+    const int *rows = nullptr;     // [n_rows][3]
+    const int *commit = nullptr;   // [n_commit][3]
+    int *trailing_len = nullptr, *n_tokens = nullptr;   // [S]
+    int *error = nullptr;
+    int n_rows = 0, n_commit = 0, src_rows = 0, S = 0, max_trailing = 0, H = 0;
+};
+bool text_append(const TextAppend &t, hipStream_t s);
+
+// A slot of the queue whose text has run out is held: parked by the done >= 0 convention (no selection, no advance)
+// with the one row the frames it still runs through would destroy, hidden[k], kept aside.  One workgroup per slot,
+// slots with mask[k] == 0 are not touched.
+//   slot_hold:    only if done[k] < 0 (a real EOS stays): save[k] = hidden[k], done[k] = frame[k] (the slot's complete
+//                 frames: what a collection may hand out), held[k] = 1
+//   slot_release: only if held[k]: hidden[k] = save[k], done[k] = -1, held[k] = 0
+struct SlotHold {
+    const int *mask = nullptr;     // [S]
+    float *hidden = nullptr, *save = nullptr;   // [S][H]
+    int *done = nullptr, *held = nullptr;       // [S]
+    const int *frame = nullptr;    // [S]
+    int H = 0;
+};
+bool slot_hold(const SlotHold &h, int S, hipStream_t s);
+bool slot_release(const SlotHold &h, int S, hipStream_t s);
+
 // *out = t[0] + t[1] + t[2] (f32 rows or f16 table rows; null terms skipped); recipe built on the host
 struct RowTerm { const void *ptr; int is_f16; };
 struct RowRecipe { float *out; RowTerm t[3]; };

@@ -109,6 +109,79 @@ bool queue_collect(const QueueCollect &q, int S, hipStream_t s) {
     return true;
 }
 
+// ------------------------------------------------------------------------------------------ text feeds
+// Workgroups [0, n_rows) copy one projected row each into its slot's trailing buffer; the last workgroup publishes
+// the counters.  Nothing in this launch reads what another workgroup of it writes: the next frame's gather does.
+__global__ void __launch_bounds__(256) k_text_append(const TextAppend t) {
+    const int b = blockIdx.x;
+    if (b < t.n_rows) {
+        const int src = t.rows[3 * b], slot = t.rows[3 * b + 1], dst = t.rows[3 * b + 2];
+        if (src < 0 || src >= t.src_rows || slot < 0 || slot >= t.S || dst < 0 || dst >= t.max_trailing) {
+            if (threadIdx.x == 0) *t.error = 1;
+            return;
+        }
+        const float4 *from = reinterpret_cast<const float4 *>(t.src + (size_t)src * t.H);
+        float4 *to = reinterpret_cast<float4 *>(t.trailing + ((size_t)slot * t.max_trailing + dst) * t.H);
+        for (int i = threadIdx.x; i < t.H / 4; i += 256) to[i] = from[i];
+        return;
+    }
+    for (int j = threadIdx.x; j < t.n_commit; j += 256) {
+        const int slot = t.commit[3 * j], tl = t.commit[3 * j + 1];
+        if (slot < 0 || slot >= t.S || tl < 0 || tl > t.max_trailing) { *t.error = 1; continue; }
+        t.trailing_len[slot] = tl;
+        t.n_tokens[slot] = t.commit[3 * j + 2];
+    }
+}
+bool text_append(const TextAppend &t, hipStream_t s) {
+    if (t.n_rows < 0 || t.n_commit < 0 || t.H <= 0 || t.H % 4 != 0 || t.S <= 0 || t.max_trailing <= 0 || !t.error ||
+        (t.n_rows > 0 && !(t.src && t.trailing && t.rows)) || (t.n_commit > 0 && !(t.commit && t.trailing_len && t.n_tokens))) {
+        set_error("text_append: bad parameters");
+        return false;
+    }
+    if (t.n_rows + t.n_commit == 0) return true;
+    hipLaunchKernelGGL(k_text_append, dim3((unsigned)t.n_rows + 1), dim3(256), 0, s, t);
+    Q3T_HIP(hipGetLastError());
+    return true;
+}
+
+// every thread reads the slot's flags before thread 0 rewrites them (the barrier)
+template <bool HOLD>
+__global__ void __launch_bounds__(256) k_slot_hold(const SlotHold h) {
+    const int k = blockIdx.x;
+    if (!h.mask[k]) return;
+    const int done = h.done[k], held = h.held[k], frame = h.frame[k];
+    __syncthreads();
+    if (HOLD ? done >= 0 : !held) return;   // uniform over the workgroup
+    const float4 *from = reinterpret_cast<const float4 *>((HOLD ? h.hidden : h.save) + (size_t)k * h.H);
+    float4 *to = reinterpret_cast<float4 *>((HOLD ? h.save : h.hidden) + (size_t)k * h.H);
+    for (int i = threadIdx.x; i < h.H / 4; i += 256) to[i] = from[i];
+    if (threadIdx.x == 0) {
+        h.done[k] = HOLD ? frame : -1;
+        h.held[k] = HOLD ? 1 : 0;
+    }
+}
+static bool slot_hold_args(const SlotHold &h) {
+    if (h.H <= 0 || h.H % 4 != 0 || !h.mask || !h.hidden || !h.save || !h.done || !h.held || !h.frame) {
+        set_error("slot_hold: bad parameters");
+        return false;
+    }
+    return true;
+}
+bool slot_hold(const SlotHold &h, int S, hipStream_t s) {
+    if (!slot_hold_args(h)) return false;
+    if (S <= 0) return true;
+    hipLaunchKernelGGL(k_slot_hold<true>, dim3(S), dim3(256), 0, s, h);
+    Q3T_HIP(hipGetLastError());
+    return true;
+}
+bool slot_release(const SlotHold &h, int S, hipStream_t s) {
+    if (!slot_hold_args(h)) return false;
+    if (S <= 0) return true;
+    hipLaunchKernelGGL(k_slot_hold<false>, dim3(S), dim3(256), 0, s, h);
+    Q3T_HIP(hipGetLastError());
+    return true;
+}
+
 __global__ void k_rows_recipe(const RowRecipe *rec, int H) {
     const RowRecipe R = rec[blockIdx.x];
     for (int h = threadIdx.x; h < H; h += blockDim.x) {

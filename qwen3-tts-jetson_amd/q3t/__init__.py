@@ -75,6 +75,13 @@ _lib.q3t_generate_utt.argtypes = [_P, _I, C.POINTER(C.POINTER(C.c_int32)), _ip, 
 _lib.q3t_generate_queue_utt.argtypes = [_P, _I, C.POINTER(C.POINTER(C.c_int32)), _ip, C.POINTER(C.POINTER(C.c_float)),
                                         C.POINTER(GenParams), C.POINTER(UttParams), _P, _ip, C.c_int32, _P, C.c_void_p,
                                         C.c_int32]
+TEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.POINTER(C.c_int32)),
+                      C.POINTER(C.c_int32), C.POINTER(C.c_int32))
+_lib.q3t_generate_queue_text.argtypes = [_P, _I, C.POINTER(C.POINTER(C.c_int32)), _ip, C.POINTER(C.POINTER(C.c_float)),
+                                         C.POINTER(GenParams), _P, _P, _P, _ip, _P, C.c_int32, _P, C.c_void_p, C.c_int32,
+                                         _P, C.c_void_p]
+_lib.q3t_text_feed_stats.argtypes = [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_double)]
 _lib.q3t_talker_prefill_ragged.argtypes = [_P, _I, _ip, _fp, _I, _P, _P]
 COMM_ID_BYTES = 128
 _lib.q3t_comm_unique_id.argtypes = [C.c_char_p]
@@ -141,7 +148,8 @@ EXPORTS = ["q3t_last_error", "q3t_default_params", "q3t_ctx_create", "q3t_ctx_de
            "q3t_vocoder_stream_frames", "q3t_vocoder_stream_halo", "q3t_vocoder_stream_close", "q3t_vocoder_stream_reset", "q3t_speaker_dim", "q3t_ctx_create_speaker", "q3t_speaker_encode", "q3t_speaker_mel",
            "q3t_tokenizer_load", "q3t_tokenizer_free", "q3t_tokenizer_info", "q3t_tokenizer_encode",
            "q3t_tokenizer_decode", "q3t_talker_forward", "q3t_talker_prefill", "q3t_talker_prefill_ragged",
-           "q3t_utt_params_from", "q3t_generate_utt", "q3t_generate_queue_utt",
+           "q3t_utt_params_from", "q3t_generate_utt", "q3t_generate_queue_utt", "q3t_generate_queue_text",
+           "q3t_text_feed_stats",
            "q3t_codepred_frame", "q3t_cb0_select", "q3t_project_text", "q3t_prefill_embd", "gpu_fp32_to_fp16",
            "gpu_argmax_f32", "gpu_embedding_lookup_by_gpu_id", "gpu_sample_topk_f32"]
 
@@ -204,6 +212,32 @@ def _check_frames(rc, nf):
 
 def _addr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _queue_cb(on_batch, errors):
+    """q3t_queue_cb over on_batch(entries) (Engine.generate_queue_stream); an exception ends the call and lands in errors"""
+    def _cb(_user, m, utt, cptr, nfr, fin, stop):
+        try:
+            entries = []
+            for i in range(m):
+                k = int(nfr[i])
+                arr = (np.ctypeslib.as_array(cptr[i], shape=(k * 16,)).reshape(k, 16).copy() if k > 0
+                       else np.zeros((0, 16), np.int32))
+                entries.append((int(utt[i]), arr, bool(fin[i])))
+            r = on_batch(entries)
+            if r is False:
+                return 0
+            if r is not None and r is not True:
+                where = {int(utt[i]): i for i in range(m)}
+                for u in r:
+                    if int(u) in where:
+                        stop[where[int(u)]] = 1
+            return 1
+        except Exception as e:  # never let an exception unwind through the C frames
+            errors.append(e)
+            return 0
+
+    return QUEUE_CB(_cb)
 
 
 def set_mfma_min_batch(b):
@@ -270,6 +304,32 @@ class Tokenizer:
         buf = C.create_string_buffer(max(nb.value, 1))
         _check(_lib.q3t_tokenizer_decode(self.h, _addr(a), len(a), buf, nb.value, C.byref(nb)))
         return buf.raw[:nb.value]
+
+
+class TextFeeder:
+    """Text that arrives in pieces -> token ids whose concatenation is Tokenizer.encode(whole text), however the text
+    was cut (the ids Engine.generate_queue_text's text_source feeds).  The tokenizer starts a word at every space and
+    keeps the space with the word, so what follows the last space is held back until more text arrives or close()."""
+
+    def __init__(self, tokenizer):
+        self.tok = tokenizer
+        self.pending = b""
+
+    def feed(self, text):
+        """ids of the words `text` completes (str, or bytes of UTF-8 text cut anywhere)"""
+        raw = text.encode("utf-8", errors="surrogateescape") if isinstance(text, str) else bytes(text)
+        buf = self.pending + raw
+        cut = buf.rfind(b" ")   # the word that starts at the last space may still grow
+        if cut <= 0:
+            self.pending = buf
+            return []
+        self.pending = buf[cut:]
+        return self.tok.encode(buf[:cut])
+
+    def close(self):
+        """ids of the held-back rest; the feeder is empty afterwards"""
+        buf, self.pending = self.pending, b""
+        return self.tok.encode(buf) if buf else []
 
 
 class VocoderStream:
@@ -526,29 +586,7 @@ class Engine:
         p = default_params(**params)
         n = len(prompts)
         errors = []
-
-        def _cb(_user, m, utt, cptr, nfr, fin, stop):
-            try:
-                entries = []
-                for i in range(m):
-                    k = int(nfr[i])
-                    arr = (np.ctypeslib.as_array(cptr[i], shape=(k * 16,)).reshape(k, 16).copy() if k > 0
-                           else np.zeros((0, 16), np.int32))
-                    entries.append((int(utt[i]), arr, bool(fin[i])))
-                r = on_batch(entries)
-                if r is False:
-                    return 0
-                if r is not None and r is not True:
-                    where = {int(utt[i]): i for i in range(m)}
-                    for u in r:
-                        if int(u) in where:
-                            stop[where[int(u)]] = 1
-                return 1
-            except Exception as e:  # never let an exception unwind through the C frames
-                errors.append(e)
-                return 0
-
-        cb = QUEUE_CB(_cb)
+        cb = _queue_cb(on_batch, errors)
         if per_utt is not None:
             out = self._generate_queue_utt(prompts, speakers, per_utt, p, max_active, cb, interval, want_codes)
             if errors:
@@ -572,6 +610,74 @@ class Engine:
         if not want_codes:
             return [int(x) for x in nf]
         return [codes[i, :nf[i]].copy() for i in range(n)]
+
+    def generate_queue_text(self, prompts, open, text_source, on_batch=None, interval=12, speakers=None, max_active=0,
+                            per_utt=None, **params):
+        """generate_queue() whose utterances may be fed their text while they speak (q3t_generate_queue_text).
+        open[u] true: prompts[u] is a head -- the three role ids and at least one text id, without the five-id suffix
+        of a whole prompt -- and its further text ids come from text_source(utt, frames, rows_ahead) -> (ids, end):
+        frames = the frames the utterance has generated, rows_ahead = the frames it can still run before it is held;
+        end true closes the text after ids.  (None or () stands for ([], False); returning False aborts the call.)
+        It is asked when the utterance takes a slot, every `interval` frames of the queue's loop, and again and again
+        while the utterance has no row for its next frame: blocking until text exists is its job.  The codes are those
+        of generate_queue() for head + fed ids + five ids, however the ids were cut.
+        on_batch: as in generate_queue_stream() (an open utterance's pieces may be shorter than `interval`).
+        Returns (codes list, held list): held[u] = how often utterance u was put on hold."""
+        if isinstance(interval, bool) or not isinstance(interval, (int, np.integer)) or interval <= 0:
+            raise ValueError("generate_queue_text: interval must be an integer > 0")
+        n = len(prompts)
+        if len(open) != n:
+            raise ValueError("generate_queue_text: one open flag per prompt")
+        if on_batch is not None and not callable(on_batch):
+            raise TypeError("generate_queue_text: on_batch must be callable or None")
+        p = default_params(**params)
+        errors = []
+        keep_ids = []   # the array handed to the C side stays alive until the next ask
+
+        def _text(_user, utt, frames, ahead, ids_out, n_out, end_out):
+            try:
+                r = text_source(int(utt), int(frames), int(ahead))
+                if r is False:
+                    return 0
+                ids, end = r if r else ((), False)
+                a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+                keep_ids[:] = [a]
+                ids_out[0] = a.ctypes.data_as(C.POINTER(C.c_int32))
+                n_out[0] = len(a)
+                end_out[0] = 1 if end else 0
+                return 1
+            except Exception as e:  # never let an exception unwind through the C frames
+                errors.append(e)
+                return 0
+
+        tcb = TEXT_CB(_text) if text_source is not None else None
+        cb = _queue_cb(on_batch, errors) if on_batch is not None else None
+        up = utt_params(p, per_utt, n) if per_utt is not None else None
+        toks = [np.ascontiguousarray(t, np.int32) for t in prompts]
+        tarr = (C.POINTER(C.c_int32) * n)(*[t.ctypes.data_as(C.POINTER(C.c_int32)) for t in toks])
+        ntok = np.array([len(t) for t in toks], np.int32)
+        sarr, keep = _speaker_array(speakers, n, per_utt is not None)
+        flags = np.ascontiguousarray([1 if o else 0 for o in open], np.uint8)
+        codes = np.zeros((n, p.max_len, 16), np.int32)
+        nf = np.zeros(n, np.int32)
+        held = np.zeros(n, np.int32)
+        rc = _lib.q3t_generate_queue_text(self.h, n, tarr, ntok, sarr, C.byref(p), C.cast(up, C.c_void_p) if up else None,
+                                          _addr(flags), _addr(codes), nf, _addr(held), int(max_active),
+                                          C.cast(cb, C.c_void_p) if cb else None, None, int(interval),
+                                          C.cast(tcb, C.c_void_p) if tcb else None, None)
+        del keep
+        if errors:
+            raise errors[0]
+        _check_frames(rc, nf)
+        return [codes[i, :nf[i]].copy() for i in range(n)], [int(x) for x in held]
+
+    def text_feed_stats(self):
+        """counters of the last generate_queue_text() with an open utterance: frame graphs launched, loop rounds that
+        launched none (every busy slot held), feed rounds, and the device time of the feed rounds in ms"""
+        a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        ms = C.c_double(0)
+        _check(_lib.q3t_text_feed_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(ms)))
+        return dict(graph_launches=a.value, idle_rounds=b.value, feed_rounds=c.value, feed_ms=ms.value)
 
     def synchronize(self):
         _check(_lib.q3t_synchronize(self.h))

@@ -1,5 +1,5 @@
-// engine.cpp — see engine.h.
-#include "engine.h"
+// engine.cpp — see engine.h.  (Continuous batching, Engine::generate_queue, is engine_queue.cpp.)
+#include "engine_internal.h"
 #include "persist.h"
 
 #include <climits>
@@ -103,23 +103,6 @@ Engine::~Engine() {
     if (astream_) hipStreamDestroy(astream_);
 }
 
-template <class T>
-T *Engine::dalloc(size_t n) {
-    void *p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
-    allocs_.push_back(p);
-    // zeroed on the context's own stream, and drained before any other stream (the admission stream, or a
-    // synchronous null-stream copy into the buffer right after this call) can touch it: without the ordering a first
-    // launch could read what a previous context freed in the same process left in this memory (DESIGN §2e').  Only
-    // this context's stream is waited for, never the device.
-    if (hipMemsetAsync(p, 0, std::max<size_t>(n, 1) * sizeof(T), stream_) != hipSuccess ||
-        hipStreamSynchronize(stream_) != hipSuccess) {
-        set_error("dalloc: zeroing failed");
-        return nullptr;
-    }
-    return static_cast<T *>(p);
-}
-
 
 // the pinned / device scratch of generate() and generate_queue(), kept across calls: a per-call hipFree or
 // hipHostFree would synchronise the whole device (every other context on it included)
@@ -132,22 +115,13 @@ bool Engine::ensure_pinned(size_t bytes) {
     pin_cap_ = bytes;
     return true;
 }
-bool Engine::ensure_qout(size_t bytes) {
-    if (bytes <= qout_cap_) return true;
-    if (qout_) hipFree(qout_);
-    qout_ = nullptr;
-    qout_cap_ = 0;
-    if (hipMalloc(&qout_, bytes) != hipSuccess) { qout_ = nullptr; set_error("device allocation failed"); return false; }
-    qout_cap_ = bytes;
-    return true;
-}
-bool Engine::ensure_qstage(size_t bytes) {
-    if (bytes <= qstage_cap_) return true;
-    if (qstage_) hipFree(qstage_);
-    qstage_ = nullptr;
-    qstage_cap_ = 0;
-    if (hipMalloc(&qstage_, bytes) != hipSuccess) { qstage_ = nullptr; set_error("device allocation failed"); return false; }
-    qstage_cap_ = bytes;
+bool Engine::ensure_device(void *&p, size_t &cap, size_t bytes) {
+    if (bytes <= cap) return true;
+    if (p) hipFree(p);
+    p = nullptr;
+    cap = 0;
+    if (hipMalloc(&p, bytes) != hipSuccess) { p = nullptr; set_error("device allocation failed"); return false; }
+    cap = bytes;
     return true;
 }
 bool Engine::pinned_chunk(size_t idx, size_t bytes, PinnedChunk **out) {
@@ -1657,27 +1631,6 @@ bool Engine::copy_weights_from(Engine &src) {
     return build_persist_tables();   // the tables derived from the weights, now that they are in place
 }
 
-namespace {
-// a HIP event for the length of a scope
-struct Event {
-    hipEvent_t ev = nullptr;
-    explicit Event(unsigned flags = hipEventDefault) { hipEventCreateWithFlags(&ev, flags); }
-    ~Event() { if (ev) hipEventDestroy(ev); }
-    Event(const Event &) = delete;
-    Event &operator=(const Event &) = delete;
-    operator hipEvent_t() const { return ev; }   // null if the creation failed: the first use reports it
-};
-// runs f on every exit of the scope
-template <class F>
-struct ScopeExit {
-    F f;
-    explicit ScopeExit(F fn) : f(std::move(fn)) {}
-    ~ScopeExit() { f(); }
-    ScopeExit(const ScopeExit &) = delete;
-    ScopeExit &operator=(const ScopeExit &) = delete;
-};
-}  // namespace
-
 bool Engine::generate(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                       const GenParams &gp, int32_t *codes, int *n_frames, FrameCb on_frames, void *user, int interval,
                       const UttParams *up) {
@@ -1733,6 +1686,16 @@ bool Engine::check_utt_args(int n_utt, const int32_t *const *tokens, const int *
     std::vector<int> idx;
     std::vector<SlotPlan> plan;
     return plan_rows(c_, n_utt, tokens, n_tokens, max_trailing_, idx, plan);
+}
+
+bool Engine::resolve_utt_params(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
+                                const GenParams &gp, const UttParams *up, std::vector<UttParams> &ups, std::vector<int> &plen) {
+    if (up) return check_utt_args(n_utt, tokens, n_tokens, speaker, gp, up, ups, plen);
+    int plen0 = 0;
+    if (!check_gen_args(n_utt, tokens, n_tokens, speaker, gp, &plen0)) return false;
+    ups.assign(n_utt, UttParams{gp.language_id, gp.max_len, gp.rep_penalty, gp.temperature, gp.top_k, gp.force_frames});
+    plen.assign(n_utt, plen0);
+    return true;
 }
 
 void Engine::set_gen_params(const GenParams &gp) {
@@ -1800,20 +1763,11 @@ private:
     static constexpr int NCB = 16;
     struct Chunk { int start; int32_t *codes; int *done; hipEvent_t ev; };
     bool take_chunk(Chunk &c) {   // the next pinned chunk of the context's pool, grown to this call's chunk size
-        const size_t chunk_bytes = ((size_t)S_ * interval_ * NCB + S_) * 4;
-        if (next_chunk_ == e_.chunk_pool_.size()) e_.chunk_pool_.push_back(PinnedChunk{});
-        PinnedChunk &pc = e_.chunk_pool_[next_chunk_++];
-        if (pc.cap < chunk_bytes) {
-            if (pc.codes) hipHostFree(pc.codes);
-            pc.codes = nullptr;
-            pc.cap = 0;
-            Q3T_HIP(hipHostMalloc(&pc.codes, chunk_bytes, hipHostMallocDefault));
-            pc.cap = chunk_bytes;
-        }
-        if (!pc.ev) Q3T_HIP(hipEventCreateWithFlags(&pc.ev, hipEventDisableTiming));
-        c.codes = pc.codes;
-        c.done = pc.codes + (size_t)S_ * interval_ * NCB;
-        c.ev = pc.ev;
+        PinnedChunk *pc = nullptr;
+        if (!e_.pinned_chunk(next_chunk_++, ((size_t)S_ * interval_ * NCB + S_) * 4, &pc)) return false;
+        c.codes = pc->codes;
+        c.done = pc->codes + (size_t)S_ * interval_ * NCB;
+        c.ev = pc->ev;
         return true;
     }
     // a chunk is handed to the caller only once the persistent kernels behind it are known to be fault-free
@@ -1822,7 +1776,7 @@ private:
         if (e_.persist_error()) { *fault_ = true; return false; }
         for (int s = 0; s < S_; ++s) {
             if (st_.stop_at[s] >= 0) continue;
-            const int nf = c.done[s] >= 0 ? std::min(c.done[s], cap_[s]) : cap_[s];
+            const int nf = frames_of(c.done[s], cap_[s]);
             if (nf < c.start + interval_) continue;   // partial chunks go to the final flush, as in the reference
             if (c.start + interval_ <= st_.delivered[s]) continue;   // delivered before a fallback re-run
             st_.delivered[s] = c.start + interval_;
@@ -1859,14 +1813,7 @@ bool Engine::generate_once(int n_utt, const int32_t *const *tokens, const int *n
     // slot's own, the prompt rows packed and the ragged prefill
     std::vector<UttParams> ups;
     std::vector<int> posv;
-    if (up) {
-        if (!check_utt_args(S, tokens, n_tokens, speaker, gp, up, ups, posv)) return false;
-    } else {
-        int plen = 0;
-        if (!check_gen_args(S, tokens, n_tokens, speaker, gp, &plen)) return false;
-        ups.assign(S, UttParams{gp.language_id, gp.max_len, gp.rep_penalty, gp.temperature, gp.top_k, gp.force_frames});
-        posv.assign(S, plen);
-    }
+    if (!resolve_utt_params(S, tokens, n_tokens, speaker, gp, up, ups, posv)) return false;
     const int plen = posv[0];   // (the call-wide form's)
     int loop_len = 0;           // the longest record: a slot past its own max_len runs on, its frames are not returned
     for (int s = 0; s < S; ++s) loop_len = std::max(loop_len, ups[s].max_len);
@@ -1965,7 +1912,7 @@ bool Engine::generate_once(int n_utt, const int32_t *const *tokens, const int *n
         *fault = true;
         return false;
     }
-    for (int s = 0; s < S; ++s) n_frames[s] = done_h[s] >= 0 ? std::min(done_h[s], cap[s]) : cap[s];
+    for (int s = 0; s < S; ++s) n_frames[s] = frames_of(done_h[s], cap[s]);
     if (!streamer.flush(codes, n_frames)) return false;
     float ms1 = 0, ms2 = 0;
     hipEventElapsedTime(&ms1, e0, e1);
@@ -1973,755 +1920,6 @@ bool Engine::generate_once(int n_utt, const int32_t *const *tokens, const int *n
     last_prefill_ms = ms1;
     last_frames_ms = ms2;
     return true;
-}
-
-// ------------------------------------------------------------------------------------------ continuous batching
-// Admissions run on their own stream with private scratch, overlapping the frame loop of the other slots (at many
-// slots the decode step leaves most of the chip idle).  The slots freed since the last admission are admitted
-// together: their prompts are projected in one pass and run through ONE causal prefill (Engine::prefill), which
-// writes the K/V rows [0, plen) of the target slots directly.  A target slot is parked in the frame loop meanwhile
-// (done >= 0: no selection, no advance, its position >= plen): the frame graph still runs it, but writes only its own
-// x / hidden / logits rows and the KV row at its parked position, none of which the admission writes.  The slot joins
-// the frame loop (activate_slot, main stream, between two frames) once its admission batch has finished.  The prefill
-// runs the running batch's kernels (S_main = q_slots_), whose per-row arithmetic does not depend on the other rows: a
-// slot's prefill is what generate()'s prefill computes for it, whichever slots were admitted alongside.
-bool Engine::alloc_admission() {
-    if (astream_) return true;
-    const int S = max_slots_, H = c_.hidden;
-    if (!ensure_prefill()) return false;
-    ahidden_ = dalloc<float>((size_t)S * H);
-    alogits_ = dalloc<float>((size_t)S * c_.codec_vocab);
-    delivered_ = dalloc<int>(S);
-    qmask_ = dalloc<int>(S);
-    if (!alloc_prompt_scratch(adm_ps_, nullptr)) return false;
-    if (!ahidden_ || !alogits_ || !delivered_ || !qmask_) { set_error("device allocation failed"); return false; }
-    // every buffer was zeroed on stream_ and drained by dalloc before the admission stream exists
-    Q3T_HIP(hipStreamCreateWithFlags(&astream_, hipStreamNonBlocking));
-    return true;
-}
-
-// admission batch on stream `as`: utterances utt[j] into slots tgt[j] (text projection, prefill / trailing / pad
-// rows, the causal prefill into the target slots, hidden / logits rows per target slot).  tgt_h: pinned
-// copy of tgt (alive until the batch has run); trailing_len[j]: the slot's trailing-text length
-bool Engine::admit_batch(const std::vector<int> &tgt, const std::vector<int> &utt, const int32_t *const *tokens,
-                         const int *n_tokens, const float *const *speaker, const std::vector<UttParams> &ups,
-                         const std::vector<int> &plen, bool ragged, hipStream_t as, int *tgt_h,
-                         std::vector<int> &trailing_len) {
-    const int H = c_.hidden, a = (int)tgt.size();
-    std::vector<PromptEntry> in(a);
-    std::vector<int> lens(a), got;
-    for (int j = 0, row = 0; j < a; row += lens[j], ++j) {
-        lens[j] = plen[utt[j]];
-        in[j] = PromptEntry{tokens[utt[j]], n_tokens[utt[j]], speaker ? speaker[utt[j]] : nullptr, tgt[j], ragged ? row : j * 10,
-                            ups[utt[j]].language_id};
-    }
-    if (!assemble_prompts(adm_ps_, as, in, got, trailing_len)) return false;
-    if (got != lens) { set_error("admit_batch: prefill length mismatch"); return false; }
-    // the causal prefill of the batch with the running batch's kernels (S_main = q_slots_), K/V straight into the
-    // target slots' rows [0, plen)
-    for (int j = 0; j < a; ++j) tgt_h[j] = tgt[j];
-    Q3T_HIP(hipMemcpyAsync(pf_slot_, tgt_h, a * 4, hipMemcpyHostToDevice, as));
-    if (ragged ? !prefill_ragged(a, lens.data(), adm_ps_.rows, q_slots_, as, adm_ps_) : !prefill(a, lens[0], adm_ps_.rows, q_slots_, as))
-        return false;
-    const int V = c_.codec_vocab;
-    for (int j = 0; j < a; ++j) {
-        const size_t r = (ragged ? (size_t)in[j].row : (size_t)j * lens[0]) + lens[j] - 1;
-        Q3T_HIP(hipMemcpyAsync(ahidden_ + (size_t)tgt[j] * H, pf_hid_ + r * H, H * 4, hipMemcpyDeviceToDevice, as));
-        Q3T_HIP(hipMemcpyAsync(alogits_ + (size_t)tgt[j] * V, pf_logits_ + r * V, (size_t)V * 4, hipMemcpyDeviceToDevice, as));
-    }
-    return true;
-}
-
-// slot k joins the frame loop (main stream, between two frames, after its admission batch): per-slot state, the
-// last prefill step's hidden state, and the CB0 of its first frame selected from the last prefill logits.
-// state_h: pinned [16]
-bool Engine::activate_slot(int k, uint64_t utt, int trailing_len, int n_tok, const UttParams &up, int plen, int *state_h,
-                           bool deliveries) {
-    const int H = c_.hidden, NCB = 16;
-    state_h[0] = trailing_len; state_h[1] = n_tok; state_h[2] = up.force_frames; state_h[3] = -1;
-    state_h[4] = plen; state_h[5] = 0;
-    std::memcpy(state_h + 6, &utt, 8);
-    state_h[8] = up.max_len;
-    const SelRec rec = sel_rec(up);
-    std::memcpy(state_h + 12, &rec, sizeof rec);
-    if (own_max_len_) Q3T_HIP(hipMemcpyAsync(slot_max_len_ + k, state_h + 8, 4, hipMemcpyHostToDevice, stream_));
-    if (rec_on_) Q3T_HIP(hipMemcpyAsync(sel_rec_ + k, state_h + 12, sizeof rec, hipMemcpyHostToDevice, stream_));
-    Q3T_HIP(hipMemcpyAsync(trailing_len_ + k, state_h + 0, 4, hipMemcpyHostToDevice, stream_));
-    Q3T_HIP(hipMemcpyAsync(n_tokens_ + k, state_h + 1, 4, hipMemcpyHostToDevice, stream_));
-    Q3T_HIP(hipMemcpyAsync(force_ + k, state_h + 2, 4, hipMemcpyHostToDevice, stream_));
-    Q3T_HIP(hipMemcpyAsync(utt_ + k, state_h + 6, 8, hipMemcpyHostToDevice, stream_));
-    Q3T_HIP(hipMemsetAsync(seen_ + (size_t)k * c_.codec_vocab, 0, c_.codec_vocab, stream_));
-    Q3T_HIP(hipMemsetAsync(codes_ + (size_t)k * codes_max_len_ * NCB, 0, (size_t)codes_max_len_ * NCB * 4, stream_));
-    Q3T_HIP(hipMemcpyAsync(hidden_ + (size_t)k * H, ahidden_ + (size_t)k * H, H * 4, hipMemcpyDeviceToDevice, stream_));
-    Q3T_HIP(hipMemcpyAsync(pos_ + k, state_h + 4, 4, hipMemcpyHostToDevice, stream_));
-    Q3T_HIP(hipMemcpyAsync(frame_ + k, state_h + 5, 4, hipMemcpyHostToDevice, stream_));
-    if (deliveries) Q3T_HIP(hipMemsetAsync(delivered_ + k, 0, 4, stream_));   // queue deliveries: nothing collected yet
-    Q3T_HIP(hipMemcpyAsync(done_ + k, state_h + 3, 4, hipMemcpyHostToDevice, stream_));
-    SelectSpec sp = select_spec(SEL_CB0, gp_, 0, 0);   // the slot's rows of every per-slot array
-    sp.tokens += (size_t)k * 16; sp.codes += (size_t)k * codes_max_len_ * NCB; sp.frame += k; sp.done += k; sp.utt += k;
-    sp.seen += (size_t)k * c_.codec_vocab; sp.n_tokens += k; sp.force_frames += k;
-    if (sp.ticket) sp.ticket += k;
-    if (sp.rec) sp.rec += k;
-    return select_tokens(sp, alogits_ + (size_t)k * c_.codec_vocab, 1, stream_);
-}
-
-// Deliveries of generate_queue() (DESIGN 2f "Queue deliveries").  A collection is ONE k_queue_collect launch over the
-// slots of a mask, one copy of the staging chunk (rows, header, error word) into a pinned chunk of the context's pool
-// and one event.  The device keeps each slot's collected-frames counter, so the host uploads the mask and nothing
-// else.  Chunks are delivered in stream order, a tick's chunk one tick late and a finish chunk one frame late, so
-// the GPU runs the queued frames during the callback; each is handed out only once the persistent kernels behind it
-// are known to be fault-free.
-class Engine::QueueStreamer {
-public:
-    // own_max_len: a collection clamps each slot's frames to its own max_len (slot_max_len_) as well
-    QueueStreamer(Engine &e, int S, int n_utt, int max_len, bool own_max_len, QueueCb cb, void *user, int interval,
-                  QueueState &st, bool *fault)
-        : e_(e), S_(S), max_len_(max_len), interval_(interval), own_max_len_(own_max_len), cb_(cb), user_(user), st_(st),
-          fault_(fault), run_(n_utt) {}
-    bool active() const { return cb_ != nullptr; }
-    int interval() const { return interval_; }
-    bool begin() {   // the staging chunk with a clear error word
-        if (!e_.ensure_qstage(stage_ints() * 4)) return false;
-        Q3T_HIP(hipMemsetAsync(static_cast<int *>(e_.qstage_) + stage_ints() - 1, 0, 4, e_.stream_));
-        return true;
-    }
-    // one collection over the slots k with sel[k] != 0 (slot_utt[k]: the slot's utterance), queued behind what the
-    // stream holds; its chunk is due when the loop clock reaches `due`
-    bool collect(const std::vector<int> &slot_utt, const std::vector<char> &sel, bool final, int due) {
-        Chunk c;
-        if (!pool_.empty()) { c = pool_.back(); pool_.pop_back(); }
-        else {
-            PinnedChunk *pc = nullptr;   // rows [S][interval][16], header [S], error word, then the mask's source [S]
-            if (!e_.pinned_chunk(next_chunk_++, (stage_ints() + S_) * 4, &pc)) return false;
-            c.rows = pc->codes;
-            c.ev = pc->ev;
-        }
-        c.final = final;
-        c.due = due;
-        c.utt.assign(S_, -1);
-        int *mask = c.rows + stage_ints();
-        for (int k = 0; k < S_; ++k) {
-            mask[k] = sel[k] ? 1 : 0;
-            if (sel[k]) c.utt[k] = slot_utt[k];
-        }
-        int32_t *stage = static_cast<int32_t *>(e_.qstage_);
-        Q3T_HIP(hipMemcpyAsync(e_.qmask_, mask, S_ * 4, hipMemcpyHostToDevice, e_.stream_));
-        QueueCollect q;
-        q.mask = e_.qmask_; q.done = e_.done_; q.frame = e_.frame_; q.delivered = e_.delivered_;
-        q.codes = e_.codes_;
-        q.rows = stage;
-        q.header = stage + (size_t)S_ * interval_ * NCB;
-        q.error = stage + stage_ints() - 1;
-        q.interval = interval_; q.codes_max_len = e_.codes_max_len_; q.max_len = max_len_;
-        if (own_max_len_) q.slot_max_len = e_.slot_max_len_;
-        if (!queue_collect(q, S_, e_.stream_)) return false;
-        Q3T_HIP(hipMemcpyAsync(c.rows, stage, stage_ints() * 4, hipMemcpyDeviceToHost, e_.stream_));
-        Q3T_HIP(hipEventRecord(c.ev, e_.stream_));
-        pend_.push_back(c);
-        return true;
-    }
-    // the pending chunks up to the last one due at loop clock f, oldest first
-    bool deliver_due(int f) {
-        size_t n = 0;
-        for (size_t i = 0; i < pend_.size(); ++i)
-            if (pend_[i].due <= f) n = i + 1;
-        for (size_t i = 0; i < n && !st_.aborted; ++i) {
-            Chunk c = pend_.front();
-            pend_.erase(pend_.begin());
-            pool_.push_back(c);
-            if (!deliver(c)) { hipStreamSynchronize(e_.stream_); return false; }
-        }
-        return true;
-    }
-    bool flush() { return deliver_due(INT_MAX); }
-    // utterances the callback cancelled since the last call (their slots are still running)
-    std::vector<int> take_stops() { std::vector<int> s; s.swap(stops_); return s; }
-
-private:
-    static constexpr int NCB = 16;
-    struct Chunk { int32_t *rows = nullptr; hipEvent_t ev = nullptr; bool final = false; int due = 0; std::vector<int> utt; };
-    size_t stage_ints() const { return (size_t)S_ * interval_ * NCB + S_ + 1; }
-    bool deliver(const Chunk &c) {
-        Q3T_HIP(hipEventSynchronize(c.ev));
-        if (e_.persist_error()) { *fault_ = true; return false; }
-        const int *hdr = c.rows + (size_t)S_ * interval_ * NCB;
-        if (hdr[S_] != 0) { set_error("generate_queue: a collection was out of step with its slot"); return false; }
-        // (a fallback re-run generates every utterance again: queue_deliver.h keeps what was handed out apart)
-        std::vector<QueueEntry> ent;
-        queue_plan(hdr, c.utt, c.final, st_, run_, ent, stops_);
-        if (ent.empty()) return true;
-        const size_t m = ent.size();
-        std::vector<int32_t> utt(m), nf(m), fin(m), stop(m, 0);
-        std::vector<const int32_t *> cp(m);
-        for (size_t i = 0; i < m; ++i) {
-            utt[i] = ent[i].utt; nf[i] = ent[i].n; fin[i] = ent[i].final;
-            cp[i] = c.rows + ((size_t)ent[i].slot * interval_ + ent[i].skip) * NCB;
-        }
-        const int go = cb_(user_, (int32_t)m, utt.data(), cp.data(), nf.data(), fin.data(), stop.data());
-        queue_commit(ent, stop.data(), go != 0, st_, run_, stops_);
-        return true;
-    }
-    Engine &e_;
-    const int S_, max_len_, interval_;
-    const bool own_max_len_;
-    const QueueCb cb_;
-    void *const user_;
-    QueueState &st_;
-    bool *const fault_;
-    QueueRun run_;                    // this run's per-utterance progress (queue_deliver.h)
-    std::vector<int> stops_;          // utterances to cancel: their slots may still be running
-    size_t next_chunk_ = 0;           // chunk_pool_[0, next_chunk_) are in use by this call
-    std::vector<Chunk> pend_, pool_;  // collections in flight, oldest first; chunks delivered and free for reuse
-};
-
-// Text feeds (DESIGN 2f "Text feeds").  A round is what the asks of one loop iteration produced: new text ids of some
-// slots (feed_.ids, with one trailing tts_eos id if an utterance closed), where their projected rows go (feed_.rows),
-// the counters they publish (feed_.commit) and the slots to hold / release (feed_.hold / feed_.rel).  It travels as
-// ONE pinned blob -> ONE device blob [hold S | release S | commit 3 n | rows 3 n | ids n] on the main stream, followed
-// by the text projection over all ids, one k_text_append and at most one hold and one release launch.
-bool Engine::ensure_text_feed() {
-    FeedScratch &F = feed_;
-    if (F.dev) return true;
-    const int S = max_slots_;
-    F.cap_rows = S * max_trailing_ + 1;
-    F.cap_ints = (size_t)5 * S + (size_t)4 * F.cap_rows;
-    if (F.cap_rows > main_ps_.cap) { set_error("text feeds: projection scratch too small"); return false; }
-    int *dev = dalloc<int>(F.cap_ints + 1);
-    hold_save_ = dalloc<float>((size_t)S * c_.hidden);
-    held_flag_ = dalloc<int>(S);
-    if (!dev || !hold_save_ || !held_flag_) { set_error("device allocation failed"); return false; }
-    for (int b = 0; b < FeedScratch::NBUF; ++b) {
-        Q3T_HIP(hipHostMalloc(reinterpret_cast<void **>(&F.pin[b]), F.cap_ints * 4, hipHostMallocDefault));
-        Q3T_HIP(hipEventCreate(&F.e0[b]));
-        Q3T_HIP(hipEventCreate(&F.e1[b]));
-    }
-    F.ids.reserve(F.cap_rows); F.rows.reserve((size_t)3 * F.cap_rows); F.commit.reserve((size_t)3 * S);
-    F.hold.reserve(S); F.rel.reserve(S);
-    F.error = dev + F.cap_ints;   // zeroed by dalloc
-    F.dev = dev;
-    return true;
-}
-
-bool Engine::drain_text_rounds() {
-    FeedScratch &F = feed_;
-    for (int i = 0; i < FeedScratch::NBUF; ++i) {
-        const int b = (F.next + i) % FeedScratch::NBUF;   // oldest first
-        if (!F.used[b]) continue;
-        F.used[b] = false;
-        Q3T_HIP(hipEventSynchronize(F.e1[b]));
-        float ms = 0;
-        Q3T_HIP(hipEventElapsedTime(&ms, F.e0[b], F.e1[b]));
-        text_stats.feed_ms += ms;
-    }
-    return true;
-}
-
-bool Engine::enqueue_text_round(int S, bool any_hold, bool any_rel) {
-    FeedScratch &F = feed_;
-    const int b = F.next;
-    F.next = (b + 1) % FeedScratch::NBUF;
-    if (F.used[b]) {   // the round that last used this blob: long since run, unless the host is NBUF rounds ahead
-        F.used[b] = false;
-        Q3T_HIP(hipEventSynchronize(F.e1[b]));
-        float ms = 0;
-        Q3T_HIP(hipEventElapsedTime(&ms, F.e0[b], F.e1[b]));
-        text_stats.feed_ms += ms;
-    }
-    const int n_ids = (int)F.ids.size(), n_rows = (int)F.rows.size() / 3, n_commit = (int)F.commit.size() / 3;
-    if (n_ids > F.cap_rows || n_rows > F.cap_rows || n_commit > S || (int)F.hold.size() != S || (int)F.rel.size() != S) {
-        set_error("text feeds: round larger than its scratch");
-        return false;
-    }
-    int *p = F.pin[b];
-    const size_t o_rel = S, o_commit = (size_t)2 * S, o_rows = (size_t)5 * S, o_ids = o_rows + (size_t)3 * n_rows;
-    std::memcpy(p, F.hold.data(), (size_t)S * 4);
-    std::memcpy(p + o_rel, F.rel.data(), (size_t)S * 4);
-    std::memset(p + o_commit, 0, (size_t)3 * S * 4);
-    if (n_commit) std::memcpy(p + o_commit, F.commit.data(), (size_t)3 * n_commit * 4);
-    if (n_rows) std::memcpy(p + o_rows, F.rows.data(), (size_t)3 * n_rows * 4);
-    if (n_ids) std::memcpy(p + o_ids, F.ids.data(), (size_t)n_ids * 4);
-    Q3T_HIP(hipEventRecord(F.e0[b], stream_));
-    Q3T_HIP(hipMemcpyAsync(F.dev, p, (o_ids + n_ids) * 4, hipMemcpyHostToDevice, stream_));
-    if (n_ids && !enqueue_text_projection(n_ids, stream_, F.dev + o_ids, main_ps_.h, main_ps_.out, true)) return false;
-    TextAppend t;
-    t.src = main_ps_.out; t.trailing = trailing_; t.rows = F.dev + o_rows; t.commit = F.dev + o_commit;
-    t.trailing_len = trailing_len_; t.n_tokens = n_tokens_; t.error = F.error;
-    t.n_rows = n_rows; t.n_commit = n_commit; t.src_rows = n_ids; t.S = S; t.max_trailing = max_trailing_; t.H = c_.hidden;
-    if (!text_append(t, stream_)) return false;
-    SlotHold h;
-    h.hidden = hidden_; h.save = hold_save_; h.done = done_; h.held = held_flag_; h.frame = frame_; h.H = c_.hidden;
-    h.mask = F.dev + o_rel;
-    if (any_rel && !slot_release(h, S, stream_)) return false;
-    h.mask = F.dev;
-    if (any_hold && !slot_hold(h, S, stream_)) return false;
-    Q3T_HIP(hipEventRecord(F.e1[b], stream_));
-    F.used[b] = true;
-    ++text_stats.feed_rounds;
-    return true;
-}
-
-bool Engine::generate_queue_once(int n_utt, const int32_t *const *tokens_in, const int *n_tokens_in, const float *const *speaker,
-                                 const GenParams &gp, const UttParams *up, int32_t *codes, int *n_frames, int max_active,
-                                 bool *faulted, QueueCb on_batch, void *user, int interval, QueueState &qst,
-                                 const TextFeed *text, TextLog *tlog) {
-    *faulted = false;
-    if (n_utt <= 0) return true;
-    const int S = std::min(max_slots_, n_utt), NCB = 16;
-    if (max_active <= 0 || max_active > S) max_active = S;
-    for (int u = 0; u < n_utt; ++u) n_frames[u] = 0;
-    if (gp.max_len <= 0) return true;
-    // open utterances (text feeds): a head [3 role ids, >= 1 text id] runs as the prompt head || five ids, whose rows
-    // are exactly the head's (the five are dropped by plan_rows); its trailing row K0 = n_head - 4, the tts_eos row of
-    // that prompt, is not counted while the text is open and is overwritten by the first feed
-    const int32_t *const *tokens = tokens_in;
-    const int *n_tokens = n_tokens_in;
-    std::vector<std::vector<int32_t>> head_pad;
-    std::vector<const int32_t *> tok_eff;
-    std::vector<int> nt_eff;
-    if (text) {
-        tok_eff.assign(tokens_in, tokens_in + n_utt);
-        nt_eff.assign(n_tokens_in, n_tokens_in + n_utt);
-        head_pad.resize(n_utt);
-        for (int u = 0; u < n_utt; ++u) {
-            if (!text->open[u]) continue;
-            const std::string who = "utterance " + std::to_string(u) + ": ";
-            if (n_tokens_in[u] < 4) { set_error(who + "an open utterance needs a head of at least 4 ids"); return false; }
-            if (n_tokens_in[u] - 4 + 1 > max_trailing_) { set_error(who + "head too long for the trailing-text buffer"); return false; }
-            for (int i = 0; i < n_tokens_in[u]; ++i)
-                if (tokens_in[u][i] < 0 || tokens_in[u][i] >= c_.text_vocab) { set_error(who + "text token out of range"); return false; }
-            head_pad[u].assign(tokens_in[u], tokens_in[u] + n_tokens_in[u]);
-            head_pad[u].insert(head_pad[u].end(), 5, c_.tts_pad);
-            tok_eff[u] = head_pad[u].data();
-            nt_eff[u] = n_tokens_in[u] + 5;
-        }
-        tokens = tok_eff.data();
-        n_tokens = nt_eff.data();
-        if (!ensure_text_feed()) return false;
-    }
-    // the call-wide form: one record and one prompt length for every utterance.  With records (up): each utterance's own;
-    // admission batches then pack their prompt rows and run the ragged prefill
-    std::vector<UttParams> ups;
-    std::vector<int> plens;
-    if (up) {
-        if (!check_utt_args(n_utt, tokens, n_tokens, speaker, gp, up, ups, plens)) return false;
-    } else {
-        int plen0 = 0;
-        if (!check_gen_args(n_utt, tokens, n_tokens, speaker, gp, &plen0)) return false;
-        ups.assign(n_utt, UttParams{gp.language_id, gp.max_len, gp.rep_penalty, gp.temperature, gp.top_k, gp.force_frames});
-        plens.assign(n_utt, plen0);
-    }
-    bool mixed_plen = false;
-    for (int u = 0; u < n_utt; ++u) mixed_plen = mixed_plen || plens[u] != plens[0];
-    // where a free slot waits: above the rows any prefill of the call writes
-    const int plen = mixed_plen ? 10 : plens[0];
-    if (gp.max_len > codes_max_len_) { set_error("max_len exceeds the code buffer"); return false; }
-    if (!alloc_admission()) return false;
-    q_slots_ = S;
-    // the single-slot context runs persistent kernels, which need the whole device: admissions go on the main stream
-    hipStream_t as = (S == 1 && persist_enabled()) ? stream_ : astream_;
-    rec_on_ = up && S > 1;
-    own_max_len_ = up != nullptr;
-    // one slot with records: each utterance's values go into the scalars when it takes the slot (activate below)
-    GenParams g1 = gp;
-    auto one_slot_params = [&](const UttParams &r) {
-        if (r.temperature == gp_.temperature && r.top_k == gp_.top_k && r.rep_penalty == gp_.rep_penalty) return;
-        hipStreamSynchronize(stream_);   // the frame graphs about to be dropped may still run
-        g1.temperature = r.temperature; g1.top_k = r.top_k; g1.rep_penalty = r.rep_penalty;
-        set_gen_params(g1);
-    };
-    if (!up) set_gen_params(gp);
-    if (!set_seed(gp.seed, stream_)) return false;
-    // the finished utterances' codes, copied to the caller once at the end (device scratch kept by the context)
-    // (a caller that takes deliveries may pass no codes buffer: nothing is parked then)
-    if (codes && !ensure_qout((size_t)n_utt * gp.max_len * NCB * 4)) return false;
-    int32_t *out_dev = codes ? static_cast<int32_t *>(qout_) : nullptr;
-    QueueStreamer qs(*this, S, n_utt, gp.max_len, up != nullptr, on_batch, user, interval, qst, faulted);
-    if (qs.active() && !qs.begin()) return false;
-    if ((qs.active() || up || text) && out_dev)   // an aborted call copies out rows of utterances that never ran (and with records
-                                          // a release parks only the utterance's own max_len rows)
-        Q3T_HIP(hipMemsetAsync(out_dev, 0, (size_t)n_utt * gp.max_len * NCB * 4, stream_));
-    // [S][16] activation staging, [S] done flags, [S] admission targets, the constants 0 (parking) and the waiting
-    // position: pinned, kept
-    // (text feeds: [S] held flags behind them, polled beside the done flags)
-    if (!ensure_pinned(((size_t)S * 19 + 2) * 4)) return false;
-    int *pin = static_cast<int *>(pin_);
-    int *done_h = pin + (size_t)S * 16, *tgt_h = pin + (size_t)S * 17, *park = pin + (size_t)S * 18;
-    int *held_h = pin + (size_t)S * 18 + 2;
-    for (int k = 0; k < S; ++k) held_h[k] = 0;
-    park[0] = 0;
-    park[1] = plen;
-    Event aev(hipEventDisableTiming), pev(hipEventDisableTiming), rev(hipEventDisableTiming);
-    // every exit drains both streams and leaves the context as generate() expects it: kernels chosen by the call's
-    // own slot count, sampling keyed by slot index
-    ScopeExit restore([&] {
-        hipStreamSynchronize(as);
-        hipStreamSynchronize(stream_);
-        policy_slots_ = 0;
-        std::vector<uint64_t> ident(max_slots_);
-        for (int k = 0; k < max_slots_; ++k) ident[k] = (uint64_t)k;
-        hipMemcpyAsync(utt_, ident.data(), max_slots_ * 8, hipMemcpyHostToDevice, stream_);
-        hipStreamSynchronize(stream_);
-    });
-    // every slot starts parked: done = 0 (no selection, no advance), position plen (above the rows a prefill writes),
-    // valid code ids for the gathers it still runs through, no trailing text
-    {
-        std::vector<int> pl(S, plen);
-        Q3T_HIP(hipMemsetAsync(done_, 0, S * 4, stream_));
-        Q3T_HIP(hipMemcpyAsync(pos_, pl.data(), S * 4, hipMemcpyHostToDevice, stream_));
-        Q3T_HIP(hipMemsetAsync(frame_, 0, S * 4, stream_));
-        Q3T_HIP(hipMemsetAsync(tokens_, 0, (size_t)S * 16 * 4, stream_));
-        Q3T_HIP(hipMemsetAsync(trailing_len_, 0, S * 4, stream_));
-        if (text) Q3T_HIP(hipMemsetAsync(held_flag_, 0, S * 4, stream_));
-        Q3T_HIP(hipStreamSynchronize(stream_));
-    }
-    enum { FREE, PENDING, ACTIVE };
-    std::vector<int> state(S, FREE), slot_utt(S, -1), tl(S, 0);
-    // ran[k]: the frames launched for slot k's utterance (while it was active and not held); ran_polled[k]: the same when
-    // the done flags now in done_h were copied.  Without text feeds a slot runs every frame of the loop: ran[k] is the
-    // loop clock less the slot's activation frame.
-    std::vector<int> ran(S, 0), ran_polled(S, 0);
-    std::vector<int> batch_tgt, batch_tl;   // the admission batch in flight (at most one)
-    int next = 0, f = 0, n_fin = 0, n_busy = 0;
-    // ---- text feeds: per utterance the known trailing rows K and whether its text has ended, per slot whether the host
-    // holds it and whether its utterance was activated since the last asks.  A one-slot context holds by not launching
-    // (its persistent kernels own the device; nothing else would run): the device-side hold is for slots that share a
-    // frame graph with running ones.
-    const bool dev_hold = text && S > 1;
-    std::vector<int> rows_known(text ? n_utt : 0, 0), replay_piece(text ? n_utt : 0, 0), replay_id(text ? n_utt : 0, 0);
-    std::vector<char> is_open(n_utt, 0), closed(n_utt, 1), hheld(S, 0), fresh(S, 0);
-    bool tick_ask = false;
-    if (text) {
-        text_stats = TextStats{};
-        for (int u = 0; u < n_utt; ++u) {
-            is_open[u] = text->open[u] != 0;
-            closed[u] = !is_open[u];
-            rows_known[u] = n_tokens_in[u] - 4;
-        }
-        feed_.next = 0;
-    }
-    ScopeExit feed_drain([&] { if (text) drain_text_rounds(); });
-    auto admit = [&]() -> bool {   // every free slot, up to max_active busy, one batch
-        std::vector<int> tgt, utt;
-        for (int k = 0; k < S && next + (int)tgt.size() < n_utt && n_busy + (int)tgt.size() < max_active; ++k)
-            if (state[k] == FREE) { tgt.push_back(k); utt.push_back(next + (int)tgt.size() - 1); }
-        if (tgt.empty()) return true;
-        if (mixed_plen && as != stream_) {
-            // a released slot was moved to the waiting position on the main stream (release): the batch's prefill, which
-            // may write more rows than the slot's last utterance had, starts behind that
-            Q3T_HIP(hipEventRecord(rev, stream_));
-            Q3T_HIP(hipStreamWaitEvent(as, rev, 0));
-        }
-        if (!admit_batch(tgt, utt, tokens, n_tokens, speaker, ups, plens, up != nullptr, as, tgt_h, batch_tl)) return false;
-        Q3T_HIP(hipEventRecord(aev, as));
-        for (size_t j = 0; j < tgt.size(); ++j) {
-            state[tgt[j]] = PENDING;
-            slot_utt[tgt[j]] = utt[j];
-            tl[tgt[j]] = batch_tl[j];
-        }
-        next += (int)tgt.size();
-        n_busy += (int)tgt.size();
-        batch_tgt = tgt;
-        return true;
-    };
-    auto activate = [&]() -> bool {   // the batch in flight has finished: its slots join the frame loop
-        if (as != stream_) Q3T_HIP(hipStreamWaitEvent(stream_, aev, 0));
-        for (int k : batch_tgt) {
-            const int u = slot_utt[k];
-            if (up && S == 1) one_slot_params(ups[u]);
-            // an open utterance: its rows without the tts_eos row, n_tokens = K + 9 (what the padded head counts)
-            if (!activate_slot(k, (uint64_t)u, tl[k] - (is_open[u] ? 1 : 0), n_tokens[u], ups[u], plens[u], pin + (size_t)k * 16, qs.active())) return false;
-            if (dev_hold) Q3T_HIP(hipMemsetAsync(held_flag_ + k, 0, 4, stream_));
-            state[k] = ACTIVE;
-            ran[k] = 0;
-            hheld[k] = 0;
-            fresh[k] = 1;
-        }
-        batch_tgt.clear();
-        return true;
-    };
-    if (!admit() || !activate()) return false;
-    // frame graph over slots [0, S_eff): S_eff = the highest busy slot + 1, rounded up to 8, never below the smallest
-    // batch that keeps the S-slot kernel family (matrix cores from 4 slots, k_attn_seq from 16), whose per-token
-    // arithmetic the graph reproduces (policy_slots_ = S): a draining queue stops paying for parked slots
-    const int fam = !mm_ok_ ? 1 : S >= 16 ? 16 : S >= gemm_mfma_min_batch() ? gemm_mfma_min_batch() : S;
-    policy_slots_ = S;
-    auto frame_graph = [&](hipGraphExec_t *g) -> bool {
-        int hi = 0;
-        for (int k = 0; k < S; ++k) if (state[k] != FREE) hi = k + 1;
-        int se = fam < S ? std::max(fam, std::min(S, (hi + 7) / 8 * 8)) : S;
-        const int key = frame_key(se + 65536 * S);
-        if (!graph_for_key(g_frame_, key, se, &Engine::enqueue_frame)) return false;
-        *g = g_frame_[key];
-        return true;
-    };
-    // an utterance leaves its slot (ended, or cancelled by the delivery callback): its codes are parked for the
-    // end-of-call copy and the slot is free for the next admission
-    auto release = [&](int k, bool park_slot) -> bool {
-        const int u = slot_utt[k];
-        if (out_dev)
-            Q3T_HIP(hipMemcpyAsync(out_dev + (size_t)u * gp.max_len * NCB, codes_ + (size_t)k * codes_max_len_ * NCB,
-                                   (size_t)ups[u].max_len * NCB * 4, hipMemcpyDeviceToDevice, stream_));
-        if (park_slot)   // still running: park the slot (no selection, no advance)
-            Q3T_HIP(hipMemcpyAsync(done_ + k, park, 4, hipMemcpyHostToDevice, stream_));
-        if (dev_hold && hheld[k]) Q3T_HIP(hipMemsetAsync(held_flag_ + k, 0, 4, stream_));   // (cancelled while held)
-        hheld[k] = 0;
-        if (mixed_plen)   // its successor's prompt may be longer than the position it stopped at: back to the waiting one
-            Q3T_HIP(hipMemcpyAsync(pos_ + k, park + 1, 4, hipMemcpyHostToDevice, stream_));
-        state[k] = FREE;
-        slot_utt[k] = -1;
-        --n_busy;
-        ++n_fin;
-        return true;
-    };
-    // the chunks due at loop clock `due`, then the slots of the utterances their callbacks cancelled
-    auto deliver = [&](int due) -> bool {
-        if (!qs.deliver_due(due)) return false;
-        for (int u : qs.take_stops()) {
-            for (int k = 0; k < S; ++k)
-                if (state[k] == ACTIVE && slot_utt[k] == u && !release(k, true)) return false;
-            // its length is what it was handed, also when it had ended (and left its slot) before the piece the
-            // callback cancelled it at was delivered
-            n_frames[u] = qst.delivered[u];
-        }
-        return true;
-    };
-    std::vector<char> sel(S, 0);
-    bool polled = false;   // one frame in flight: frame f is launched before frame f-1's done flags are read
-    // the slots whose utterance ended by the polled flags (done_h / held_h, copied when slot k had run ran_polled[k]
-    // frames): a held slot's done flag is its hold, not an end, and a slot the host holds may have ended before
-    // k_slot_hold ran (its real EOS stays and it is not flagged held)
-    auto reap = [&]() -> bool {
-        Q3T_HIP(hipEventSynchronize(pev));
-        bool any = false;
-        for (int k = 0; k < S; ++k) {
-            if (held_h[k]) done_h[k] = -1;
-            sel[k] = state[k] == ACTIVE && !(done_h[k] < 0 && ran_polled[k] < ups[slot_utt[k]].max_len);
-            any = any || sel[k];
-        }
-        // the rest of the finished slots' frames, before a slot is parked or handed to a successor
-        if (qs.active() && any && !qs.collect(slot_utt, sel, true, f + 1)) return false;
-        for (int k = 0; k < S; ++k) {
-            if (!sel[k]) continue;
-            const int d = done_h[k];
-            const int cap = ups[slot_utt[k]].max_len;
-            n_frames[slot_utt[k]] = d >= 0 ? std::min(d, cap) : cap;
-            if (!release(k, d < 0)) return false;   // d < 0: stopped at max_len
-        }
-        return true;
-    };
-    // ---- text feeds: the asks of this iteration and the round they make.  An open utterance that holds a slot is asked
-    // when it was activated (before its first frame), at every tick, and on every iteration on which it has no row for
-    // its next frame.  Each answer is validated, logged (a fallback re-run replays the log instead of asking) and added to
-    // the round; then every open slot is held or released by `frames >= K && !closed`.
-    // n_tokens_ is published as K + 9 with every feed, so CB0's EOS ramp (expected = max(20, 4 * n_tokens)) sees a
-    // count that grows.  That never changes a selection: while the text is open the slot only runs frames f < K, and the
-    // selection at the end of frame f uses frame = f + 1 <= K < 4 * (K + 9) <= 4 * (K_final + 9), so the ramp is off under
-    // the running count and under the final one alike; after the close the two are equal.
-    auto feed_piece = [&](int u, int k, const int32_t *ids, int n, bool end) -> bool {
-        const std::string who = "utterance " + std::to_string(u) + ": ";
-        if (n < 0 || (n > 0 && !ids)) { set_error(who + "bad text feed"); return false; }
-        for (int i = 0; i < n; ++i)
-            if (ids[i] < 0 || ids[i] >= c_.text_vocab) { set_error(who + "fed text token out of range"); return false; }
-        if (rows_known[u] + n + 1 > max_trailing_) { set_error(who + "text feed exceeds the trailing-text buffer"); return false; }
-        FeedScratch &F = feed_;
-        for (int i = 0; i < n; ++i) {
-            F.rows.push_back((int)F.ids.size()); F.rows.push_back(k); F.rows.push_back(rows_known[u] + i);
-            F.ids.push_back(ids[i]);
-        }
-        rows_known[u] += n;
-        if (end) {   // row K becomes the tts_eos row (its source row is fixed up when the round is closed)
-            closed[u] = 1;
-            F.rows.push_back(-1); F.rows.push_back(k); F.rows.push_back(rows_known[u]);
-        }
-        if (n > 0 || end) {
-            F.commit.push_back(k); F.commit.push_back(rows_known[u] + (end ? 1 : 0)); F.commit.push_back(rows_known[u] + 9);
-        }
-        return true;
-    };
-    auto text_round = [&]() -> bool {
-        FeedScratch &F = feed_;
-        F.ids.clear(); F.rows.clear(); F.commit.clear();
-        F.hold.assign(S, 0); F.rel.assign(S, 0);
-        for (int k = 0; k < S && !qst.aborted; ++k) {
-            const int u = slot_utt[k];
-            if (state[k] != ACTIVE || !is_open[u] || closed[u]) { fresh[k] = 0; continue; }
-            if (!(fresh[k] || tick_ask || ran[k] >= rows_known[u])) continue;
-            fresh[k] = 0;
-            // a re-run: the pieces the first run was given by now, without asking again
-            std::vector<TextLog::Piece> &pieces = tlog->pieces[u];
-            bool replayed = false;
-            while (replay_piece[u] < (int)pieces.size() && pieces[replay_piece[u]].frames <= ran[k] && !closed[u]) {
-                const TextLog::Piece pc = pieces[replay_piece[u]++];
-                if (!feed_piece(u, k, tlog->ids[u].data() + replay_id[u], pc.n, pc.end)) return false;
-                replay_id[u] += pc.n;
-                replayed = true;
-            }
-            if (replayed || replay_piece[u] < (int)pieces.size()) continue;
-            const int32_t *ids = nullptr;
-            int32_t n = 0, end = 0;
-            if (!text->cb(text->user, u, ran[k], std::max(0, rows_known[u] - ran[k]), &ids, &n, &end)) { qst.aborted = true; break; }
-            if (n == 0 && !end) continue;
-            if (!feed_piece(u, k, ids, n, end != 0)) return false;
-            if (n > 0) tlog->ids[u].insert(tlog->ids[u].end(), ids, ids + n);
-            pieces.push_back(TextLog::Piece{ran[k], n, end != 0});
-            replay_piece[u] = (int)pieces.size();
-            replay_id[u] = (int)tlog->ids[u].size();
-        }
-        tick_ask = false;
-        if (qst.aborted) return true;
-        bool any_hold = false, any_rel = false, any_eos = false;
-        for (size_t i = 0; i < F.rows.size(); i += 3)
-            if (F.rows[i] < 0) { F.rows[i] = (int)F.ids.size(); any_eos = true; }
-        if (any_eos) F.ids.push_back(c_.tts_eos);
-        for (int k = 0; k < S; ++k) {
-            const int u = slot_utt[k];
-            if (state[k] != ACTIVE || !is_open[u]) continue;
-            const bool want = !closed[u] && ran[k] >= rows_known[u] && ran[k] < ups[u].max_len;
-            if (want && !hheld[k]) {
-                if (text->held) ++text->held[u];
-                if (dev_hold) { F.hold[k] = 1; any_hold = true; }
-            } else if (!want && hheld[k] && dev_hold) {
-                F.rel[k] = 1; any_rel = true;
-            }
-            hheld[k] = want;
-        }
-        if (F.ids.empty() && F.commit.empty() && !any_hold && !any_rel) return true;
-        return enqueue_text_round(S, any_hold, any_rel);
-    };
-    while (n_fin < n_utt && !qst.aborted) {
-        if (text) {
-            if (!text_round()) return false;
-            if (qst.aborted) break;
-        }
-        int n_active = 0, n_run = 0;
-        for (int k = 0; k < S; ++k) {
-            n_active += state[k] == ACTIVE;
-            n_run += state[k] == ACTIVE && !hheld[k];
-        }
-        if (n_active > 0 && n_run == 0) {
-            // every busy slot is held: launch nothing.  What the last poll shows, the pending deliveries (nothing runs
-            // behind them), an admission if one is in flight or possible, then ask again: waiting for text is the
-            // callback's job
-            ++text_stats.idle_rounds;
-            if (polled && !reap()) return false;
-            polled = false;
-            if (qs.active() && !deliver(INT_MAX)) return false;
-            if (qst.aborted) break;
-            if (batch_tgt.empty() && next < n_utt && !admit()) return false;
-            if (!batch_tgt.empty()) {
-                Q3T_HIP(hipEventSynchronize(aev));
-                if (!activate()) return false;
-            }
-            continue;
-        }
-        if (n_active == 0) {   // only an admission in flight: wait for it instead of running empty frames
-            if (qs.active() && !deliver(INT_MAX)) return false;   // nothing runs behind them: hand out what is pending
-            if (qst.aborted) break;
-            if (batch_tgt.empty() && !admit()) return false;
-            Q3T_HIP(hipEventSynchronize(aev));
-            if (!activate()) return false;
-            polled = false;
-            continue;
-        }
-        hipGraphExec_t fg = nullptr;
-        if (!frame_graph(&fg)) return false;
-        if (!persist_fault_hook(S, (persist_ ? 1 : 0) + (persist_cp_ ? 1 : 0))) return false;
-        Q3T_HIP(hipGraphLaunch(fg, stream_));
-        ++f;
-        for (int k = 0; k < S; ++k) ran[k] += state[k] == ACTIVE && !hheld[k];
-        if (text) {
-            ++text_stats.graph_launches;
-            tick_ask = f % interval == 0;
-        }
-        if (qs.active()) {
-            // a tick: the new frames of every active slot, behind this frame's graph; then the chunks due by now (the
-            // previous tick's, and the finish chunks of the previous frame)
-            if (f % qs.interval() == 0) {
-                for (int k = 0; k < S; ++k) sel[k] = state[k] == ACTIVE;
-                if (!qs.collect(slot_utt, sel, false, f + qs.interval())) return false;
-            }
-            if (!deliver(f)) return false;
-            if (qst.aborted) break;
-        }
-        if (polled && !reap()) return false;   // done_h: after frame f-1
-        if (!batch_tgt.empty() && (as == stream_ || hipEventQuery(aev) == hipSuccess) && !activate()) return false;
-        if (batch_tgt.empty() && next < n_utt && !admit()) return false;
-        if (as == stream_ && !batch_tgt.empty() && !activate()) return false;
-        Q3T_HIP(hipMemcpyAsync(done_h, done_, S * 4, hipMemcpyDeviceToHost, stream_));
-        if (dev_hold) Q3T_HIP(hipMemcpyAsync(held_h, held_flag_, S * 4, hipMemcpyDeviceToHost, stream_));
-        ran_polled = ran;
-        Q3T_HIP(hipEventRecord(pev, stream_));
-        polled = true;
-        if (f > (n_utt + 1) * (gp.max_len + plen + 2)) { set_error("generate_queue: no progress"); return false; }
-    }
-    if (qs.active()) {
-        if (!qst.aborted && !qs.flush()) return false;   // the last finish chunks
-        if (qst.aborted) {   // the callback ended the call: every utterance is as long as what it was handed
-            for (int k = 0; k < S; ++k)
-                if (state[k] == ACTIVE && !release(k, false)) return false;
-            for (int u = 0; u < n_utt; ++u) n_frames[u] = qst.delivered[u];
-        } else {
-            for (int u = 0; u < n_utt; ++u)
-                if (qst.stopped[u]) n_frames[u] = qst.delivered[u];   // (a re-run: cancelled before the fault)
-            for (int u = 0; u < n_utt; ++u)
-                if (!(qst.stopped[u] || (qst.finaled[u] && qst.delivered[u] == n_frames[u]))) {
-                    set_error("generate_queue: utterance " + std::to_string(u) + " ended without its final delivery");
-                    return false;
-                }
-        }
-    } else if (qst.aborted) {   // the text callback ended a call without deliveries: the utterances that had ended keep
-                                // their frames, the others have none
-        for (int k = 0; k < S; ++k)
-            if (state[k] == ACTIVE && !release(k, false)) return false;
-    }
-    if (text) {   // the error word of the rounds' descriptors (never expected: the host validated every feed)
-        Q3T_HIP(hipMemcpyAsync(held_h, feed_.error, 4, hipMemcpyDeviceToHost, stream_));
-        Q3T_HIP(hipStreamSynchronize(stream_));
-        if (held_h[0]) {
-            Q3T_HIP(hipMemsetAsync(feed_.error, 0, 4, stream_));
-            set_error("generate_queue: a text feed named a row outside its buffers");
-            return false;
-        }
-    }
-    if (codes)
-        for (int u = 0; u < n_utt; ++u)
-            Q3T_HIP(hipMemcpyAsync(codes + (size_t)u * gp.max_len * NCB, out_dev + (size_t)u * gp.max_len * NCB,
-                                   (size_t)gp.max_len * NCB * 4, hipMemcpyDeviceToHost, stream_));
-    Q3T_HIP(hipStreamSynchronize(stream_));
-    if (persist_error()) { set_error("persistent kernel: an in-launch hand-off timed out"); *faulted = true; return false; }
-    return true;
-}
-
-bool Engine::generate_queue(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
-                            const GenParams &gp, int32_t *codes, int *n_frames, int max_active, QueueCb on_batch, void *user,
-                            int interval, const UttParams *up, const TextFeed *text) {
-    for (int u = 0; u < n_utt; ++u) n_frames[u] = 0;
-    if (!on_batch && !codes && n_utt > 0) { set_error("generate_queue: no codes buffer and no callback"); return false; }
-    if (on_batch && interval <= 0) { set_error("generate_queue: the delivery interval must be > 0"); return false; }
-    // text feeds only with an open utterance: a call without one is the queue as it was, launch for launch
-    int first_open = -1;
-    for (int u = n_utt - 1; text && text->open && u >= 0; --u)
-        if (text->open[u]) first_open = u;
-    if (text && text->held)
-        for (int u = 0; u < n_utt; ++u) text->held[u] = 0;
-    if (first_open < 0) text = nullptr;
-    if (text && !text->cb) { set_error("utterance " + std::to_string(first_open) + ": open without a text callback"); return false; }
-    if (text && interval <= 0) { set_error("generate_queue: text feeds need an interval > 0"); return false; }
-    TextLog tlog;
-    if (text) { tlog.ids.resize(n_utt); tlog.pieces.resize(n_utt); }
-    const int S = std::min(max_slots_, std::max(n_utt, 1));
-    DeviceLock lk(persist_exclusive(S), device_);
-    QueueState qst(std::max(n_utt, 0));
-    bool fault = false;
-    ScopeExit rec_off([&] { rec_on_ = false; });
-    if (generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, up, codes, n_frames, max_active, &fault, on_batch, user, interval, qst, text, &tlog))
-        return true;
-    if (!fault) return false;
-    // a single-slot persistent launch gave up on a hand-off: continue on the launch-per-op graphs, which are
-    // bit-identical, and re-run the queue (sampling is keyed by utterance, so the re-run gives the same codes; what
-    // was delivered, cancelled or finished before the fault is kept in qst and not delivered again)
-    if (!persist_recover()) return false;
-    return generate_queue_once(n_utt, tokens, n_tokens, speaker, gp, up, codes, n_frames, max_active, &fault, on_batch, user, interval, qst, text, &tlog);
 }
 
 bool Engine::time_stage(int stage, int S, int pos, int iters, double *ms) {

@@ -12,6 +12,7 @@
 #include "gguf.h"
 #include "kernels.h"
 #include "queue_deliver.h"
+#include "queue_sched.h"
 
 namespace q3t {
 
@@ -131,14 +132,6 @@ struct StackCache {
     float *part; unsigned *ticket;   // split attention: partials and arrival counters
 };
 
-// what the open utterances of a queue were fed (text feeds), kept across a fallback re-run: the re-run replays it
-// against the same `frames` schedule instead of asking the callback again
-struct TextLog {
-    struct Piece { int frames, n; bool end; };
-    std::vector<std::vector<int32_t>> ids;     // per utterance, every fed id
-    std::vector<std::vector<Piece>> pieces;    // per utterance: at `frames` generated frames, n ids (and the end)
-};
-
 class Engine {
 public:
     Engine();
@@ -177,12 +170,14 @@ public:
                   void *user = nullptr, int interval = 40, const UttParams *up = nullptr);
     // continuous batching: n_utt utterances (any number) through min(max_slots, n_utt) slots, at
     // most max_active of them at a time.  A slot whose utterance ended (EOS or max_len) is refilled with the next
-    // queued utterance between two frames: its text rows are projected, its prefill rows assembled and replayed
-    // token by token through a single-slot talker step on that slot's KV region while the other slots wait, and its
-    // state (position, frame, EOS, repetition set, codes) is reset.  Sampling streams are keyed by the utterance's
-    // index in the call (utt id), so an utterance's codes do not depend on its slot, its admission frame or the
-    // other utterances in flight (the S-slot decode step never mixes tokens); on the matrix-core path (>= 4 slots) the
-    // admission prefill runs the batch's kernels for its one slot, so the first wave's codes equal generate()'s.
+    // queued utterance between two frames.  The slots freed since the last admission are admitted together, on the
+    // admission stream while the other slots go on decoding: their text rows are projected, their prompt rows assembled
+    // and run through one causal prefill that writes K/V straight into the target slots; each slot then joins the
+    // frame loop on the main stream with its state (position, frame, EOS, repetition set, codes) reset.  Sampling
+    // streams are keyed by the utterance's index in the call (utt id), so an utterance's codes do not depend on its
+    // slot, its admission frame or the other utterances in flight (the S-slot decode step never mixes tokens); the
+    // admission prefill runs the running batch's kernels, whose per-row arithmetic does not depend on the other rows,
+    // so the first wave's codes equal generate()'s.
     // on_batch (q3t_queue_cb) with interval > 0: the queue hands frames out while it runs (DESIGN 2f "Queue
     // deliveries").  Every `interval` frames of the loop clock one collection launch gathers the new frames of all
     // active slots (a tick); when a slot's utterance ends, one more gathers the rest of the finished slots and is
@@ -281,11 +276,11 @@ private:
     bool generate_once(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                        const GenParams &gp, const UttParams *up, int32_t *codes, int *n_frames, FrameCb on_frames, void *user,
                        int interval, StreamState &st, bool *fault);
-    class QueueStreamer;   // the queue callback's collections and deliveries (engine.cpp)
-    bool generate_queue_once(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
-                             const GenParams &gp, const UttParams *up, int32_t *codes, int *n_frames, int max_active,
-                             bool *faulted, QueueCb on_batch, void *user, int interval, QueueState &qst,
-                             const TextFeed *text, TextLog *tlog);
+    class QueueStreamer;   // the queue callback's collections and deliveries (engine_queue.cpp)
+    class QueueLoop;       // one run of the queue: the scheduler objects of queue_sched.h and the HIP calls they ask for
+    // the records and prompt lengths of a call, validated: up's own, or (up null) the call-wide gp for every utterance
+    bool resolve_utt_params(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
+                            const GenParams &gp, const UttParams *up, std::vector<UttParams> &ups, std::vector<int> &plen);
     // host scratch kept across calls (a per-call hipFree / hipHostFree synchronises the whole device)
     struct PinnedChunk { size_t cap = 0; int32_t *codes = nullptr; hipEvent_t ev = nullptr; };
     std::vector<PinnedChunk> chunk_pool_;   // streaming chunks of generate() and of the queue's deliveries
@@ -293,8 +288,9 @@ private:
     void *pin_ = nullptr, *qout_ = nullptr, *qstage_ = nullptr;
     size_t pin_cap_ = 0, qout_cap_ = 0, qstage_cap_ = 0;
     bool ensure_pinned(size_t bytes);
-    bool ensure_qout(size_t bytes);
-    bool ensure_qstage(size_t bytes);   // the queue deliveries' device staging chunk [S][interval][16] + header [S] + error word
+    // device scratch p grown to bytes: qout_ (the queue's finished codes) and qstage_ (the queue deliveries' staging
+    // chunk [S][interval][16] + header [S] + error word)
+    bool ensure_device(void *&p, size_t &cap, size_t bytes);
     bool enqueue_talker_step(int S, hipStream_t s);
     bool enqueue_talker(int S, hipStream_t s, bool gather_input, bool select_next, bool prenormed = false,
                         bool *fold_advance = nullptr);
@@ -383,13 +379,14 @@ private:
         int *dev = nullptr, *error = nullptr;
         size_t cap_ints = 0;
         int cap_rows = 0, next = 0;
-        std::vector<int> ids, rows, commit, hold, rel;   // the round being built (reserved once)
+        TextRound round;   // the round being built (reserved once)
     } feed_;
     float *hold_save_ = nullptr;   // [max_slots][H]
     int *held_flag_ = nullptr;     // [max_slots] device: the slot is held (k_slot_hold)
     bool ensure_text_feed();
-    bool enqueue_text_round(int S, bool any_hold, bool any_rel);   // feed_'s round, on the main stream
-    bool drain_text_rounds();                       // wait for the rounds in flight; their times into text_stats
+    bool enqueue_text_round(int S);   // feed_'s round, on the main stream
+    bool retire_text_round(int b);    // ring blob b, if in use: wait for its round; its time into text_stats
+    bool drain_text_rounds();         // the same for every round in flight, oldest first
     hipStream_t astream_ = nullptr;
     int *delivered_ = nullptr, *qmask_ = nullptr;   // queue deliveries: per-slot frames collected so far; a collection's slot mask
     float *ahidden_ = nullptr, *alogits_ = nullptr;

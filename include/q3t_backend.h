@@ -216,6 +216,45 @@ int q3t_generate_queue_text(q3t_ctx *ctx, int n_utt, const int32_t *const *token
  * and the append / hold / release launches of one loop iteration) and their summed device time in ms */
 int q3t_text_feed_stats(const q3t_ctx *ctx, int32_t *graph_launches, int32_t *idle_rounds, int32_t *feed_rounds,
                         double *feed_ms);
+/* ---- the open queue: admit new utterances while continuous batching runs.  The utterances are not given up front:
+ * `arrive` is asked for them on the caller's thread, between two frames, at most once per iteration of the frame loop and
+ * only when no admission batch is in flight and room = min(free slots, max_active - busy slots) > 0.
+ *   next_id  the id of the first utterance it returns (arrival order, from 0 per call; the rest follow)
+ *   room     how many it may return: more is Q3T_ERR.  The engine keeps no backlog; a request that finds no room waits
+ *            with the caller
+ *   running  busy slots
+ *   idle     1 exactly when no slot is busy: the callback may block until a request exists.  With idle == 0 it must
+ *            return at once (the other utterances wait for it)
+ * It fills out[0 .. *n) and sets *closed != 0 when no more will arrive after these; the call returns when the source is
+ * closed and every accepted utterance has ended.  Return 0 to abort the call (Q3T_OK, as q3t_queue_cb).
+ * Deliveries keep the contract of q3t_generate_queue_stream with utt[i] = the arrival id: increasing ids within a
+ * callback, exactly one final delivery per utterance, a delivery that is neither an utterance's first nor its last has
+ * exactly `interval` frames, stop[i] cancels.  Both callbacks get the same `user`.
+ * An utterance that arrives with key k, record r, speaker s and tokens t gets, bit for bit and in length, the codes
+ * q3t_generate_queue_utt returns for index k of a call at the same slots, seed and p->max_len in which utterance k has
+ * (t, s, r): whenever it arrived, whatever else ran, whichever slot it took.
+ * slots (<= 0: the context's max_slots) is fixed for the call; p gives max_len and seed.  Each arrival is validated with
+ * the checks of q3t_generate_queue_utt (q3t_check_utt); an invalid one, or more than `room`, ends the call with Q3T_ERR
+ * and a message naming its id, after both streams are drained.  Ids are int32: the call ends with Q3T_ERR when they run
+ * out.  The host state is bounded by the slot count, not by the arrivals so far.
+ * Lock rule: the call holds the context's device lock (devlock.h) from start to end, also while an idle ask blocks; at
+ * slot counts that run persistent kernels that lock is exclusive, and other contexts on the device wait.
+ * n_arrived / n_finished (may be NULL): utterances accepted / ended by a final delivery or a cancel. */
+typedef struct q3t_arrival {
+    const int32_t *tokens; int32_t n_tokens;   /* read before the callback returns */
+    const float *speaker;                      /* hidden floats or NULL; read before the callback returns */
+    q3t_utt_params up;
+    uint64_t key;                              /* sampling key: (seed, key, frame, step) */
+} q3t_arrival;
+typedef int (*q3t_arrive_cb)(void *user, int32_t next_id, int32_t room, int32_t running, int32_t idle,
+                             q3t_arrival *out, int32_t *n, int32_t *closed);
+int q3t_generate_queue_open(q3t_ctx *ctx, const q3t_gen_params *p, int32_t slots, int32_t max_active,
+                            q3t_arrive_cb arrive, q3t_queue_cb cb, void *user, int32_t interval, int32_t *n_arrived,
+                            int32_t *n_finished);
+/* what q3t_generate_queue_open (and q3t_generate_queue_utt) would refuse of one utterance: Q3T_ERR with the message in
+ * q3t_last_error (it names utterance 0), Q3T_OK otherwise.  Nothing runs. */
+int q3t_check_utt(const q3t_ctx *ctx, const int32_t *tokens, int32_t n_tokens, const float *speaker,
+                  const q3t_gen_params *p, const q3t_utt_params *up);
 /* tuning knob (process-wide): batches of >= min_batch slots run the projections on the matrix cores (MFMA GEMM,
  * gemm_mfma.hip) instead of the weight-streaming GEMV; 0 disables the matrix-core path.  Default 4 (env
  * Q3T_MFMA_MIN_B).  Applies to graphs captured afterwards (create contexts after changing it). */

@@ -24,12 +24,24 @@
 //                        may come out of request order; each carries its output path.  Combines with --stream-full
 //                        (one vocoder stream per slot, a callback's frames pushed as one batch).  Takes precedence
 //                        over --batch
+//   --queue-open <n>     --serve runs an open queue of n slots (Qwen3TTS::serve_queue): a reader thread takes request
+//                        lines from stdin while the queue runs, and a request is admitted into a free slot as soon as
+//                        it is read instead of waiting for the queue to drain.  A request with a bad third field, or
+//                        one the engine would refuse, is answered with ERR alone and never enters the queue; each
+//                        reply is written when its request ends; "quit" or end of input closes the queue, which ends
+//                        when the requests read so far have.  --max-tokens is the cap of every request.  Takes
+//                        precedence over --queue and --batch
 #include <poll.h>
 #include <unistd.h>
 
+#include <condition_variable>
 #include <cstdio>
 #include <cstring>
+#include <deque>
+#include <map>
+#include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "qwen3_tts_pipeline.h"
@@ -61,6 +73,8 @@ void print_usage(const char *program) {
     fprintf(stderr, "  --batch <n>            Server mode: decode up to n queued requests together (default: 1)\n");
     fprintf(stderr, "  --queue <n>            Server mode: run the waiting requests (up to 8n) through n continuously batched\n");
     fprintf(stderr, "                         slots; a reply is written when its request ends (replies may be out of order)\n");
+    fprintf(stderr, "  --queue-open <n>       Server mode: an open queue of n slots; requests are read and admitted while the\n");
+    fprintf(stderr, "                         others run (--max-tokens caps every request)\n");
     fprintf(stderr, "  -h, --help             Show this help\n");
     fprintf(stderr, "\n");
     fprintf(stderr, "Example:\n");
@@ -261,12 +275,99 @@ int run_server(qwen3_tts::Qwen3TTS &tts, const std::vector<float> &speaker_embd,
     return 0;
 }
 
+// --serve --queue-open: the reader thread turns stdin lines into requests (or ERR replies) while the main thread runs
+// the open queue, which asks for them between two frames
+int run_server_open(qwen3_tts::Qwen3TTS &tts, const std::vector<float> &speaker_embd, const std::string &reference_audio,
+                    const qwen3_tts::tts_params &params) {
+    struct Item { qwen3_tts::tts_request t; std::string output; };
+    std::mutex mu, out_mu;   // the request queue; stdout
+    std::condition_variable cv;
+    std::deque<Item> waiting;
+    bool eof = false;
+    fprintf(stderr, "\nServer ready. Send: text<TAB>output.wav  (or 'quit' to exit)\n");
+    fflush(stderr);
+    auto refuse = [&](const std::string &why) {
+        std::lock_guard<std::mutex> lk(out_mu);
+        fprintf(stdout, "ERR\t%s\n", why.c_str());
+        fflush(stdout);
+    };
+    std::thread reader([&] {
+        bool quit = false;
+        Request q;
+        while (read_request(q, quit)) {
+            if (!q.error.empty()) { refuse(q.error); q = Request(); continue; }
+            Item it;
+            it.output = q.output;
+            qwen3_tts::tts_request &t = it.t;
+            t.text = q.text;
+            t.params = params;
+            t.speaker_embedding = speaker_embd;
+            if (q.has_language) t.language_id = q.language_id;
+            if (q.has_temperature) t.params.temperature = q.temperature;
+            if (q.has_top_k) t.params.top_k = q.top_k;
+            if (q.has_repetition_penalty) t.params.repetition_penalty = q.repetition_penalty;
+            if (q.has_max_tokens) t.params.max_audio_tokens = q.max_tokens;
+            std::string why;
+            if (q.has_speaker) {
+                t.speaker_embedding = load_embedding(q.speaker);
+                if (t.speaker_embedding.empty()) why = "cannot read speaker embedding " + q.speaker;
+            } else if (speaker_embd.empty() && !reference_audio.empty()) {
+                why = "the open queue needs the server's voice as an embedding (-e), or speaker=<file>";
+            }
+            if (why.empty()) tts.check_request(t, why);
+            if (!why.empty()) { refuse(why); q = Request(); continue; }
+            fprintf(stderr, "Synthesizing: \"%s\" -> %s\n", q.text.c_str(), q.output.c_str());
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                waiting.push_back(std::move(it));
+            }
+            cv.notify_one();
+            q = Request();
+        }
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            eof = true;
+        }
+        cv.notify_one();
+    });
+    std::map<int32_t, std::string> outputs;   // by request number, until its reply
+    int32_t handed = 0;
+    const bool ok = tts.serve_queue(
+        [&](std::vector<qwen3_tts::tts_request> &out, int32_t room, bool may_block) {
+            std::unique_lock<std::mutex> lk(mu);
+            if (may_block) cv.wait(lk, [&] { return !waiting.empty() || eof; });
+            while (room-- > 0 && !waiting.empty()) {
+                outputs[handed++] = waiting.front().output;
+                out.push_back(std::move(waiting.front().t));
+                waiting.pop_front();
+            }
+            return !(eof && waiting.empty());
+        },
+        [&](int32_t number, const qwen3_tts::tts_result &r) {
+            Request q;
+            q.output = outputs[number];
+            outputs.erase(number);
+            std::lock_guard<std::mutex> lk(out_mu);
+            reply(r, q);
+        },
+        params.max_audio_tokens);
+    if (!ok) {
+        // an engine error ended the queue: the reader may sit in a read, so the process ends here
+        fprintf(stderr, "Error: %s\n", tts.get_error().c_str());
+        fflush(stdout);
+        _exit(1);
+    }
+    reader.join();
+    fprintf(stderr, "Server shutting down.\n");
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     std::string model_dir, text, output_file = "output.wav", reference_audio, embedding_file;
     bool serve_mode = false;
-    int device = 0, batch = 1, queue = 0, vocoder_chunk = -1, stream_full = 0;
+    int device = 0, batch = 1, queue = 0, queue_open = 0, vocoder_chunk = -1, stream_full = 0;
     unsigned long long seed = 0;
     qwen3_tts::tts_params params;
     auto need = [&](int &i, const char *what) -> const char * {
@@ -298,6 +399,7 @@ int main(int argc, char **argv) {
             else if (arg == "--stream-full") { if (!(v = need(i, "stream-full interval"))) return 1; stream_full = std::stoi(v); }
             else if (arg == "--vocoder-chunk") { if (!(v = need(i, "vocoder-chunk value"))) return 1; vocoder_chunk = std::stoi(v); }
             else if (arg == "--batch") { if (!(v = need(i, "batch value"))) return 1; batch = std::max(1, std::stoi(v)); }
+            else if (arg == "--queue-open") { if (!(v = need(i, "queue-open value"))) return 1; queue_open = std::max(1, std::stoi(v)); }
             else if (arg == "--queue") { if (!(v = need(i, "queue value"))) return 1; queue = std::max(1, std::stoi(v)); }
             else {
                 fprintf(stderr, "Error: unknown argument: %s\n", arg.c_str());
@@ -325,6 +427,7 @@ int main(int argc, char **argv) {
     if (vocoder_chunk >= 0) tts.set_vocoder_chunk(vocoder_chunk);
     if (stream_full > 0) tts.set_stream_full(stream_full);
     if (queue > 0) tts.set_queue_slots(queue);
+    if (queue_open > 0) tts.set_queue_slots(queue_open);
     fprintf(stderr, "Loading models from: %s\n", model_dir.c_str());
     if (!tts.load_models(model_dir)) {
         fprintf(stderr, "Error: %s\n", tts.get_error().c_str());
@@ -334,6 +437,7 @@ int main(int argc, char **argv) {
     std::vector<float> speaker_embd;
     if (embedding_file.empty() && !reference_audio.empty()) embedding_file = reference_audio + ".embd";
     if (!embedding_file.empty() && !resolve_embedding(tts, embedding_file, reference_audio, speaker_embd)) return 1;
+    if (serve_mode && queue_open > 0) return run_server_open(tts, speaker_embd, reference_audio, params);
     if (serve_mode) return run_server(tts, speaker_embd, reference_audio, params, batch, queue);
     fprintf(stderr, "Synthesizing: \"%s\"\n", text.c_str());
     if (!reference_audio.empty() && speaker_embd.empty()) fprintf(stderr, "Reference audio: %s\n", reference_audio.c_str());

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 
 #include "q3t_backend.h"
 #include "qwen3_tts_pipeline.h"
@@ -348,6 +349,194 @@ struct QueueSynthState {
 int queue_synth_cb(void *user, int32_t n, const int32_t *utt, const int32_t *const *codes, const int32_t *n_frames,
                    const int32_t *final, int32_t * /*stop*/) {
     return static_cast<QueueSynthState *>(user)->deliver(n, utt, codes, n_frames, final) ? 1 : 0;
+}
+
+// serve_queue(): the open queue's two callbacks.  Requests are numbered as the caller hands them over; the ones the
+// engine accepts also get its arrival id, under which their deliveries come.  Only the running utterances are kept
+// (`live`): the state does not grow with the requests served.  The vocoder handling is QueueSynthState's.
+struct OpenQueueState {
+    q3t_ctx *ctx = nullptr;
+    bool stream_full = false;
+    int32_t vocoder_chunk = 0, max_len = 0, hidden = 0;
+    q3t_gen_params p{};
+    const TextTokenizer *tokenizer = nullptr;
+    const std::function<bool(std::vector<tts_request> &, int32_t, bool)> *next_request = nullptr;
+    const std::function<void(int32_t, const tts_result &)> *on_result = nullptr;
+    struct Live {
+        int32_t request = 0;              // the caller's number
+        int32_t n_frames = 0;
+        double decode_ms = 0;
+        int64_t t0 = 0;
+        tts_result r;
+        std::vector<int32_t> codes;       // (no stream interval)
+        q3t_voc_stream *vs = nullptr;
+    };
+    std::map<int32_t, Live> live;         // by arrival id
+    std::vector<q3t_voc_stream *> pool, free_list;
+    std::vector<std::vector<int32_t>> toks;   // what the last answer points into: alive until the next ask
+    std::vector<std::vector<float>> spk;
+    std::vector<float> zero;
+    int32_t next_request_no = 0;
+    std::string error_msg;
+
+    ~OpenQueueState() {
+        for (q3t_voc_stream *v : pool) q3t_vocoder_stream_close(v);
+    }
+    void report(Live &l, bool ok, const std::string &msg) {
+        tts_result &r = l.r;
+        r.success = ok;
+        r.error_msg = msg;
+        if (!ok) r.audio.clear();
+        r.sample_rate = kSampleRate;
+        r.t_total_ms = now_ms() - l.t0;
+        r.t_decode_ms = (int64_t)(l.decode_ms + 0.5);
+        r.t_generate_ms = std::max<int64_t>(r.t_total_ms - r.t_decode_ms, 0);
+        if (on_result && *on_result) (*on_result)(l.request, r);
+    }
+    void refuse(int32_t request, const std::string &msg) {   // a request that never enters the queue
+        Live l;
+        l.request = request;
+        l.t0 = now_ms();
+        report(l, false, msg);
+    }
+    bool open_pool(int32_t slots) {
+        for (int32_t i = 0; i < slots; ++i) {
+            q3t_voc_stream *v = nullptr;
+            if (q3t_vocoder_stream_open(ctx, max_len, &v) != Q3T_OK) return false;
+            pool.push_back(v);
+            free_list.push_back(v);
+        }
+        return true;
+    }
+    int arrive(int32_t next_id, int32_t room, int32_t idle, q3t_arrival *out, int32_t *n, int32_t *closed) {
+        std::vector<tts_request> reqs;
+        const bool more = (*next_request)(reqs, room, idle != 0);
+        toks.clear();
+        spk.clear();
+        int32_t m = 0;
+        for (const tts_request &r : reqs) {
+            const int32_t no = next_request_no++;
+            if (m >= room) { refuse(no, "more requests than the queue has room for"); continue; }
+            if (!r.speaker_embedding.empty() && (int32_t)r.speaker_embedding.size() != hidden) {
+                refuse(no, "a speaker embedding must be empty or hold one value per hidden channel");
+                continue;
+            }
+            const int64_t t = now_ms();
+            std::vector<int32_t> ids = tokenizer->encode_for_tts(r.text);
+            const int64_t t_tok = now_ms() - t;
+            if (ids.empty()) { refuse(no, "Failed to tokenize text"); continue; }
+            q3t_arrival &a = out[m];
+            a.up.language_id = r.language_id;
+            a.up.max_len = std::max(r.params.max_audio_tokens, 1);
+            a.up.repetition_penalty = r.params.repetition_penalty;
+            a.up.temperature = r.params.temperature;
+            a.up.top_k = r.params.top_k;
+            a.up.force_frames = 0;
+            const float *s = r.speaker_embedding.empty() ? zero.data() : r.speaker_embedding.data();
+            // what the engine would refuse fails this request alone (an invalid arrival would end the whole call)
+            if (q3t_check_utt(ctx, ids.data(), (int32_t)ids.size(), s, &p, &a.up) != Q3T_OK) { refuse(no, q3t_error()); continue; }
+            toks.push_back(std::move(ids));
+            spk.emplace_back(s, s + hidden);
+            a.key = (uint64_t)(next_id + m);
+            Live &l = live[next_id + m];
+            l.request = no;
+            l.t0 = now_ms();
+            l.r.t_tokenize_ms = t_tok;
+            ++m;
+        }
+        for (int32_t i = 0; i < m; ++i) {   // (the vectors have stopped moving)
+            out[i].tokens = toks[i].data();
+            out[i].n_tokens = (int32_t)toks[i].size();
+            out[i].speaker = spk[i].data();
+        }
+        *n = m;
+        *closed = more ? 0 : 1;
+        return 1;
+    }
+    bool decode_whole(Live &l) {
+        tts_result &r = l.r;
+        int64_t got = 0;
+        int rc;
+        if (vocoder_chunk > 0) {
+            r.audio.resize((size_t)l.n_frames * 1920);
+            rc = q3t_vocoder_decode_chunked(ctx, l.codes.data(), l.n_frames, 16, vocoder_chunk, r.audio.data(), &got);
+        } else {
+            r.audio.resize((size_t)std::max<int64_t>(q3t_vocoder_num_samples(ctx, l.n_frames, Q3T_VOCODER_FULL), 0));
+            rc = q3t_vocoder_decode(ctx, l.codes.data(), l.n_frames, Q3T_VOCODER_FULL, r.audio.data(), &got);
+        }
+        if (rc != Q3T_OK) return false;
+        r.audio.resize((size_t)got);
+        return true;
+    }
+    // one delivery callback (QueueSynthState::deliver over the live table): false aborts the queue (error_msg set)
+    bool deliver(int32_t n, const int32_t *utt, const int32_t *const *cp, const int32_t *nf, const int32_t *fin) {
+        const int64_t td = now_ms();
+        std::vector<q3t_voc_stream *> st;
+        std::vector<const int32_t *> pc;
+        std::vector<int32_t> pn;
+        std::vector<Live *> pl;
+        std::vector<float *> pp;
+        std::vector<int64_t> cap;
+        std::vector<size_t> at;
+        for (int32_t i = 0; i < n; ++i) {
+            auto it = live.find(utt[i]);
+            if (it == live.end()) { error_msg = "unexpected delivery from the queue"; return false; }
+            Live &l = it->second;
+            if (nf[i] <= 0) continue;
+            l.n_frames += nf[i];
+            if (!stream_full) { l.codes.insert(l.codes.end(), cp[i], cp[i] + (size_t)nf[i] * 16); continue; }
+            if (!l.vs) {
+                if (free_list.empty()) { error_msg = "more utterances in flight than vocoder streams in the pool"; return false; }
+                l.vs = free_list.back();
+                free_list.pop_back();
+                if (q3t_vocoder_stream_reset(l.vs) != Q3T_OK) { error_msg = "Failed to reset the vocoder stream: " + q3t_error(); return false; }
+            }
+            const int64_t total = q3t_vocoder_num_samples(ctx, q3t_vocoder_stream_frames(l.vs) + nf[i], Q3T_VOCODER_FULL);
+            const int64_t c = total - q3t_vocoder_stream_samples(l.vs);
+            if (total < 0 || c < 0) { error_msg = "bad sample count of a vocoder stream"; return false; }
+            std::vector<float> &a = l.r.audio;
+            at.push_back(a.size());
+            a.resize(a.size() + (size_t)c);
+            st.push_back(l.vs); pc.push_back(cp[i]); pn.push_back(nf[i]); pl.push_back(&l); cap.push_back(c);
+            pp.push_back(a.data() + at.back());
+        }
+        if (!st.empty()) {
+            std::vector<int64_t> got(st.size(), 0);
+            const int rc = q3t_vocoder_stream_push_batch(st.data(), (int32_t)st.size(), pc.data(), pn.data(), pp.data(),
+                                                         cap.data(), got.data());
+            for (size_t j = 0; j < st.size(); ++j) pl[j]->r.audio.resize(at[j] + (size_t)(rc == Q3T_OK ? got[j] : 0));
+            if (rc != Q3T_OK) { error_msg = "Vocoder stream decode failed: " + q3t_error(); return false; }
+        }
+        const double push_ms = (double)(now_ms() - td);
+        int64_t pushed = 0;
+        for (int32_t f : pn) pushed += f;
+        for (size_t j = 0; j < pl.size(); ++j) pl[j]->decode_ms += push_ms * pn[j] / (double)pushed;
+        for (int32_t i = 0; i < n; ++i) {
+            if (!fin[i]) continue;
+            auto it = live.find(utt[i]);
+            Live &l = it->second;
+            if (l.vs) { free_list.push_back(l.vs); l.vs = nullptr; }
+            if (l.n_frames == 0) report(l, false, "No speech codes generated");
+            else if (stream_full) report(l, true, "");
+            else {
+                const int64_t t = now_ms();
+                const bool ok = decode_whole(l);
+                l.decode_ms += (double)(now_ms() - t);
+                report(l, ok, ok ? "" : "Failed to decode speech codes: " + q3t_error());
+            }
+            live.erase(it);
+        }
+        return true;
+    }
+};
+
+int open_queue_arrive(void *user, int32_t next_id, int32_t room, int32_t /*running*/, int32_t idle, q3t_arrival *out,
+                      int32_t *n, int32_t *closed) {
+    return static_cast<OpenQueueState *>(user)->arrive(next_id, room, idle, out, n, closed);
+}
+int open_queue_cb(void *user, int32_t n, const int32_t *utt, const int32_t *const *codes, const int32_t *n_frames,
+                  const int32_t *final, int32_t * /*stop*/) {
+    return static_cast<OpenQueueState *>(user)->deliver(n, utt, codes, n_frames, final) ? 1 : 0;
 }
 
 }  // namespace
@@ -809,6 +998,38 @@ std::vector<tts_result> Qwen3TTS::queue_requests(const std::vector<tts_request> 
     if (rc != Q3T_OK) return fail_rest("Failed to generate speech codes: " + q3t_error());
     if (!qs.error_msg.empty()) return fail_rest(qs.error_msg);
     return fail_rest("the queue ended without the utterance's final delivery");   // none is left after a clean run
+}
+
+// The open queue: requests are admitted while the others run (q3t_generate_queue_open)
+bool Qwen3TTS::serve_queue(const std::function<bool(std::vector<tts_request> &, int32_t, bool)> &next_request,
+                           const std::function<void(int32_t, const tts_result &)> &on_result, int32_t max_audio_tokens) {
+    if (!models_loaded_) { error_msg_ = "Models not loaded"; return false; }
+    if (!next_request) { error_msg_ = "serve_queue: no request source"; return false; }
+    const int32_t slots = std::max(queue_slots_, 1), max_len = std::max(max_audio_tokens, 1);
+    if (!ensure_slots(slots, max_len)) return false;
+    OpenQueueState qs;
+    qs.ctx = ctx_;
+    qs.stream_full = stream_full_ > 0 && vocoder_chunk_ <= 0;
+    qs.vocoder_chunk = vocoder_chunk_;
+    qs.max_len = max_len;
+    qs.hidden = hidden_;
+    qs.tokenizer = &tokenizer_;
+    qs.next_request = &next_request;
+    qs.on_result = &on_result;
+    qs.zero.assign(hidden_, 0.0f);   // no embedding: a zero speaker row, as in every call of this pipeline
+    q3t_default_params(&qs.p);
+    qs.p.seed = seed_;
+    qs.p.max_len = max_len;
+    if (qs.stream_full && !qs.open_pool(slots)) { error_msg_ = "Failed to open the vocoder stream: " + q3t_error(); return false; }
+    // (the context may hold more slots than this queue uses: it only grows)
+    const int rc = q3t_generate_queue_open(ctx_, &qs.p, slots, slots, open_queue_arrive, open_queue_cb, &qs,
+                                           qs.stream_full ? stream_full_ : kQueueTick, nullptr, nullptr);
+    const std::string why = rc != Q3T_OK ? "Failed to generate speech codes: " + q3t_error()
+                            : !qs.error_msg.empty() ? qs.error_msg : "the queue ended without the utterance's final delivery";
+    for (auto &kv : qs.live) qs.report(kv.second, false, why);   // none is left after a clean run
+    if (rc == Q3T_OK && qs.error_msg.empty()) return true;
+    error_msg_ = why;
+    return false;
 }
 
 // ======================================================================================================= audio

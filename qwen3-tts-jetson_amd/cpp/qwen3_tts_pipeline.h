@@ -121,6 +121,21 @@ public:
     std::vector<tts_result> synthesize_queue(const std::vector<tts_request> &requests,
                                              const std::function<void(int32_t, const tts_result &)> &on_result = nullptr);
 
+    // The open queue (q3t_generate_queue_open): requests are taken while the others run, so one that arrives a frame
+    // after the call began is admitted into a free slot at once instead of waiting for the queue to drain.
+    // next_request(out, room, may_block) is asked between two frames whenever a slot could take a newcomer: it appends
+    // at most `room` requests to `out` and returns false when no more will come (the call returns when the accepted
+    // ones have ended).  It must return at once unless may_block is true (nothing runs: it may wait for a request).
+    // Requests are numbered from 0 in the order they are handed over; on_result(number, result) fires at a request's
+    // final delivery, or at once, alone, for one that is refused (the checks of check_request and of the engine, a text
+    // that does not tokenize, more max_audio_tokens than the call's).  max_audio_tokens is the cap of every request of
+    // the call: the context is sized once, before the first request.  Slots, vocoder handling and timings are
+    // synthesize_queue's; a request's codes are those synthesize_queue gives it at the index it has among the accepted
+    // requests.  The device lock of the context is held for the whole call, also while next_request blocks.  False with
+    // get_error(): an engine error ended the call (every running request got the message).
+    bool serve_queue(const std::function<bool(std::vector<tts_request> &, int32_t, bool)> &next_request,
+                     const std::function<void(int32_t, const tts_result &)> &on_result, int32_t max_audio_tokens = 4096);
+
 private:
     tts_result synthesize_internal(const std::string &text, const float *speaker_embedding, const tts_params &params,
                                    tts_result &result);

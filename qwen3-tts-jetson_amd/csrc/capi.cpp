@@ -292,6 +292,67 @@ int q3t_generate_queue_text(q3t_ctx *ctx, int n_utt, const int32_t *const *token
     GUARD_END
 }
 
+namespace {
+// the C callback pair of q3t_generate_queue_open behind the engine's: both get the caller's `user`
+struct OpenQueueUser {
+    q3t_arrive_cb arrive;
+    q3t_queue_cb cb;
+    void *user;
+    std::vector<q3t_arrival> buf;
+};
+int open_arrive(void *u, int32_t next_id, int32_t room, int32_t running, int32_t idle, q3t::Arrival *out, int32_t *n,
+                int32_t *closed) {
+    OpenQueueUser &q = *static_cast<OpenQueueUser *>(u);
+    q.buf.assign((size_t)std::max(room, 0), q3t_arrival{});
+    if (!q.arrive(q.user, next_id, room, running, idle, q.buf.data(), n, closed)) return 0;
+    for (int i = 0; i < *n && i < room; ++i) {   // (more than room: refused by the planner, which reads none)
+        out[i].tokens = q.buf[i].tokens;
+        out[i].n_tokens = q.buf[i].n_tokens;
+        out[i].speaker = q.buf[i].speaker;
+        out[i].up = to_up(&q.buf[i].up, 1)[0];
+        out[i].key = q.buf[i].key;
+    }
+    return 1;
+}
+int open_deliver(void *u, int32_t n, const int32_t *utt, const int32_t *const *codes, const int32_t *n_frames,
+                 const int32_t *final, int32_t *stop) {
+    OpenQueueUser &q = *static_cast<OpenQueueUser *>(u);
+    return q.cb(q.user, n, utt, codes, n_frames, final, stop);
+}
+}  // namespace
+
+int q3t_generate_queue_open(q3t_ctx *ctx, const q3t_gen_params *p, int32_t slots, int32_t max_active, q3t_arrive_cb arrive,
+                            q3t_queue_cb cb, void *user, int32_t interval, int32_t *n_arrived, int32_t *n_finished) {
+    GUARD_BEGIN
+    if (n_arrived) *n_arrived = 0;
+    if (n_finished) *n_finished = 0;
+    CHECK_CTX(ctx);
+    CHECK_TALKER(ctx);
+    if (!arrive || !cb) { q3t::set_error("q3t_generate_queue_open: null callback"); return Q3T_ERR; }
+    if (interval <= 0) { q3t::set_error("q3t_generate_queue_open: interval must be > 0"); return Q3T_ERR; }
+    OpenQueueUser q{arrive, cb, user, {}};
+    return ctx->engine.generate_queue_open(to_gp(p), slots, max_active, open_arrive, open_deliver, &q, interval, n_arrived,
+                                           n_finished) ? Q3T_OK : Q3T_ERR;
+    GUARD_END
+}
+
+int q3t_check_utt(const q3t_ctx *ctx, const int32_t *tokens, int32_t n_tokens, const float *speaker, const q3t_gen_params *p,
+                  const q3t_utt_params *up) {
+    GUARD_BEGIN
+    CHECK_CTX(ctx);
+    CHECK_TALKER(ctx);
+    if (!up) { q3t::set_error("null argument"); return Q3T_ERR; }
+    q3t::Arrival a;
+    a.tokens = tokens; a.n_tokens = n_tokens; a.speaker = speaker;
+    a.up = to_up(up, 1)[0];
+    q3t::UttParams r;
+    int plen = 0;
+    const std::string err = const_cast<q3t_ctx *>(ctx)->engine.check_arrival(0, a, to_gp(p), &r, &plen);
+    if (!err.empty()) { q3t::set_error(err); return Q3T_ERR; }
+    return Q3T_OK;
+    GUARD_END
+}
+
 int q3t_text_feed_stats(const q3t_ctx *ctx, int32_t *graph_launches, int32_t *idle_rounds, int32_t *feed_rounds,
                         double *feed_ms) {
     CHECK_CTX(ctx);

@@ -1668,12 +1668,13 @@ bool Engine::check_gen_args(int n_utt, const int32_t *const *tokens, const int *
 }
 
 bool Engine::check_utt_args(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
-                            const GenParams &gp, const UttParams *up, std::vector<UttParams> &ups, std::vector<int> &plen) {
+                            const GenParams &gp, const UttParams *up, std::vector<UttParams> &ups, std::vector<int> &plen,
+                            int id0) {
     ups.assign(up, up + n_utt);
     plen.assign(n_utt, 0);
     for (int u = 0; u < n_utt; ++u) {
         UttParams &r = ups[u];
-        const std::string who = "utterance " + std::to_string(u) + ": ";
+        const std::string who = "utterance " + std::to_string(id0 + u) + ": ";
         if (r.max_len <= 0) r.max_len = gp.max_len;
         if (r.language_id >= c_.codec_vocab) { set_error(who + "language id out of range"); return false; }
         if (r.max_len > gp.max_len) { set_error(who + "max_len exceeds the call's max_len"); return false; }
@@ -1696,6 +1697,23 @@ bool Engine::resolve_utt_params(int n_utt, const int32_t *const *tokens, const i
     ups.assign(n_utt, UttParams{gp.language_id, gp.max_len, gp.rep_penalty, gp.temperature, gp.top_k, gp.force_frames});
     plen.assign(n_utt, plen0);
     return true;
+}
+
+std::string Engine::check_arrival(int32_t id, const Arrival &a, const GenParams &gp, UttParams *up, int *plen) {
+    const std::string who = "utterance " + std::to_string(id) + ": ";
+    if (a.n_tokens < 0 || !a.tokens) return who + "no prompt";
+    std::vector<UttParams> ups;
+    std::vector<int> pl;
+    const int32_t *tok = a.tokens;
+    const int n_tok = a.n_tokens;
+    const float *spk = a.speaker;
+    if (!check_utt_args(1, &tok, &n_tok, &spk, gp, &a.up, ups, pl, id)) {
+        const std::string &m = last_error();   // (the prompt checks do not name the utterance)
+        return m.compare(0, 10, "utterance ") == 0 ? m : who + m;
+    }
+    *up = ups[0];
+    *plen = pl[0];
+    return std::string();
 }
 
 void Engine::set_gen_params(const GenParams &gp) {

@@ -40,15 +40,7 @@ struct GenParams {
     int force_frames = 0;      // bench: mask EOS until this many frames are produced
 };
 
-// one utterance's own values (q3t_utt_params): what GenParams holds for the whole call, except the seed
-struct UttParams {
-    int language_id = 2050;    // < 0: the nothink prompt (one row shorter)
-    int max_len = 0;           // 1 .. GenParams::max_len
-    float rep_penalty = 1.05f;
-    float temperature = 0.9f;
-    int top_k = 50;
-    int force_frames = 0;
-};
+// (UttParams, one utterance's own values, is queue_sched.h's: the arrival log keeps a copy per utterance)
 
 struct DevLayer {
     uint16_t *qkv = nullptr, *o = nullptr, *gu = nullptr, *down = nullptr;
@@ -203,6 +195,19 @@ public:
     bool generate_queue(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                         const GenParams &gp, int32_t *codes, int *n_frames, int max_active, QueueCb on_batch = nullptr,
                         void *user = nullptr, int interval = 0, const UttParams *up = nullptr, const TextFeed *text = nullptr);
+    // the open queue (q3t_generate_queue_open; DESIGN 2f "Arrivals"): the utterances come from `arrive`, asked on the
+    // caller's thread between two frames under the rules of queue_sched.h's ArrivalPlanner, and leave through on_batch
+    // (required, interval > 0) under the delivery contract above with utt[i] = the arrival id.  slots (<= 0: max_slots) is
+    // fixed for the call: it chooses the kernel family.  Every utterance runs with its own record (the records path) and
+    // the ragged prefill, its sampling keyed by its arrival's key: its codes are those of index `key` of a closed call
+    // with records at the same slots, seed and gp.max_len.  The device lock is held for the whole call, also while an
+    // idle ask blocks.  gp gives max_len and the seed.
+    typedef ArrivalPlanner::AskFn ArriveCb;
+    bool generate_queue_open(const GenParams &gp, int slots, int max_active, ArriveCb arrive, QueueCb on_batch, void *user,
+                             int interval, int32_t *n_arrived, int32_t *n_finished);
+    // what the open queue would refuse of one utterance (q3t_check_utt): the message, or empty.  id: the utterance the
+    // message names; *up: the record with max_len resolved, *plen: its prompt rows
+    std::string check_arrival(int32_t id, const Arrival &a, const GenParams &gp, UttParams *up, int *plen);
     // counters of the last generate_queue with text feeds (q3t_text_feed_stats): frame graphs launched, loop rounds that
     // launched none because every busy slot was held, feed rounds (one copy + projection + k_text_append / hold /
     // release launches each) and the device time of those rounds (an event pair around each)
@@ -331,9 +336,10 @@ private:
     bool check_gen_args(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
                         const GenParams &gp, int *plen);
     // the same with a record per utterance: every record is validated before anything runs; ups: the records with
-    // max_len resolved, plen: per utterance
+    // max_len resolved, plen: per utterance; id0: the id the messages give utterance 0 (an arrival's)
     bool check_utt_args(int n_utt, const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,
-                        const GenParams &gp, const UttParams *up, std::vector<UttParams> &ups, std::vector<int> &plen);
+                        const GenParams &gp, const UttParams *up, std::vector<UttParams> &ups, std::vector<int> &plen,
+                        int id0 = 0);
     void set_gen_params(const GenParams &gp);   // gp_ = gp; drops the frame graphs that baked other sampling values
     // per-utterance sampling: the [max_slots] records the batched selections read while rec_on_ (select_spec); a one-slot
     // run leaves it off and bakes its utterance's values into the scalars (set_gen_params)

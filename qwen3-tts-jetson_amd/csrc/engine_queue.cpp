@@ -108,10 +108,18 @@ bool Engine::activate_slot(int k, uint64_t utt, int trailing_len, int n_tok, con
 class Engine::QueueStreamer {
 public:
     // own_max_len: a collection clamps each slot's frames to its own max_len (slot_max_len_) as well
+    // alog (the open queue): the utterance indices are handles of the arrival log, and the callback is given their ids
     QueueStreamer(Engine &e, int S, int n_utt, int max_len, bool own_max_len, QueueCb cb, void *user, int interval,
-                  QueueState &st, bool *fault)
+                  QueueState &st, bool *fault, const ArrivalLog *alog = nullptr)
         : e_(e), S_(S), max_len_(max_len), interval_(interval), own_max_len_(own_max_len), cb_(cb), user_(user), st_(st),
-          fault_(fault), run_(n_utt) {}
+          fault_(fault), alog_(alog), run_(n_utt) {}
+    // the open queue: the per-utterance tables have n rows now; the chunks collected / delivered so far (a handle is
+    // reused only when no pending chunk can name it: retire_arrivals)
+    void grow(size_t n) { run_.run.resize(n, 0); run_.gone.resize(n, 0); }
+    QueueRun &run() { return run_; }
+    bool pending() const { return !pend_.empty(); }
+    size_t collected() const { return n_collected_; }
+    size_t delivered() const { return n_delivered_; }
     bool active() const { return cb_ != nullptr; }
     int interval() const { return interval_; }
     bool begin() {   // the staging chunk with a clear error word
@@ -152,6 +160,7 @@ public:
         Q3T_HIP(hipMemcpyAsync(c.rows, stage, stage_ints() * 4, hipMemcpyDeviceToHost, e_.stream_));
         Q3T_HIP(hipEventRecord(c.ev, e_.stream_));
         pend_.push_back(c);
+        ++n_collected_;
         return true;
     }
     // the pending chunks up to the last one due at loop clock f, oldest first
@@ -163,6 +172,7 @@ public:
             Chunk c = pend_.front();
             pend_.erase(pend_.begin());
             pool_.push_back(c);
+            ++n_delivered_;
             if (!deliver(c)) { hipStreamSynchronize(e_.stream_); return false; }
         }
         return true;
@@ -184,11 +194,13 @@ private:
         std::vector<QueueEntry> ent;
         queue_plan(hdr, c.utt, c.final, st_, run_, ent, stops_);
         if (ent.empty()) return true;
+        if (alog_)   // handles are reused: increasing id is not increasing handle
+            std::sort(ent.begin(), ent.end(), [this](const QueueEntry &a, const QueueEntry &b) { return alog_->e[a.utt].id < alog_->e[b.utt].id; });
         const size_t m = ent.size();
         std::vector<int32_t> utt(m), nf(m), fin(m), stop(m, 0);
         std::vector<const int32_t *> cp(m);
         for (size_t i = 0; i < m; ++i) {
-            utt[i] = ent[i].utt; nf[i] = ent[i].n; fin[i] = ent[i].final;
+            utt[i] = alog_ ? alog_->e[ent[i].utt].id : ent[i].utt; nf[i] = ent[i].n; fin[i] = ent[i].final;
             cp[i] = c.rows + ((size_t)ent[i].slot * interval_ + ent[i].skip) * NCB;
         }
         const int go = cb_(user_, (int32_t)m, utt.data(), cp.data(), nf.data(), fin.data(), stop.data());
@@ -202,6 +214,8 @@ private:
     void *const user_;
     QueueState &st_;
     bool *const fault_;
+    const ArrivalLog *const alog_;
+    size_t n_collected_ = 0, n_delivered_ = 0;
     QueueRun run_;                    // this run's per-utterance progress (queue_deliver.h)
     std::vector<int> stops_;          // utterances to cancel: their slots may still be running
     size_t next_chunk_ = 0;           // chunk_pool_[0, next_chunk_) are in use by this call
@@ -298,7 +312,16 @@ public:
           gp_(gp), up_(up), codes_(codes), n_frames_(n_frames), qst_(qst), text_(text), tlog_(tlog), dev_hold_(text && S_ > 1),
           qs_(e, S_, n_utt, gp.max_len, up != nullptr, on_batch, user, interval, qst, &fault_), t_(S_), tp_(n_utt), sel_(S_, 0),
           g1_(gp) {}
+    // the open form (generate_queue_open): S slots whatever arrives, the records path, the ragged prefill
+    QueueLoop(Engine &e, const GenParams &gp, int S, int max_active, ArriveCb arrive, QueueCb on_batch, void *user, int interval,
+              QueueState &qst, ArrivalLog *alog)
+        : e_(e), n_utt_(0), S_(S), max_active_(max_active <= 0 || max_active > S ? S : max_active), interval_(interval),
+          tokens_in_(nullptr), n_tokens_in_(nullptr), tokens_(nullptr), n_tokens_(nullptr), speaker_(nullptr), gp_(gp), up_(nullptr),
+          codes_(nullptr), n_frames_(nullptr), qst_(qst), text_(nullptr), tlog_(nullptr), dev_hold_(false),
+          qs_(e, S, 0, gp.max_len, true, on_batch, user, interval, qst, &fault_, alog), t_(S), tp_(0), sel_(S, 0), g1_(gp),
+          alog_(alog), arrive_(arrive), arrive_user_(user) {}
     bool run();
+    bool run_open();
     bool faulted() const { return fault_; }   // run() failed on a persistent kernel's hand-off fault
 
 private:
@@ -318,6 +341,19 @@ private:
     bool wait_admission();
     bool poll();
     void one_slot_params(const UttParams &r);
+    void restore_context();
+    // the open form
+    bool prepare_open();
+    bool loop_open();
+    bool arrivals();
+    bool admit_open();
+    bool retire();
+    void sync_tables();
+    void bind(int h);
+    static std::string check_cb(void *ctx, int32_t id, const Arrival &a, UttParams *up, int *plen) {
+        QueueLoop *q = static_cast<QueueLoop *>(ctx);
+        return q->e_.check_arrival(id, a, q->gp_, up, plen);
+    }
 
     Engine &e_;
     const int n_utt_, S_, max_active_, interval_;
@@ -325,11 +361,11 @@ private:
     const int *const n_tokens_in_;
     const int32_t *const *tokens_;   // (open utterances: their heads padded, below)
     const int *n_tokens_;
-    const float *const *const speaker_;
+    const float *const *speaker_;
     const GenParams &gp_;            // the call's (e_.gp_: what the captured frame graphs bake)
     const UttParams *const up_;
     int32_t *const codes_;
-    int *const n_frames_;
+    int *n_frames_;
     QueueState &qst_;
     const TextFeed *const text_;
     TextLog *const tlog_;
@@ -357,6 +393,14 @@ private:
     Event aev_{hipEventDisableTiming}, pev_{hipEventDisableTiming}, rev_{hipEventDisableTiming};   // admission, poll, release
     int f_ = 0;                      // the loop clock: frame graphs launched
     bool polled_ = false;            // one frame in flight: frame f is launched before frame f-1's done flags are read
+    // the open form: every per-utterance table above is indexed by the handles of the arrival log and grows with it
+    ArrivalLog *const alog_ = nullptr;
+    const ArriveCb arrive_ = nullptr;
+    void *const arrive_user_ = nullptr;
+    ArrivalPlanner ap_;
+    std::vector<const float *> spk_eff_;
+    std::vector<int> nf_;            // n_frames_ of the open form
+    int f_mark_ = 0;                 // the loop clock at the last arrival, activation or release
 };
 
 bool Engine::QueueLoop::prepare() {
@@ -463,9 +507,10 @@ bool Engine::QueueLoop::activate() {   // the batch in flight has finished: its 
     if (as_ != e.stream_) Q3T_HIP(hipStreamWaitEvent(e.stream_, aev_, 0));
     for (int k : t_.batch_tgt) {
         const int u = t_.slot_utt[k];
-        if (up_ && S_ == 1) one_slot_params(ups_[u]);
-        // an open utterance: its rows without the tts_eos row, n_tokens = K + 9 (what the padded head counts)
-        if (!e.activate_slot(k, (uint64_t)u, t_.tl[k] - (tp_.is_open[u] ? 1 : 0), n_tokens_[u], ups_[u], plens_[u],
+        if ((up_ || alog_) && S_ == 1) one_slot_params(ups_[u]);
+        // an open utterance: its rows without the tts_eos row, n_tokens = K + 9 (what the padded head counts).  Sampling is
+        // keyed by the utterance's index, in the open form by its arrival's key
+        if (!e.activate_slot(k, alog_ ? alog_->e[u].key : (uint64_t)u, t_.tl[k] - (text_ && tp_.is_open[u] ? 1 : 0), n_tokens_[u], ups_[u], plens_[u],
                              pin_ + (size_t)k * 16, qs_.active()))
             return false;
         if (dev_hold_) Q3T_HIP(hipMemsetAsync(e.held_flag_ + k, 0, 4, e.stream_));
@@ -656,21 +701,24 @@ bool Engine::QueueLoop::finish() {
     return true;
 }
 
+void Engine::QueueLoop::restore_context() {
+    Engine &e = e_;
+    hipStreamSynchronize(as_);
+    hipStreamSynchronize(e.stream_);
+    e.policy_slots_ = 0;
+    std::vector<uint64_t> ident(e.max_slots_);
+    for (int k = 0; k < e.max_slots_; ++k) ident[k] = (uint64_t)k;
+    hipMemcpyAsync(e.utt_, ident.data(), e.max_slots_ * 8, hipMemcpyHostToDevice, e.stream_);
+    hipStreamSynchronize(e.stream_);
+}
+
 bool Engine::QueueLoop::run() {
     Engine &e = e_;
     for (int u = 0; u < n_utt_; ++u) n_frames_[u] = 0;
     if (!prepare()) return false;
     // every exit drains both streams and leaves the context as generate() expects it: kernels chosen by the call's
     // own slot count, sampling keyed by slot index
-    ScopeExit restore([&] {
-        hipStreamSynchronize(as_);
-        hipStreamSynchronize(e.stream_);
-        e.policy_slots_ = 0;
-        std::vector<uint64_t> ident(e.max_slots_);
-        for (int k = 0; k < e.max_slots_; ++k) ident[k] = (uint64_t)k;
-        hipMemcpyAsync(e.utt_, ident.data(), e.max_slots_ * 8, hipMemcpyHostToDevice, e.stream_);
-        hipStreamSynchronize(e.stream_);
-    });
+    ScopeExit restore([&] { restore_context(); });
     if (!park_all()) return false;
     if (text_) {
         e.text_stats = TextStats{};
@@ -684,6 +732,187 @@ bool Engine::QueueLoop::run() {
     fam_ = queue_family(S_, e.mm_ok_, gemm_mfma_min_batch());
     e.policy_slots_ = S_;
     return loop() && finish();
+}
+
+// ------------------------------------------------------------------------------------------------ the open queue
+// (DESIGN 2f "Arrivals")  The device side is the closed queue's with records: the same admission batches (ragged
+// prefill, waiting position 10), activations, frame graphs and collections.  What differs is the host side: the
+// utterances come from the arrival callback (ArrivalPlanner), live in the arrival log and are named by its handles.
+
+// the per-utterance tables follow the log's rows
+void Engine::QueueLoop::sync_tables() {
+    const size_t n = alog_->e.size();
+    cap_.resize(n, 0); plens_.resize(n, 0); ups_.resize(n);
+    tok_eff_.resize(n, nullptr); nt_eff_.resize(n, 0); spk_eff_.resize(n, nullptr); nf_.resize(n, 0);
+    qst_.delivered.resize(n, 0); qst_.stopped.resize(n, 0); qst_.finaled.resize(n, 0);
+    qs_.grow(n);
+    tokens_ = tok_eff_.data(); n_tokens_ = nt_eff_.data(); speaker_ = spk_eff_.data(); n_frames_ = nf_.data();
+    for (int h = 0; h < (int)n; ++h)
+        if (alog_->e[h].id >= 0) bind(h);
+}
+
+// handle h's rows from its log entry
+void Engine::QueueLoop::bind(int h) {
+    const ArrivalLog::Entry &x = alog_->e[h];
+    cap_[h] = x.up.max_len; plens_[h] = x.plen; ups_[h] = x.up;
+    tok_eff_[h] = x.tokens.data(); nt_eff_[h] = (int)x.tokens.size();
+    spk_eff_[h] = x.speaker.empty() ? nullptr : x.speaker.data();
+}
+
+bool Engine::QueueLoop::prepare_open() {
+    Engine &e = e_;
+    mixed_plen_ = true;   // prompt lengths are not known ahead: free slots wait above every prompt
+    plen_ = 10;
+    if (gp_.max_len > e.codes_max_len_) { set_error("max_len exceeds the code buffer"); return false; }
+    if (!e.alloc_admission()) return false;
+    e.q_slots_ = S_;
+    as_ = (S_ == 1 && e.persist_enabled()) ? e.stream_ : e.astream_;
+    e.rec_on_ = S_ > 1;
+    e.own_max_len_ = true;
+    if (!e.set_seed(gp_.seed, e.stream_)) return false;
+    if (!qs_.begin()) return false;
+    if (!e.ensure_pinned(((size_t)S_ * 19 + 2) * 4)) return false;   // (the layout of prepare())
+    pin_ = static_cast<int *>(e.pin_);
+    done_h_ = pin_ + (size_t)S_ * 16; tgt_h_ = pin_ + (size_t)S_ * 17; park_ = pin_ + (size_t)S_ * 18;
+    held_h_ = pin_ + (size_t)S_ * 18 + 2;
+    for (int k = 0; k < S_; ++k) held_h_[k] = 0;
+    park_[0] = 0;
+    park_[1] = plen_;
+    // a re-run: what ended before the fault leaves the log, every handle in limbo is free (the chunks that named it
+    // died with the run), and the utterances still alive are admitted again, in id order
+    sync_tables();
+    retire_arrivals(*alog_, t_, qst_, qs_.run(), 0, SIZE_MAX);
+    ap_.max_active = max_active_;
+    ap_.hidden = e.c_.hidden;
+    ap_.begin(*alog_);
+    return true;
+}
+
+// at most one ask of the arrival callback (if the planner's rules allow one), then the admission of what waits
+bool Engine::QueueLoop::arrivals() {
+    if (!t_.batch_tgt.empty()) return true;
+    std::vector<int> acc;
+    bool grown = false, aborted = false;
+    const std::string err = ap_.ask(t_, *alog_, qs_.pending(), arrive_, arrive_user_, &QueueLoop::check_cb, this, acc, &grown, &aborted);
+    if (!err.empty()) { set_error(err); return false; }
+    if (aborted) { qst_.aborted = true; return true; }
+    if (grown) sync_tables();
+    for (int h : acc) { bind(h); nf_[h] = 0; }
+    if (!acc.empty()) f_mark_ = f_;
+    return ap_.waiting.empty() || admit_open();
+}
+
+bool Engine::QueueLoop::admit_open() {   // admit() with the utterances taken from the planner's waiting list
+    Engine &e = e_;
+    std::vector<int> tgt, utt;
+    t_.pick_waiting(ap_.waiting, max_active_, tgt, utt);
+    if (tgt.empty()) return true;
+    if (as_ != e.stream_) {
+        Q3T_HIP(hipEventRecord(rev_, e.stream_));
+        Q3T_HIP(hipStreamWaitEvent(as_, rev_, 0));
+    }
+    if (!e.admit_batch(tgt, utt, tokens_, n_tokens_, speaker_, ups_, plens_, true, as_, tgt_h_, batch_tl_)) return false;
+    Q3T_HIP(hipEventRecord(aev_, as_));
+    t_.admitted(tgt, utt, batch_tl_);
+    ap_.admitted(tgt.size());
+    return true;
+}
+
+// after deliveries: the utterances that had their final delivery or were cancelled leave the log and the tables
+bool Engine::QueueLoop::retire() {
+    for (int h = 0; h < (int)alog_->e.size(); ++h)
+        if (alog_->e[h].id >= 0 && qst_.finaled[h] && !qst_.stopped[h] && qst_.delivered[h] != n_frames_[h]) {
+            set_error("generate_queue_open: utterance " + std::to_string(alog_->e[h].id) + " ended without its final delivery");
+            return false;
+        }
+    retire_arrivals(*alog_, t_, qst_, qs_.run(), qs_.collected(), qs_.delivered());
+    return true;
+}
+
+bool Engine::QueueLoop::loop_open() {
+    Engine &e = e_;
+    int fin_seen = 0;
+    while (!qst_.aborted && !ap_.finished(t_, *alog_)) {
+        if (t_.n_active() == 0) {
+            // nothing runs, so nothing runs behind the pending deliveries: hand them out.  Then the ask (with no slot
+            // busy it is the idle one, which may block), the admission of what it brought, and the wait for the batch
+            if (!deliver(INT_MAX) || !retire()) return false;
+            if (qst_.aborted) break;
+            if (!arrivals()) return false;
+            if (qst_.aborted) break;
+            if (!t_.batch_tgt.empty()) {
+                Q3T_HIP(hipEventSynchronize(aev_));
+                if (!activate()) return false;
+                f_mark_ = f_;
+                polled_ = false;
+            }
+            continue;
+        }
+        hipGraphExec_t fg = nullptr;
+        if (!frame_graph(&fg)) return false;
+        if (!e.persist_fault_hook(S_, (e.persist_ ? 1 : 0) + (e.persist_cp_ ? 1 : 0))) return false;
+        Q3T_HIP(hipGraphLaunch(fg, e.stream_));
+        ++f_;
+        t_.launched();
+        if (f_ % qs_.interval() == 0) {   // a tick, as in loop()
+            for (int k = 0; k < S_; ++k) sel_[k] = t_.state[k] == SlotTable::ACTIVE;
+            if (!qs_.collect(t_.slot_utt, sel_, false, f_ + qs_.interval())) return false;
+        }
+        if (!deliver(f_) || !retire()) return false;
+        if (qst_.aborted) break;
+        if (polled_ && !reap()) return false;
+        if (t_.n_fin != fin_seen) { fin_seen = t_.n_fin; f_mark_ = f_; }
+        if (!t_.batch_tgt.empty() && (as_ == e.stream_ || hipEventQuery(aev_) == hipSuccess)) {
+            if (!activate()) return false;
+            f_mark_ = f_;
+        }
+        if (!arrivals()) return false;
+        if (qst_.aborted) break;
+        if (as_ == e.stream_ && !t_.batch_tgt.empty()) {
+            if (!activate()) return false;
+            f_mark_ = f_;
+        }
+        if (!poll()) return false;
+        if (queue_no_progress(f_ - f_mark_, t_.n_busy, gp_.max_len, plen_)) { set_error("generate_queue_open: no progress"); return false; }
+    }
+    return true;
+}
+
+bool Engine::QueueLoop::run_open() {
+    Engine &e = e_;
+    if (!prepare_open()) return false;
+    ScopeExit restore([&] { restore_context(); });
+    if (!park_all()) return false;
+    fam_ = queue_family(S_, e.mm_ok_, gemm_mfma_min_batch());
+    e.policy_slots_ = S_;
+    if (!loop_open() || !finish() || !retire()) return false;
+    if (!qst_.aborted && alog_->n_live != 0) { set_error("generate_queue_open: an utterance ended without its final delivery"); return false; }
+    return true;
+}
+
+bool Engine::generate_queue_open(const GenParams &gp, int slots, int max_active, ArriveCb arrive, QueueCb on_batch, void *user,
+                                 int interval, int32_t *n_arrived, int32_t *n_finished) {
+    if (n_arrived) *n_arrived = 0;
+    if (n_finished) *n_finished = 0;
+    if (!arrive || !on_batch) { set_error("generate_queue_open: null callback"); return false; }
+    if (interval <= 0) { set_error("generate_queue_open: the delivery interval must be > 0"); return false; }
+    if (gp.max_len <= 0) { set_error("generate_queue_open: max_len must be > 0"); return false; }
+    if (slots > max_slots_) { set_error("generate_queue_open: more slots than the context has"); return false; }
+    const int S = slots <= 0 ? max_slots_ : slots;
+    // held for the whole call, also while an idle ask blocks
+    DeviceLock lk(persist_exclusive(S), device_);
+    QueueState qst(0);
+    ArrivalLog log;
+    ScopeExit rec_off([&] { rec_on_ = false; });
+    for (int run = 0;; ++run) {
+        QueueLoop loop(*this, gp, S, max_active, arrive, on_batch, user, interval, qst, &log);
+        const bool ok = loop.run_open();
+        if (n_arrived) *n_arrived = log.next_id;
+        if (n_finished) *n_finished = log.n_done;
+        if (ok) return true;
+        if (!loop.faulted() || run == 1) return false;
+        if (!persist_recover()) return false;   // as generate_queue: the re-run admits the log's live utterances again
+    }
 }
 
 bool Engine::generate_queue(int n_utt,const int32_t *const *tokens, const int *n_tokens, const float *const *speaker,

@@ -1,16 +1,30 @@
 // queue_sched.h — the host decisions of the continuous-batching queue (Engine::QueueLoop, engine_queue.cpp):
 // the slot table (which utterance holds which slot, what is admitted next, which slots a frame graph covers, which
 // utterances ended by the polled flags) and the text-feed planner (when an open utterance is asked, what a feed adds to
-// the round, the log a fallback re-run replays, the hold / release rule, the round's blob).  Header-only and free of HIP
-// so tests/cpp/test_queue_sched.cpp drives it on the CPU against a scripted device.  A function that can reject input
-// returns its message (empty: ok); the caller hands it to set_error.
+// the round, the log a fallback re-run replays, the hold / release rule, the round's blob) and, for the open queue, the
+// arrival planner and log (when the arrival callback is asked, what a re-run admits again).  Header-only and free of HIP
+// so tests/cpp/test_queue_sched.cpp and test_queue_arrivals.cpp drive it on the CPU against a scripted device.  A
+// function that can reject input returns its message (empty: ok); the caller hands it to set_error.
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <cstdint>
 #include <string>
 #include <vector>
 
+#include "queue_deliver.h"
+
 namespace q3t {
+
+// one utterance's own values (q3t_utt_params): what GenParams holds for the whole call, except the seed
+struct UttParams {
+    int language_id = 2050;    // < 0: the nothink prompt (one row shorter)
+    int max_len = 0;           // 1 .. GenParams::max_len
+    float rep_penalty = 1.05f;
+    float temperature = 0.9f;
+    int top_k = 50;
+    int force_frames = 0;
+};
 
 // an utterance's length by its done word (the index of the frame whose CB0 was EOS, < 0: none yet) and its max_len
 inline int frames_of(int done, int cap) { return done >= 0 ? std::min(done, cap) : cap; }
@@ -43,6 +57,12 @@ struct SlotTable {
         tgt.clear(); utt.clear();
         for (int k = 0; k < slots() && next + (int)tgt.size() < n_utt && n_busy + (int)tgt.size() < max_active; ++k)
             if (state[k] == FREE) { tgt.push_back(k); utt.push_back(next + (int)tgt.size() - 1); }
+    }
+    // the same for the open queue: the utterances come from `waiting` (accepted arrivals not yet admitted, in id order)
+    void pick_waiting(const std::vector<int> &waiting, int max_active, std::vector<int> &tgt, std::vector<int> &utt) const {
+        tgt.clear(); utt.clear();
+        for (int k = 0; k < slots() && tgt.size() < waiting.size() && n_busy + (int)tgt.size() < max_active; ++k)
+            if (state[k] == FREE) { tgt.push_back(k); utt.push_back(waiting[tgt.size() - 1]); }
     }
     void admitted(const std::vector<int> &tgt, const std::vector<int> &utt, const std::vector<int> &batch_tl) {
         for (size_t j = 0; j < tgt.size(); ++j) {
@@ -245,5 +265,171 @@ struct TextPlanner {
         }
     }
 };
+
+// ------------------------------------------------------------------------------------------------------ arrivals
+// The open queue (Engine::generate_queue_open; DESIGN 2f "Arrivals"): the utterances are not known up front, they come
+// from an arrival callback while the loop runs.  An accepted utterance has an id (arrival order, from 0 per call) and,
+// while it lives, a handle: the index of its row in every per-utterance table of the loop (SlotTable::slot_utt,
+// QueueState, QueueRun, the log below).  Handles are reused, so the tables are as large as the most utterances that
+// were ever alive at once, which the slot count bounds, not as the number of arrivals so far.
+
+// what the arrival callback hands over: read before the callback returns
+struct Arrival {
+    const int32_t *tokens = nullptr;
+    int n_tokens = 0;
+    const float *speaker = nullptr;   // hidden floats or null
+    UttParams up;
+    uint64_t key = 0;                 // the utterance's sampling key
+};
+
+// Every accepted arrival, copied when the callback returned and kept until its final delivery or its cancel (end()):
+// what a re-run after a hand-off fault admits again, and where the admissions read the prompts from.  It also keeps
+// what must survive a re-run: the next id and the close.
+struct ArrivalLog {
+    struct Entry {
+        int32_t id = -1;              // -1: the handle is free (or in limbo)
+        uint64_t key = 0;
+        std::vector<int32_t> tokens;
+        std::vector<float> speaker;   // empty: none
+        UttParams up;                 // validated, max_len resolved
+        int plen = 0;                 // its prompt rows
+    };
+    struct Limbo { int h; size_t stamp; };
+    std::vector<Entry> e;             // by handle
+    std::vector<int> free_h;
+    // an ended utterance's handle is reused only when every chunk collected before it ended has been delivered: such a
+    // chunk may still name the handle (a tick's chunk is delivered one tick late)
+    std::vector<Limbo> limbo;
+    int32_t next_id = 0, n_done = 0;  // ids handed out; utterances ended (final delivery or cancel)
+    int n_live = 0;
+    bool closed = false;
+
+    // a handle for a new utterance (the tables grow by one row when none is free); *grown: e.size() changed
+    int take(bool *grown) {
+        *grown = free_h.empty();
+        if (*grown) { e.emplace_back(); free_h.push_back((int)e.size() - 1); }
+        const int h = free_h.back();
+        free_h.pop_back();
+        ++n_live;
+        return h;
+    }
+    // the utterance of handle h had its final delivery or was cancelled; stamp: the chunks collected so far
+    void end(int h, size_t stamp) {
+        Entry &x = e[h];
+        x.id = -1;
+        std::vector<int32_t>().swap(x.tokens);
+        std::vector<float>().swap(x.speaker);
+        limbo.push_back(Limbo{h, stamp});
+        --n_live;
+        ++n_done;
+    }
+    // `delivered` chunks have been delivered: the handles in limbo that no pending chunk can name are free again
+    // (reset(h): clear the handle's rows in the other tables)
+    template <class F> void recycle(size_t delivered, F &&reset) {
+        size_t keep = 0;
+        for (const Limbo &l : limbo) {
+            if (l.stamp <= delivered) { reset(l.h); free_h.push_back(l.h); }
+            else limbo[keep++] = l;
+        }
+        limbo.resize(keep);
+    }
+    // the handles of the live utterances in id order: what a re-run admits again
+    std::vector<int> unfinished() const {
+        std::vector<int> v;
+        for (int h = 0; h < (int)e.size(); ++h) if (e[h].id >= 0) v.push_back(h);
+        std::sort(v.begin(), v.end(), [this](int a, int b) { return e[a].id < e[b].id; });
+        return v;
+    }
+};
+
+// When the arrival callback is asked, and what its answer does.  It is asked at most once per loop iteration, between
+// two frames, and only when no admission batch is in flight, the source is not closed, nothing accepted is still
+// waiting for a slot and room = min(free slots, max_active - busy) > 0.  idle = 1 exactly when no slot is busy (and so
+// nothing runs or is pending): then the callback may block; with idle = 0 it must return at once.  It returns at most
+// `room` utterances: the engine keeps no backlog.  Every arrival of an answer is validated before any is accepted.
+// While deliveries are pending the idle ask waits (the loop hands them out first): nothing waits behind a blocking ask.
+struct ArrivalPlanner {
+    // the arrival callback (Engine::ArriveCb): 0 ends the call
+    typedef int (*AskFn)(void *user, int32_t next_id, int32_t room, int32_t running, int32_t idle, Arrival *out, int32_t *n,
+                         int32_t *closed);
+    // the checks of an arrival (Engine::check_arrival): its message or empty; *up: the record with max_len resolved
+    typedef std::string (*CheckFn)(void *ctx, int32_t id, const Arrival &a, UttParams *up, int *plen);
+    int max_active = 0;               // <= the slot count
+    int hidden = 0;                   // floats of a speaker row
+    std::vector<int> waiting;         // handles accepted and not yet admitted, in id order
+    std::vector<Arrival> buf;
+    int last_room = 0, last_idle = 0; // of the last ask
+
+    // a run begins: a re-run admits the log's unfinished utterances again, in id order, before the callback is asked
+    void begin(const ArrivalLog &log) { waiting = log.unfinished(); }
+    int room(const SlotTable &t) const { return std::min(t.slots(), max_active) - t.n_busy - (int)waiting.size(); }
+    bool may_ask(const SlotTable &t, const ArrivalLog &log) const {
+        return t.batch_tgt.empty() && !log.closed && waiting.empty() && room(t) > 0;
+    }
+    // the source is closed and every accepted utterance has left its slot
+    bool finished(const SlotTable &t, const ArrivalLog &log) const { return log.closed && waiting.empty() && t.n_busy == 0; }
+    void admitted(size_t n) { waiting.erase(waiting.begin(), waiting.begin() + n); }
+    // one ask, if the rules allow it.  accepted: the handles of the utterances it brought (also in `waiting`);
+    // *grown: the log has more rows than before; *aborted: the callback returned 0.  deliveries_pending: collected chunks
+    // wait for their delivery
+    std::string ask(const SlotTable &t, ArrivalLog &log, bool deliveries_pending, AskFn cb, void *user, CheckFn check,
+                    void *cctx, std::vector<int> &accepted, bool *grown, bool *aborted) {
+        accepted.clear();
+        *grown = *aborted = false;
+        if (!may_ask(t, log) || (t.n_busy == 0 && deliveries_pending)) return std::string();
+        if (log.next_id == INT32_MAX) return "arrival ids exhausted: a call takes at most 2^31 - 1 utterances";
+        const int rm = room(t);
+        buf.assign(rm, Arrival());
+        int32_t n = 0, cl = 0;
+        last_room = rm;
+        last_idle = t.n_busy == 0;
+        if (!cb(user, log.next_id, rm, t.n_busy, last_idle, buf.data(), &n, &cl)) { *aborted = true; return std::string(); }
+        if (n < 0 || n > rm)
+            return "utterance " + std::to_string(log.next_id) + ": the arrival callback returned " + std::to_string(n) +
+                   " utterances for a room of " + std::to_string(rm);
+        if (n > INT32_MAX - log.next_id) return "arrival ids exhausted: a call takes at most 2^31 - 1 utterances";
+        std::vector<UttParams> ups(n);
+        std::vector<int> plens(n);
+        for (int i = 0; i < n; ++i) {
+            const std::string err = check(cctx, log.next_id + i, buf[i], &ups[i], &plens[i]);
+            if (!err.empty()) return err;
+        }
+        for (int i = 0; i < n; ++i) {
+            bool g = false;
+            const int h = log.take(&g);
+            *grown = *grown || g;
+            ArrivalLog::Entry &x = log.e[h];
+            x.id = log.next_id++;
+            x.key = buf[i].key;
+            x.tokens.assign(buf[i].tokens, buf[i].tokens + buf[i].n_tokens);
+            if (buf[i].speaker) x.speaker.assign(buf[i].speaker, buf[i].speaker + hidden);
+            else x.speaker.clear();
+            x.up = ups[i];
+            x.plen = plens[i];
+            waiting.push_back(h);
+            accepted.push_back(h);
+        }
+        if (cl) log.closed = true;
+        return std::string();
+    }
+};
+
+// After deliveries (and after the slots of cancelled utterances were released): the utterances that had their final
+// delivery or were cancelled leave the log, and the handles no pending chunk can name any more are cleared for reuse.
+// collected / delivered: the chunks collected / delivered so far in this run
+inline void retire_arrivals(ArrivalLog &log, const SlotTable &t, QueueState &st, QueueRun &r, size_t collected, size_t delivered) {
+    for (int h = 0; h < (int)log.e.size(); ++h) {
+        if (log.e[h].id < 0 || !(st.finaled[h] || st.stopped[h])) continue;
+        bool in_slot = false;
+        for (int k = 0; k < t.slots() && !in_slot; ++k) in_slot = t.state[k] != SlotTable::FREE && t.slot_utt[k] == h;
+        // (a final chunk is the last one collected that names its utterance, and chunks are delivered in order: only a
+        // cancelled utterance can still be named by a pending chunk)
+        if (!in_slot) log.end(h, st.stopped[h] ? collected : 0);
+    }
+    log.recycle(delivered, [&](int h) {
+        st.delivered[h] = 0; st.stopped[h] = 0; st.finaled[h] = 0;
+        r.run[h] = 0; r.gone[h] = 0;
+    });
+}
 
 }  // namespace q3t

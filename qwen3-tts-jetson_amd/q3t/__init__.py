@@ -4,8 +4,10 @@ The compute runs in libq3t.so (hand-written gfx950 HIP kernels).  There is NO CP
 module fails loudly if the in-tree extension is missing, and every call raises Q3TError with
 q3t_last_error() when the C ABI reports failure (the reference's bool + get_error() convention).
 """
+import collections
 import ctypes as C
 import os
+import threading
 import weakref
 
 import numpy as np
@@ -82,6 +84,19 @@ _lib.q3t_generate_queue_text.argtypes = [_P, _I, C.POINTER(C.POINTER(C.c_int32))
                                          _P, C.c_void_p]
 _lib.q3t_text_feed_stats.argtypes = [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                      C.POINTER(C.c_double)]
+
+
+class Arrival(C.Structure):
+    """q3t_arrival: one utterance handed to the open queue"""
+    _fields_ = [("tokens", C.POINTER(C.c_int32)), ("n_tokens", C.c_int32), ("speaker", C.POINTER(C.c_float)),
+                ("up", UttParams), ("key", C.c_uint64)]
+
+
+ARRIVE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Arrival),
+                        C.POINTER(C.c_int32), C.POINTER(C.c_int32))
+_lib.q3t_generate_queue_open.argtypes = [_P, C.POINTER(GenParams), C.c_int32, C.c_int32, ARRIVE_CB, QUEUE_CB, C.c_void_p,
+                                         C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+_lib.q3t_check_utt.argtypes = [_P, _P, C.c_int32, _P, C.POINTER(GenParams), C.POINTER(UttParams)]
 _lib.q3t_talker_prefill_ragged.argtypes = [_P, _I, _ip, _fp, _I, _P, _P]
 COMM_ID_BYTES = 128
 _lib.q3t_comm_unique_id.argtypes = [C.c_char_p]
@@ -149,7 +164,7 @@ EXPORTS = ["q3t_last_error", "q3t_default_params", "q3t_ctx_create", "q3t_ctx_de
            "q3t_tokenizer_load", "q3t_tokenizer_free", "q3t_tokenizer_info", "q3t_tokenizer_encode",
            "q3t_tokenizer_decode", "q3t_talker_forward", "q3t_talker_prefill", "q3t_talker_prefill_ragged",
            "q3t_utt_params_from", "q3t_generate_utt", "q3t_generate_queue_utt", "q3t_generate_queue_text",
-           "q3t_text_feed_stats",
+           "q3t_text_feed_stats", "q3t_generate_queue_open", "q3t_check_utt",
            "q3t_codepred_frame", "q3t_cb0_select", "q3t_project_text", "q3t_prefill_embd", "gpu_fp32_to_fp16",
            "gpu_argmax_f32", "gpu_embedding_lookup_by_gpu_id", "gpu_sample_topk_f32"]
 
@@ -330,6 +345,44 @@ class TextFeeder:
         """ids of the held-back rest; the feeder is empty afterwards"""
         buf, self.pending = self.pending, b""
         return self.tok.encode(buf) if buf else []
+
+
+class ArrivalQueue:
+    """A thread-safe source for Engine.generate_queue_open: any thread submit()s requests while the queue runs on
+    another; pass its `source` method as the call's source.  Requests are handed over in submission order, so the id
+    submit() returns is the id the deliveries name.  The source waits (on a condition) only when the engine says it is
+    idle; otherwise it returns at once with what is there and fits."""
+
+    def __init__(self):
+        self._cv = threading.Condition()
+        self._q = collections.deque()
+        self._next = 0
+        self._closed = False
+
+    def submit(self, prompt, speaker=None, key=None, **per_utt):
+        """queue one request (per_utt: language_id / max_len / repetition_penalty / temperature / top_k /
+        force_frames); key: its sampling key (default: its id).  Returns its id."""
+        with self._cv:
+            if self._closed:
+                raise ValueError("ArrivalQueue: submit after close")
+            uid = self._next
+            self._next += 1
+            self._q.append(dict(prompt=prompt, speaker=speaker, key=uid if key is None else key, **per_utt))
+            self._cv.notify_all()
+            return uid
+
+    def close(self):
+        """no more requests: the call returns when the ones submitted have ended"""
+        with self._cv:
+            self._closed = True
+            self._cv.notify_all()
+
+    def source(self, next_id, room, running, idle):
+        with self._cv:
+            if idle:
+                self._cv.wait_for(lambda: self._q or self._closed)
+            out = [self._q.popleft() for _ in range(min(room, len(self._q)))]
+            return out, self._closed and not self._q
 
 
 class VocoderStream:
@@ -670,6 +723,79 @@ class Engine:
             raise errors[0]
         _check_frames(rc, nf)
         return [codes[i, :nf[i]].copy() for i in range(n)], [int(x) for x in held]
+
+    def generate_queue_open(self, source, on_batch, interval=12, slots=0, max_active=0, **params):
+        """The open queue (q3t_generate_queue_open): utterances are admitted while continuous batching runs.
+        source(next_id, room, running, idle) -> (list of dict(prompt=, speaker=, key=, **per_utt), closed) is asked
+        between two frames whenever a slot could take a newcomer; it returns at most `room` requests (the first gets
+        id next_id) and must return at once unless idle is true, when it may block until a request exists.  closed true:
+        no more will come; the call returns when every accepted utterance has ended.  None stands for ([], False),
+        returning False aborts the call.  key (default: the id) is the sampling key: the utterance's codes are those of
+        index `key` of generate_queue(per_utt=...) at the same slot count, seed and max_len.  on_batch: as in
+        generate_queue_stream(), with the ids in place of the indices.  q3t.ArrivalQueue is a ready-made source.
+        params: max_len and seed, and the defaults of the per-utterance values.  Returns (n_arrived, n_finished)."""
+        if not callable(source) or not callable(on_batch):
+            raise TypeError("generate_queue_open: source and on_batch must be callable")
+        if isinstance(interval, bool) or not isinstance(interval, (int, np.integer)) or interval <= 0:
+            raise ValueError("generate_queue_open: interval must be an integer > 0")
+        p = default_params(**params)
+        errors = []
+        keep = []   # what the records point into stays alive until the next ask
+
+        def _arrive(_user, next_id, room, running, idle, out, n_out, closed_out):
+            try:
+                r = source(int(next_id), int(room), int(running), bool(idle))
+                if r is False:
+                    return 0
+                items, closed = r if r else ((), False)
+                items = list(items)
+                keep.clear()
+                for i, it in enumerate(items[:room]):
+                    it = dict(it)
+                    tok = np.ascontiguousarray(it.pop("prompt"), np.int32).reshape(-1)
+                    spk = it.pop("speaker", None)
+                    key = it.pop("key", None)
+                    up = utt_params(p, [it], 1)
+                    keep.append(tok)
+                    out[i].tokens = tok.ctypes.data_as(C.POINTER(C.c_int32))
+                    out[i].n_tokens = len(tok)
+                    if spk is None:
+                        out[i].speaker = C.POINTER(C.c_float)()
+                    else:
+                        spk = np.ascontiguousarray(spk, np.float32).reshape(-1)
+                        if len(spk) != self.cfg["hidden"]:
+                            raise ValueError(f"utterance {next_id + i}: a speaker embedding has {self.cfg['hidden']} floats")
+                        keep.append(spk)
+                        out[i].speaker = spk.ctypes.data_as(C.POINTER(C.c_float))
+                    out[i].up = up[0]
+                    out[i].key = int(next_id + i if key is None else key)
+                n_out[0] = len(items)   # (more than room: the engine refuses the answer)
+                closed_out[0] = 1 if closed else 0
+                return 1
+            except Exception as e:  # never let an exception unwind through the C frames
+                errors.append(e)
+                return 0
+
+        acb = ARRIVE_CB(_arrive)
+        cb = _queue_cb(on_batch, errors)
+        na, nfin = C.c_int32(0), C.c_int32(0)
+        rc = _lib.q3t_generate_queue_open(self.h, C.byref(p), int(slots), int(max_active), acb, cb, None, int(interval),
+                                          C.byref(na), C.byref(nfin))
+        keep.clear()
+        if errors:
+            raise errors[0]
+        _check(rc)
+        return na.value, nfin.value
+
+    def check_utt(self, prompt, speaker=None, per_utt=None, **params):
+        """What generate_queue_open (or generate_queue with per_utt) would refuse of one request (q3t_check_utt): the
+        message, or None if it is fine.  Nothing runs."""
+        p = default_params(**params)
+        up = utt_params(p, [per_utt], 1)
+        tok = np.ascontiguousarray(prompt, np.int32).reshape(-1)
+        spk = None if speaker is None else np.ascontiguousarray(speaker, np.float32).reshape(-1)
+        rc = _lib.q3t_check_utt(self.h, _addr(tok), len(tok), _addr(spk), C.byref(p), up)
+        return None if rc == 0 else _lib.q3t_last_error().decode(errors="replace")
 
     def text_feed_stats(self):
         """counters of the last generate_queue_text() with an open utterance: frame graphs launched, loop rounds that

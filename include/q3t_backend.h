@@ -360,6 +360,58 @@ int q3t_vocoder_stream_push_batch(q3t_voc_stream *const *streams, int32_t n_stre
                                   float *const *pcm, const int64_t *pcm_cap, int64_t *n_samples);
 int32_t q3t_vocoder_stream_last_groups(const q3t_ctx *ctx);
 
+/* ---- output stage: resampled f32 / s16 / mu-law PCM from decodes and streams, converted on the device so that only
+ * the client's bytes are copied back.  The input is the vocoder's f32 at its native rate (24000).  Rates: 8000, 12000,
+ * 16000, 22050, 24000, 32000, 44100, 48000; anything else is Q3T_ERR with a message naming the rate and the list.  The
+ * resampler is a causal polyphase FIR (Kaiser-windowed sinc, 16 zero crossings a side, cut-off 0.9 of the lower
+ * Nyquist; DESIGN 2c "Output stage" states it exactly) whose every output sample is one fmaf chain in a fixed order:
+ * a stream's bytes do not depend on how its frames were cut into pushes or on which streams shared a launch, and the
+ * concatenation over its pushes (the last one final) is, byte for byte, q3t_vocoder_decode_out of all frames.
+ * After S input samples a stream has produced ceil(S * L / M) outputs (L / M = rate / 24000 in lowest terms); the
+ * filter delays the signal by 16 * max(L, M) / L input samples (0.67 .. 2 ms, not compensated); a final push appends
+ * D = ceil(16 * max(L, M) / L) zero samples once, so the tail is emitted.  24000 bypasses the filter: the output is
+ * the input bit for bit, and final adds nothing.
+ * s16: (int16)(clamp(y, -1, 1) * 32767.0f), truncated toward zero (the WAV writer's rule); mu-law: G.711 of that. */
+#define Q3T_PCM_F32 0
+#define Q3T_PCM_S16 1
+#define Q3T_PCM_MULAW 2
+typedef struct q3t_pcm_spec { int32_t sample_rate; int32_t format; } q3t_pcm_spec;
+/* host-only helpers (no device touched) */
+int32_t q3t_pcm_bytes_per_sample(int32_t format);   /* 4 / 2 / 1; 0 for an unknown format */
+/* outputs after n_in_total input samples (final != 0: with the tail); -1 for an unsupported rate */
+int64_t q3t_pcm_num_samples(int64_t n_in_total, int32_t sample_rate, int32_t final);
+/* the exact f32 tap table the kernel uses, [L][K] row-major, taps[p][k] = (float)(L * h[p + k * L]); taps == NULL
+ * queries L, M, K.  24000 has K = 0 (no table).  Q3T_ERR: an unsupported rate, cap < L * K */
+int q3t_pcm_taps(int32_t sample_rate, int32_t *L, int32_t *M, int32_t *K, float *taps, int64_t cap);
+/* one-shot decode (FULL or CHUNK40) through the stage with final = 1: *n_samples samples of spec->format into out
+ * (q3t_pcm_num_samples(q3t_vocoder_num_samples(n_frames, mode), rate, 1) of them) */
+int q3t_vocoder_decode_out(q3t_ctx *ctx, const int32_t *codes /* [n_frames][16] */, int32_t n_frames, int mode,
+                           const q3t_pcm_spec *spec, void *out, int64_t out_cap_bytes, int64_t *n_samples);
+/* give a stream an output spec: only at zero frames (fresh or reset), Q3T_ERR otherwise; spec == NULL clears it.
+ * q3t_vocoder_stream_reset keeps the spec and rewinds the stage (history zeroed, counts 0).  A stream with a spec is
+ * pushed with the _out calls only (the plain pushes return Q3T_ERR, state unchanged) and a stream without one with the
+ * plain calls only; a stream that never had a spec behaves exactly as before. */
+int q3t_vocoder_stream_set_output(q3t_voc_stream *s, const q3t_pcm_spec *spec);
+/* q3t_vocoder_stream_push through the stage: *n_samples samples of the stream's format into out.  final != 0 emits
+ * the tail; after it the stream takes no further output push until it is reset.  An extension over the plain push: a
+ * final push may carry no frames (n_frames == 0, codes ignored) and then only flushes the tail, for an utterance whose
+ * last queue delivery is empty.  Errors as q3t_vocoder_stream_push (out_cap_bytes in place of pcm_cap; n_frames == 0
+ * without final), state unchanged.  A device error after the frames were taken leaves the stream refusing output pushes
+ * until q3t_vocoder_stream_reset (its samples for the stage are gone). */
+int q3t_vocoder_stream_push_out(q3t_voc_stream *s, const int32_t *codes /* [n_frames][16] */, int32_t n_frames,
+                                int32_t final, void *out, int64_t out_cap_bytes, int64_t *n_samples);
+/* q3t_vocoder_stream_push_batch through the stage.  Streams of one call may carry different specs; each stream's bytes
+ * are those of pushing it alone.  The call adds ONE conversion launch (plus the history update) to the launches of
+ * q3t_vocoder_stream_push_batch, and its device-to-host copies carry output bytes only.  final: [n_streams] or NULL
+ * (none).  Error contract of q3t_vocoder_stream_push_batch: every stream unchanged, every n_samples[j] = 0. */
+int q3t_vocoder_stream_push_batch_out(q3t_voc_stream *const *streams, int32_t n_streams, const int32_t *const *codes,
+                                      const int32_t *n_frames, const int32_t *final /* [n_streams] or NULL */,
+                                      void *const *out, const int64_t *out_cap_bytes, int64_t *n_samples);
+int64_t q3t_vocoder_stream_out_samples(const q3t_voc_stream *s); /* output samples so far; -1 without a spec */
+/* diagnostic, not part of the serving interface: k_pcm_out launches made by this process so far (a successful call of
+ * the _out pushes or of q3t_vocoder_decode_out adds exactly one); process-wide, for tests and tools/dev/pcm_out_bench.py */
+int64_t q3t_pcm_out_launches(void);
+
 /* ---- speaker encoder (ECAPA-TDNN; the TTS GGUF's spk_enc.* tensors)
  * q3t_speaker_dim: embedding length, 0 when the model has no speaker encoder.
  * q3t_speaker_encode: AudioTokenizerEncoder::encode (src/audio_tokenizer_encoder.h:107-108): samples in [-1, 1] at

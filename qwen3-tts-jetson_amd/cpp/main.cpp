@@ -73,6 +73,8 @@ void print_usage(const char *program) {
     fprintf(stderr, "  --batch <n>            Server mode: decode up to n queued requests together (default: 1)\n");
     fprintf(stderr, "  --queue <n>            Server mode: run the waiting requests (up to 8n) through n continuously batched\n");
     fprintf(stderr, "                         slots; a reply is written when its request ends (replies may be out of order)\n");
+    fprintf(stderr, "  --sample-rate <hz>     WAV sample rate: 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000; the GPU's\n");
+    fprintf(stderr, "                         output stage resamples and writes the s16 (default: 24000, converted on the host)\n");
     fprintf(stderr, "  --queue-open <n>       Server mode: an open queue of n slots; requests are read and admitted while the\n");
     fprintf(stderr, "                         others run (--max-tokens caps every request)\n");
     fprintf(stderr, "  -h, --help             Show this help\n");
@@ -84,7 +86,8 @@ void print_usage(const char *program) {
     fprintf(stderr, "Server mode:\n");
     fprintf(stderr, "  %s -m ./models -e speaker.bin --serve\n", program);
     fprintf(stderr, "  Then send lines: text<TAB>output.wav[<TAB>key=value;...]\n");
-    fprintf(stderr, "    per-request keys: language, temperature, top_k, repetition_penalty, max_tokens, speaker\n");
+    fprintf(stderr, "    per-request keys: language, temperature, top_k, repetition_penalty, max_tokens, speaker,\n");
+    fprintf(stderr, "                      sample_rate\n");
     fprintf(stderr, "  Responds with:   OK<TAB>duration_s<TAB>time_ms<TAB>output.wav\n");
     fprintf(stderr, "  Send 'quit' to exit.\n");
 }
@@ -172,12 +175,12 @@ void reply(const qwen3_tts::tts_result &result, const Request &q) {
         fflush(stdout);
         return;
     }
-    if (!qwen3_tts::save_audio_file(q.output, result.audio, result.sample_rate)) {
+    if (!qwen3_tts::save_audio_file(q.output, result)) {
         fprintf(stdout, "ERR\tfailed to save %s\n", q.output.c_str());
         fflush(stdout);
         return;
     }
-    const float duration = (float)result.audio.size() / result.sample_rate;
+    const float duration = (float)result.num_samples() / result.sample_rate;
     fprintf(stdout, "OK\t%.2f\t%lld\t%s\n", duration, (long long)result.t_total_ms, q.output.c_str());
     fflush(stdout);
     fprintf(stderr, "  Done: %.2fs audio in %lldms (RTF=%.1f)\n", duration, (long long)result.t_total_ms,
@@ -222,6 +225,7 @@ int run_server(qwen3_tts::Qwen3TTS &tts, const std::vector<float> &speaker_embd,
                 if (q.has_top_k) t.params.top_k = q.top_k;
                 if (q.has_repetition_penalty) t.params.repetition_penalty = q.repetition_penalty;
                 if (q.has_max_tokens) t.params.max_audio_tokens = q.max_tokens;
+                if (q.has_sample_rate) t.params.output_sample_rate = q.sample_rate;
                 if (q.has_speaker) {
                     t.speaker_embedding = load_embedding(q.speaker);
                     if (t.speaker_embedding.empty()) {
@@ -307,6 +311,7 @@ int run_server_open(qwen3_tts::Qwen3TTS &tts, const std::vector<float> &speaker_
             if (q.has_top_k) t.params.top_k = q.top_k;
             if (q.has_repetition_penalty) t.params.repetition_penalty = q.repetition_penalty;
             if (q.has_max_tokens) t.params.max_audio_tokens = q.max_tokens;
+            if (q.has_sample_rate) t.params.output_sample_rate = q.sample_rate;
             std::string why;
             if (q.has_speaker) {
                 t.speaker_embedding = load_embedding(q.speaker);
@@ -400,6 +405,7 @@ int main(int argc, char **argv) {
             else if (arg == "--vocoder-chunk") { if (!(v = need(i, "vocoder-chunk value"))) return 1; vocoder_chunk = std::stoi(v); }
             else if (arg == "--batch") { if (!(v = need(i, "batch value"))) return 1; batch = std::max(1, std::stoi(v)); }
             else if (arg == "--queue-open") { if (!(v = need(i, "queue-open value"))) return 1; queue_open = std::max(1, std::stoi(v)); }
+            else if (arg == "--sample-rate") { if (!(v = need(i, "sample-rate value"))) return 1; params.output_sample_rate = std::stoi(v); }
             else if (arg == "--queue") { if (!(v = need(i, "queue value"))) return 1; queue = std::max(1, std::stoi(v)); }
             else {
                 fprintf(stderr, "Error: unknown argument: %s\n", arg.c_str());
@@ -447,12 +453,12 @@ int main(int argc, char **argv) {
         return 1;
     }
     fprintf(stderr, "\n");
-    if (!qwen3_tts::save_audio_file(output_file, result.audio, result.sample_rate)) {
+    if (!qwen3_tts::save_audio_file(output_file, result)) {
         fprintf(stderr, "Error: failed to save output file: %s\n", output_file.c_str());
         return 1;
     }
     fprintf(stderr, "Output saved to: %s\n", output_file.c_str());
-    fprintf(stderr, "Audio duration: %.2f seconds\n", (float)result.audio.size() / result.sample_rate);
+    fprintf(stderr, "Audio duration: %.2f seconds\n", (float)result.num_samples() / result.sample_rate);
     if (params.print_timing) {
         fprintf(stderr, "\nTiming:\n");
         fprintf(stderr, "  Load:      %6lld ms\n", (long long)result.t_load_ms);

@@ -71,7 +71,7 @@ struct MemSampler {
 
 // Timing / RTF / memory report, format of qwen3_tts.cpp:536-561
 void print_report(const tts_result &r) {
-    const double audio_sec = r.sample_rate > 0 ? (double)r.audio.size() / (double)r.sample_rate : 0.0;
+    const double audio_sec = r.sample_rate > 0 ? (double)r.num_samples() / (double)r.sample_rate : 0.0;
     const double wall_sec = (double)r.t_total_ms / 1000.0;
     const double rtf = audio_sec > 0.0 ? wall_sec / audio_sec : 0.0;
     const double xrt = wall_sec > 0.0 ? audio_sec / wall_sec : 0.0;
@@ -103,8 +103,90 @@ constexpr int32_t kPrefillLen = 10;   // prefill rows with a speaker row (tts_tr
 constexpr int32_t kSampleRate = 24000;
 constexpr int32_t kQueueTick = 12;   // synthesize_queue without a stream interval: frames per delivery tick
 
+// ---- the output stage (tts_params::output_sample_rate > 0): the utterance's samples come back from the device as
+// s16 at the asked rate (tts_result::pcm16), through q3t_vocoder_decode_out or the _out stream pushes; audio stays empty
+bool rate_ok(int32_t rate, int32_t vocoder_chunk, std::string &why) {
+    if (rate == 0) return true;
+    if (q3t_pcm_num_samples(0, rate, 0) < 0) {
+        why = "sample rate " + std::to_string(rate) + " is not supported (supported: 8000, 12000, 16000, 22050, 24000, "
+              "32000, 44100, 48000)";
+        return false;
+    }
+    if (vocoder_chunk > 0) { why = "a sample rate needs the whole-utterance vocoder (vocoder chunk 0)"; return false; }
+    return true;
+}
+
+// a fresh or reset stream takes the utterance's rate, or drops the one of the utterance that held it before
+bool set_stream_rate(q3t_voc_stream *v, int32_t rate) {
+    const q3t_pcm_spec spec = {rate, Q3T_PCM_S16};
+    return q3t_vocoder_stream_set_output(v, rate > 0 ? &spec : nullptr) == Q3T_OK;
+}
+
+// one stream's share of an output push: n frames (0 with final: the filter's tail alone), its s16 appended to *pcm
+struct OutPiece {
+    q3t_voc_stream *st = nullptr;
+    const int32_t *codes = nullptr;
+    int32_t n = 0, final = 0, rate = 0;
+    std::vector<int16_t> *pcm = nullptr;   // one piece per vector and call
+};
+
+// ONE q3t_vocoder_stream_push_batch_out over the pieces; on an error no stream has moved and no sample is kept
+bool push_out_pieces(q3t_ctx *ctx, const std::vector<OutPiece> &pc, std::string &err) {
+    const size_t k = pc.size();
+    if (k == 0) return true;
+    std::vector<q3t_voc_stream *> st(k);
+    std::vector<const int32_t *> cp(k);
+    std::vector<int32_t> nf(k), fin(k);
+    std::vector<void *> out(k);
+    std::vector<int64_t> cap(k), got(k, 0);
+    std::vector<size_t> at(k);
+    for (size_t j = 0; j < k; ++j) {
+        const OutPiece &q = pc[j];
+        st[j] = q.st; cp[j] = q.codes; nf[j] = q.n; fin[j] = q.final;
+        const int64_t in_total = q3t_vocoder_num_samples(ctx, q3t_vocoder_stream_frames(q.st) + q.n, Q3T_VOCODER_FULL);
+        const int64_t n = q3t_pcm_num_samples(in_total, q.rate, q.final) - q3t_vocoder_stream_out_samples(q.st);
+        if (in_total < 0 || n < 0) { err = "bad sample count of a vocoder stream"; return false; }
+        at[j] = q.pcm->size();
+        q.pcm->resize(at[j] + (size_t)n + 1);   // (+ 1: a push of no samples still gets a pointer)
+        out[j] = q.pcm->data() + at[j];
+        cap[j] = n * 2;
+    }
+    const int rc = q3t_vocoder_stream_push_batch_out(st.data(), (int32_t)k, cp.data(), nf.data(), fin.data(), out.data(),
+                                                     cap.data(), got.data());
+    for (size_t j = 0; j < k; ++j) pc[j].pcm->resize(at[j] + (size_t)(rc == Q3T_OK ? got[j] : 0));
+    if (rc != Q3T_OK) err = q3t_error();
+    return rc == Q3T_OK;
+}
+
+// an utterance decoded whole: f32 at 24 kHz into r.audio (FULL, or vocoder_chunk-long chunks), or with a rate the
+// device's s16 at that rate into r.pcm16
+bool decode_utterance(q3t_ctx *ctx, const int32_t *codes, int32_t nf, int32_t vocoder_chunk, int32_t rate, tts_result &r) {
+    int64_t got = 0;
+    int rc;
+    if (rate > 0) {
+        const q3t_pcm_spec spec = {rate, Q3T_PCM_S16};
+        const int64_t n = q3t_pcm_num_samples(q3t_vocoder_num_samples(ctx, nf, Q3T_VOCODER_FULL), rate, 1);
+        r.pcm16.resize((size_t)std::max<int64_t>(n, 0) + 1);
+        rc = q3t_vocoder_decode_out(ctx, codes, nf, Q3T_VOCODER_FULL, &spec, r.pcm16.data(), std::max<int64_t>(n, 0) * 2, &got);
+        r.pcm16.resize(rc == Q3T_OK ? (size_t)got : 0);
+        return rc == Q3T_OK;
+    }
+    if (vocoder_chunk > 0) {
+        r.audio.resize((size_t)nf * 1920);
+        rc = q3t_vocoder_decode_chunked(ctx, codes, nf, 16, vocoder_chunk, r.audio.data(), &got);
+    } else {
+        r.audio.resize((size_t)std::max<int64_t>(q3t_vocoder_num_samples(ctx, nf, Q3T_VOCODER_FULL), 0));
+        rc = q3t_vocoder_decode(ctx, codes, nf, Q3T_VOCODER_FULL, r.audio.data(), &got);
+    }
+    if (rc != Q3T_OK) return false;
+    r.audio.resize((size_t)got);
+    return true;
+}
+
 struct StreamState {
     q3t_ctx *ctx = nullptr;
+    int32_t rate = 0;                        // > 0: the stream has an output spec, the pushes fill *pcm16
+    std::vector<int16_t> *pcm16 = nullptr;
     q3t_voc_stream *voc = nullptr;   // set: full_stream_cb pushes into it
     int32_t chunk = 0;
     std::vector<float> *audio = nullptr;
@@ -135,6 +217,13 @@ int full_stream_cb(void *user, int32_t /*utt*/, const int32_t *codes, int32_t n_
     auto *s = static_cast<StreamState *>(user);
     if (n_frames <= 0) return 1;
     const int64_t t0 = now_ms();
+    if (s->rate > 0) {
+        OutPiece q;
+        q.st = s->voc; q.codes = codes; q.n = n_frames; q.rate = s->rate; q.pcm = s->pcm16;
+        if (!push_out_pieces(s->ctx, {q}, s->error_msg)) { s->error = true; return 0; }
+        s->decode_ms += now_ms() - t0;
+        return 1;
+    }
     const int64_t total = q3t_vocoder_num_samples(s->ctx, q3t_vocoder_stream_frames(s->voc) + n_frames, Q3T_VOCODER_FULL);
     const int64_t cap = total - q3t_vocoder_stream_samples(s->voc);
     const size_t at = s->audio->size();
@@ -158,6 +247,7 @@ int full_stream_cb(void *user, int32_t /*utt*/, const int32_t *codes, int32_t n_
 struct BatchStreamState {
     q3t_ctx *ctx = nullptr;
     std::vector<q3t_voc_stream *> voc;       // per utterance
+    std::vector<int32_t> rate;               // per utterance: > 0, its stream has an output spec and fills pcm16
     std::vector<tts_result> *out = nullptr;  // per utterance: audio appended in order
     struct Piece { int32_t utt = 0, n = 0; std::vector<int32_t> codes; };
     std::vector<Piece> pending;
@@ -179,6 +269,19 @@ struct BatchStreamState {
         if (error) return false;
         if (pending.empty()) return true;
         const int64_t t0 = now_ms();
+        // the pieces of utterances with a sample rate go through the output stage, in a call of their own
+        std::vector<OutPiece> op;
+        std::vector<Piece> plain;
+        for (Piece &q : pending) {
+            if (rate[q.utt] <= 0) { plain.push_back(std::move(q)); continue; }
+            OutPiece o;
+            o.st = voc[q.utt]; o.codes = q.codes.data(); o.n = q.n; o.rate = rate[q.utt]; o.pcm = &(*out)[q.utt].pcm16;
+            op.push_back(o);
+        }
+        std::string why;
+        if (!push_out_pieces(ctx, op, why)) return fail(why);
+        pending.swap(plain);
+        if (pending.empty()) { decode_ms += now_ms() - t0; return true; }
         const size_t k = pending.size();
         std::vector<q3t_voc_stream *> st(k);
         std::vector<const int32_t *> cp(k);
@@ -203,6 +306,22 @@ struct BatchStreamState {
         for (size_t j = 0; j < k; ++j) (*out)[pending[j].utt].audio.resize(at[j] + (size_t)(rc == Q3T_OK ? got[j] : 0));
         if (rc != Q3T_OK) return fail(q3t_error());
         pending.clear();
+        decode_ms += now_ms() - t0;
+        return true;
+    }
+    // after the generation: the filter's tail of every utterance with a sample rate, in one call
+    bool finish() {
+        if (error) return false;
+        const int64_t t0 = now_ms();
+        std::vector<OutPiece> op;
+        for (size_t u = 0; u < voc.size(); ++u) {
+            if (rate[u] <= 0 || q3t_vocoder_stream_frames(voc[u]) <= 0) continue;
+            OutPiece o;
+            o.st = voc[u]; o.final = 1; o.rate = rate[u]; o.pcm = &(*out)[u].pcm16;
+            op.push_back(o);
+        }
+        std::string why;
+        if (!push_out_pieces(ctx, op, why)) return fail(why);
         decode_ms += now_ms() - t0;
         return true;
     }
@@ -238,6 +357,7 @@ struct QueueSynthState {
     std::vector<std::vector<int32_t>> codes;        // per utterance (no stream interval)
     std::vector<q3t_voc_stream *> pool, free_list;  // every stream opened; those no utterance holds
     std::vector<q3t_voc_stream *> mine;             // per utterance
+    std::vector<int32_t> rate;                      // per utterance: tts_params::output_sample_rate
     const std::function<void(int32_t, const tts_result &)> *on_result = nullptr;
     std::string error_msg;
 
@@ -248,8 +368,8 @@ struct QueueSynthState {
         tts_result &r = (*out)[u];
         r.success = ok;
         r.error_msg = msg;
-        if (!ok) r.audio.clear();
-        r.sample_rate = kSampleRate;
+        if (!ok) { r.audio.clear(); r.pcm16.clear(); }
+        r.sample_rate = u < (int32_t)rate.size() && rate[u] > 0 ? rate[u] : kSampleRate;
         r.t_total_ms = now_ms() - t0;
         r.t_decode_ms = u < (int32_t)decode_ms.size() ? (int64_t)(decode_ms[u] + 0.5) : 0;
         r.t_generate_ms = std::max<int64_t>(r.t_total_ms - r.t_decode_ms, 0);   // includes the wait for a slot
@@ -271,25 +391,12 @@ struct QueueSynthState {
         if (free_list.empty()) { error_msg = "more utterances in flight than vocoder streams in the pool"; return false; }
         mine[u] = free_list.back();
         free_list.pop_back();
-        if (q3t_vocoder_stream_reset(mine[u]) == Q3T_OK) return true;
+        if (q3t_vocoder_stream_reset(mine[u]) == Q3T_OK && set_stream_rate(mine[u], rate[u])) return true;
         error_msg = "Failed to reset the vocoder stream: " + q3t_error();
         return false;
     }
     bool decode_whole(int32_t u) {
-        tts_result &r = (*out)[u];
-        const int32_t nf = n_frames[u];
-        int64_t got = 0;
-        int rc;
-        if (vocoder_chunk > 0) {
-            r.audio.resize((size_t)nf * 1920);
-            rc = q3t_vocoder_decode_chunked(ctx, codes[u].data(), nf, 16, vocoder_chunk, r.audio.data(), &got);
-        } else {
-            r.audio.resize((size_t)std::max<int64_t>(q3t_vocoder_num_samples(ctx, nf, Q3T_VOCODER_FULL), 0));
-            rc = q3t_vocoder_decode(ctx, codes[u].data(), nf, Q3T_VOCODER_FULL, r.audio.data(), &got);
-        }
-        if (rc != Q3T_OK) return false;
-        r.audio.resize((size_t)got);
-        return true;
+        return decode_utterance(ctx, codes[u].data(), n_frames[u], vocoder_chunk, rate[u], (*out)[u]);
     }
     // one callback: false aborts the queue (error_msg set)
     bool deliver(int32_t n, const int32_t *utt, const int32_t *const *cp, const int32_t *nf, const int32_t *fin) {
@@ -300,9 +407,23 @@ struct QueueSynthState {
         std::vector<float *> pp;
         std::vector<int64_t> cap;
         std::vector<size_t> at;
+        std::vector<OutPiece> op;   // the pieces of utterances with a sample rate: a call of their own
+        std::vector<int32_t> ou;
         for (int32_t i = 0; i < n; ++i) {
             const int32_t u = utt[i];
             if (u < 0 || u >= (int32_t)out->size() || reported[u]) { error_msg = "unexpected delivery from the queue"; return false; }
+            if (stream_full && rate[u] > 0 && (nf[i] > 0 || (fin[i] && mine[u]))) {
+                // its frames through the output stage; the final delivery also brings the filter's tail (alone when
+                // it carries no frame)
+                if (!mine[u] && !take_stream(u)) return false;
+                n_frames[u] += std::max(nf[i], 0);
+                OutPiece o;
+                o.st = mine[u]; o.codes = cp[i]; o.n = std::max(nf[i], 0); o.final = fin[i] ? 1 : 0; o.rate = rate[u];
+                o.pcm = &(*out)[u].pcm16;
+                op.push_back(o);
+                ou.push_back(u);
+                continue;
+            }
             if (nf[i] <= 0) continue;
             n_frames[u] += nf[i];
             if (!stream_full) { codes[u].insert(codes[u].end(), cp[i], cp[i] + (size_t)nf[i] * 16); continue; }
@@ -323,11 +444,16 @@ struct QueueSynthState {
             for (size_t j = 0; j < st.size(); ++j) (*out)[pu[j]].audio.resize(at[j] + (size_t)(rc == Q3T_OK ? got[j] : 0));
             if (rc != Q3T_OK) { error_msg = "Vocoder stream decode failed: " + q3t_error(); return false; }
         }
+        {
+            std::string why;
+            if (!push_out_pieces(ctx, op, why)) { error_msg = "Vocoder stream decode failed: " + why; return false; }
+            for (size_t j = 0; j < op.size(); ++j) { pu.push_back(ou[j]); pn.push_back(op[j].n); }
+        }
         // the batched push serves all its pieces at once: its time is split over them by their frames
         const double push_ms = (double)(now_ms() - td);
         int64_t pushed = 0;
         for (int32_t f : pn) pushed += f;
-        for (size_t j = 0; j < pu.size(); ++j) decode_ms[pu[j]] += push_ms * pn[j] / (double)pushed;
+        for (size_t j = 0; j < pu.size(); ++j) if (pushed > 0) decode_ms[pu[j]] += push_ms * pn[j] / (double)pushed;
         for (int32_t i = 0; i < n; ++i) {
             if (!fin[i]) continue;
             const int32_t u = utt[i];
@@ -364,6 +490,7 @@ struct OpenQueueState {
     const std::function<void(int32_t, const tts_result &)> *on_result = nullptr;
     struct Live {
         int32_t request = 0;              // the caller's number
+        int32_t rate = 0;                 // tts_params::output_sample_rate of the request
         int32_t n_frames = 0;
         double decode_ms = 0;
         int64_t t0 = 0;
@@ -386,8 +513,8 @@ struct OpenQueueState {
         tts_result &r = l.r;
         r.success = ok;
         r.error_msg = msg;
-        if (!ok) r.audio.clear();
-        r.sample_rate = kSampleRate;
+        if (!ok) { r.audio.clear(); r.pcm16.clear(); }
+        r.sample_rate = l.rate > 0 ? l.rate : kSampleRate;
         r.t_total_ms = now_ms() - l.t0;
         r.t_decode_ms = (int64_t)(l.decode_ms + 0.5);
         r.t_generate_ms = std::max<int64_t>(r.t_total_ms - r.t_decode_ms, 0);
@@ -421,6 +548,8 @@ struct OpenQueueState {
                 refuse(no, "a speaker embedding must be empty or hold one value per hidden channel");
                 continue;
             }
+            std::string bad_rate;
+            if (!rate_ok(r.params.output_sample_rate, vocoder_chunk, bad_rate)) { refuse(no, bad_rate); continue; }
             const int64_t t = now_ms();
             std::vector<int32_t> ids = tokenizer->encode_for_tts(r.text);
             const int64_t t_tok = now_ms() - t;
@@ -440,6 +569,7 @@ struct OpenQueueState {
             a.key = (uint64_t)(next_id + m);
             Live &l = live[next_id + m];
             l.request = no;
+            l.rate = r.params.output_sample_rate;
             l.t0 = now_ms();
             l.r.t_tokenize_ms = t_tok;
             ++m;
@@ -454,19 +584,15 @@ struct OpenQueueState {
         return 1;
     }
     bool decode_whole(Live &l) {
-        tts_result &r = l.r;
-        int64_t got = 0;
-        int rc;
-        if (vocoder_chunk > 0) {
-            r.audio.resize((size_t)l.n_frames * 1920);
-            rc = q3t_vocoder_decode_chunked(ctx, l.codes.data(), l.n_frames, 16, vocoder_chunk, r.audio.data(), &got);
-        } else {
-            r.audio.resize((size_t)std::max<int64_t>(q3t_vocoder_num_samples(ctx, l.n_frames, Q3T_VOCODER_FULL), 0));
-            rc = q3t_vocoder_decode(ctx, l.codes.data(), l.n_frames, Q3T_VOCODER_FULL, r.audio.data(), &got);
-        }
-        if (rc != Q3T_OK) return false;
-        r.audio.resize((size_t)got);
-        return true;
+        return decode_utterance(ctx, l.codes.data(), l.n_frames, vocoder_chunk, l.rate, l.r);
+    }
+    bool take_stream(Live &l) {
+        if (free_list.empty()) { error_msg = "more utterances in flight than vocoder streams in the pool"; return false; }
+        l.vs = free_list.back();
+        free_list.pop_back();
+        if (q3t_vocoder_stream_reset(l.vs) == Q3T_OK && set_stream_rate(l.vs, l.rate)) return true;
+        error_msg = "Failed to reset the vocoder stream: " + q3t_error();
+        return false;
     }
     // one delivery callback (QueueSynthState::deliver over the live table): false aborts the queue (error_msg set)
     bool deliver(int32_t n, const int32_t *utt, const int32_t *const *cp, const int32_t *nf, const int32_t *fin) {
@@ -478,19 +604,27 @@ struct OpenQueueState {
         std::vector<float *> pp;
         std::vector<int64_t> cap;
         std::vector<size_t> at;
+        std::vector<OutPiece> op;
+        std::vector<Live *> ol;
         for (int32_t i = 0; i < n; ++i) {
             auto it = live.find(utt[i]);
             if (it == live.end()) { error_msg = "unexpected delivery from the queue"; return false; }
             Live &l = it->second;
+            if (stream_full && l.rate > 0 && (nf[i] > 0 || (fin[i] && l.vs))) {
+                // as QueueSynthState::deliver: the output stage's pieces, the tail with the final delivery
+                if (!l.vs && !take_stream(l)) return false;
+                l.n_frames += std::max(nf[i], 0);
+                OutPiece o;
+                o.st = l.vs; o.codes = cp[i]; o.n = std::max(nf[i], 0); o.final = fin[i] ? 1 : 0; o.rate = l.rate;
+                o.pcm = &l.r.pcm16;
+                op.push_back(o);
+                ol.push_back(&l);
+                continue;
+            }
             if (nf[i] <= 0) continue;
             l.n_frames += nf[i];
             if (!stream_full) { l.codes.insert(l.codes.end(), cp[i], cp[i] + (size_t)nf[i] * 16); continue; }
-            if (!l.vs) {
-                if (free_list.empty()) { error_msg = "more utterances in flight than vocoder streams in the pool"; return false; }
-                l.vs = free_list.back();
-                free_list.pop_back();
-                if (q3t_vocoder_stream_reset(l.vs) != Q3T_OK) { error_msg = "Failed to reset the vocoder stream: " + q3t_error(); return false; }
-            }
+            if (!l.vs && !take_stream(l)) return false;
             const int64_t total = q3t_vocoder_num_samples(ctx, q3t_vocoder_stream_frames(l.vs) + nf[i], Q3T_VOCODER_FULL);
             const int64_t c = total - q3t_vocoder_stream_samples(l.vs);
             if (total < 0 || c < 0) { error_msg = "bad sample count of a vocoder stream"; return false; }
@@ -507,10 +641,15 @@ struct OpenQueueState {
             for (size_t j = 0; j < st.size(); ++j) pl[j]->r.audio.resize(at[j] + (size_t)(rc == Q3T_OK ? got[j] : 0));
             if (rc != Q3T_OK) { error_msg = "Vocoder stream decode failed: " + q3t_error(); return false; }
         }
+        {
+            std::string why;
+            if (!push_out_pieces(ctx, op, why)) { error_msg = "Vocoder stream decode failed: " + why; return false; }
+            for (size_t j = 0; j < op.size(); ++j) { pl.push_back(ol[j]); pn.push_back(op[j].n); }
+        }
         const double push_ms = (double)(now_ms() - td);
         int64_t pushed = 0;
         for (int32_t f : pn) pushed += f;
-        for (size_t j = 0; j < pl.size(); ++j) pl[j]->decode_ms += push_ms * pn[j] / (double)pushed;
+        for (size_t j = 0; j < pl.size(); ++j) if (pushed > 0) pl[j]->decode_ms += push_ms * pn[j] / (double)pushed;
         for (int32_t i = 0; i < n; ++i) {
             if (!fin[i]) continue;
             auto it = live.find(utt[i]);
@@ -708,6 +847,8 @@ tts_result Qwen3TTS::synthesize_internal(const std::string &text, const float *s
         if (tokens.size() > 10) fprintf(stderr, "...");
         fprintf(stderr, "\n");
     }
+    const int32_t rate = params.output_sample_rate;
+    if (!rate_ok(rate, vocoder_chunk_, result.error_msg)) return result;
     const int64_t t_gen = now_ms();
     const int32_t max_len = std::max(params.max_audio_tokens, 0);
     if (!ensure_slots(1, std::max(max_len, 1))) { result.error_msg = "Failed to generate speech codes: " + error_msg_; return result; }
@@ -727,9 +868,16 @@ tts_result Qwen3TTS::synthesize_internal(const std::string &text, const float *s
     st.ctx = ctx_;
     st.chunk = vocoder_chunk_;
     st.audio = &result.audio;
+    st.rate = rate;
+    st.pcm16 = &result.pcm16;
     const bool stream_full = stream_full_ > 0 && vocoder_chunk_ <= 0 && max_len > 0;
     if (stream_full && q3t_vocoder_stream_open(ctx_, max_len, &st.voc) != Q3T_OK) {
         result.error_msg = "Failed to open the vocoder stream: " + q3t_error();
+        return result;
+    }
+    if (st.voc && rate > 0 && !set_stream_rate(st.voc, rate)) {
+        result.error_msg = "Failed to open the vocoder stream: " + q3t_error();
+        q3t_vocoder_stream_close(st.voc);
         return result;
     }
     int rc;
@@ -747,6 +895,13 @@ tts_result Qwen3TTS::synthesize_internal(const std::string &text, const float *s
         st.error_msg = "the callback saw " + std::to_string(q3t_vocoder_stream_frames(st.voc)) + " of " +
                        std::to_string(n_frames) + " generated frames";
     }
+    if (st.voc && rate > 0 && rc == Q3T_OK && !st.error && n_frames > 0) {   // the filter's tail
+        OutPiece q;
+        q.st = st.voc; q.final = 1; q.rate = rate; q.pcm = &result.pcm16;
+        const int64_t t0 = now_ms();
+        if (!push_out_pieces(ctx_, {q}, st.error_msg)) st.error = true;
+        st.decode_ms += now_ms() - t0;
+    }
     if (st.voc) q3t_vocoder_stream_close(st.voc);
     if (rc != Q3T_OK) { result.error_msg = "Failed to generate speech codes: " + q3t_error(); return result; }
     if (st.error) {
@@ -758,7 +913,12 @@ tts_result Qwen3TTS::synthesize_internal(const std::string &text, const float *s
     if (params.print_progress) fprintf(stderr, "Speech codes generated: %d frames x %d codebooks\n", n_frames, 16);
     if (n_frames == 0) { result.error_msg = "No speech codes generated"; return result; }
     const int64_t t_dec = now_ms();
-    if (vocoder_chunk_ <= 0 && !stream_full) {
+    if (vocoder_chunk_ <= 0 && !stream_full && rate > 0) {
+        if (!decode_utterance(ctx_, codes.data(), n_frames, 0, rate, result)) {
+            result.error_msg = "Failed to decode speech codes: " + q3t_error();
+            return result;
+        }
+    } else if (vocoder_chunk_ <= 0 && !stream_full) {
         const int64_t n = q3t_vocoder_num_samples(ctx_, n_frames, Q3T_VOCODER_FULL);
         result.audio.resize((size_t)std::max<int64_t>(n, 0));
         int64_t got = 0;
@@ -768,7 +928,7 @@ tts_result Qwen3TTS::synthesize_internal(const std::string &text, const float *s
         }
         result.audio.resize((size_t)got);
     }
-    result.sample_rate = kSampleRate;
+    result.sample_rate = rate > 0 ? rate : kSampleRate;
     result.t_decode_ms = st.decode_ms + (now_ms() - t_dec);
     mem("synth/after-decode");
     result.success = true;
@@ -803,6 +963,7 @@ bool Qwen3TTS::check_request(const tts_request &r, std::string &error) const {
     else if (!r.speaker_embedding.empty() && (int32_t)r.speaker_embedding.size() != hidden_)
         error = "speaker embedding holds " + std::to_string(r.speaker_embedding.size()) + " values, the model needs " +
                 std::to_string(hidden_);
+    else rate_ok(r.params.output_sample_rate, vocoder_chunk_, error);
     return error.empty();
 }
 
@@ -850,6 +1011,9 @@ std::vector<tts_result> Qwen3TTS::batch_requests(const std::vector<tts_request> 
     for (const tts_request &r : requests)
         if (!r.speaker_embedding.empty() && (int32_t)r.speaker_embedding.size() != hidden_)
             return fail_all("a speaker embedding must be empty or hold one value per hidden channel");
+    std::string bad_rate;
+    for (const tts_request &r : requests)
+        if (!rate_ok(r.params.output_sample_rate, vocoder_chunk_, bad_rate)) return fail_all(bad_rate);
     const int64_t t0 = now_ms();
     std::vector<std::vector<int32_t>> toks(n);
     std::vector<const int32_t *> tp(n);
@@ -879,48 +1043,47 @@ std::vector<tts_result> Qwen3TTS::batch_requests(const std::vector<tts_request> 
         bs.ctx = ctx_;
         bs.out = &out;
         bs.voc.assign(n, nullptr);
-        for (int32_t i = 0; i < n; ++i)
-            if (q3t_vocoder_stream_open(ctx_, max_len, &bs.voc[i]) != Q3T_OK)
+        bs.rate.assign(n, 0);
+        for (int32_t i = 0; i < n; ++i) {
+            bs.rate[i] = requests[i].params.output_sample_rate;
+            if (q3t_vocoder_stream_open(ctx_, max_len, &bs.voc[i]) != Q3T_OK || !set_stream_rate(bs.voc[i], bs.rate[i]))
                 return fail_all("Failed to open the vocoder stream: " + q3t_error());
+        }
     }
     const int64_t tg = now_ms();
     const int rc_gen = q3t_generate_utt(ctx_, n, tp.data(), nt.data(), spk.data(), &p, up.data(), codes.data(), nf.data(),
                                         stream_full ? batch_full_stream_cb : nullptr, &bs, stream_full ? stream_full_ : 0);
     if (rc_gen != Q3T_OK) {
-        for (auto &r : out) r.audio.clear();
+        for (auto &r : out) { r.audio.clear(); r.pcm16.clear(); }
         return fail_all("Failed to generate speech codes: " + q3t_error());
     }
-    if (stream_full) bs.flush();   // the remainders
+    if (stream_full && bs.flush()) bs.finish();   // the remainders, then the output stage's tails
     const int64_t gen_ms = now_ms() - tg - bs.decode_ms;
     for (int32_t i = 0; i < n; ++i) {
         tts_result &r = out[i];
         r.t_generate_ms = gen_ms;
-        if (nf[i] == 0) { r.error_msg = "No speech codes generated"; r.audio.clear(); continue; }
+        const int32_t rate = requests[i].params.output_sample_rate;
+        if (nf[i] == 0) { r.error_msg = "No speech codes generated"; r.audio.clear(); r.pcm16.clear(); continue; }
         if (stream_full) {
             if (!bs.error && q3t_vocoder_stream_frames(bs.voc[i]) != nf[i])
                 bs.fail("the callback saw " + std::to_string(q3t_vocoder_stream_frames(bs.voc[i])) + " of " +
                         std::to_string(nf[i]) + " generated frames");
-            if (bs.error) { r.error_msg = "Vocoder stream decode failed: " + bs.error_msg; r.audio.clear(); continue; }
+            if (bs.error) { r.error_msg = "Vocoder stream decode failed: " + bs.error_msg; r.audio.clear(); r.pcm16.clear(); continue; }
             r.t_decode_ms = bs.decode_ms;
-            r.sample_rate = kSampleRate;
+            r.sample_rate = rate > 0 ? rate : kSampleRate;
             r.success = true;
             continue;
         }
         const int32_t *c = codes.data() + (size_t)i * max_len * 16;
         const int64_t td = now_ms();
-        int64_t got = 0;
-        int rc;
-        if (vocoder_chunk_ > 0) {
-            r.audio.resize((size_t)nf[i] * 1920);
-            rc = q3t_vocoder_decode_chunked(ctx_, c, nf[i], 16, vocoder_chunk_, r.audio.data(), &got);
-        } else {
-            r.audio.resize((size_t)std::max<int64_t>(q3t_vocoder_num_samples(ctx_, nf[i], Q3T_VOCODER_FULL), 0));
-            rc = q3t_vocoder_decode(ctx_, c, nf[i], Q3T_VOCODER_FULL, r.audio.data(), &got);
+        if (!decode_utterance(ctx_, c, nf[i], vocoder_chunk_, rate, r)) {
+            r.error_msg = "Failed to decode speech codes: " + q3t_error();
+            r.audio.clear();
+            r.pcm16.clear();
+            continue;
         }
-        if (rc != Q3T_OK) { r.error_msg = "Failed to decode speech codes: " + q3t_error(); r.audio.clear(); continue; }
-        r.audio.resize((size_t)got);
         r.t_decode_ms = now_ms() - td;
-        r.sample_rate = kSampleRate;
+        r.sample_rate = rate > 0 ? rate : kSampleRate;
         r.success = true;
     }
     const int64_t total = now_ms() - t0;
@@ -963,6 +1126,11 @@ std::vector<tts_result> Qwen3TTS::queue_requests(const std::vector<tts_request> 
     for (const tts_request &r : requests)
         if (!r.speaker_embedding.empty() && (int32_t)r.speaker_embedding.size() != hidden_)
             return fail_rest("a speaker embedding must be empty or hold one value per hidden channel");
+    std::string bad_rate;
+    for (const tts_request &r : requests)
+        if (!rate_ok(r.params.output_sample_rate, vocoder_chunk_, bad_rate)) return fail_rest(bad_rate);
+    qs.rate.resize(n);
+    for (int32_t i = 0; i < n; ++i) qs.rate[i] = requests[i].params.output_sample_rate;
     std::vector<std::vector<int32_t>> toks(n);
     std::vector<const int32_t *> tp(n);
     std::vector<int32_t> nt(n), nf(n);
@@ -1118,6 +1286,28 @@ bool save_audio_file(const std::string &path, const std::vector<float> &samples,
                     (pcm.empty() || fwrite(pcm.data(), 2, pcm.size(), f) == pcm.size());
     fclose(f);
     return ok;
+}
+
+bool save_audio_file(const std::string &path, const std::vector<int16_t> &pcm, int sample_rate) {
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) { fprintf(stderr, "ERROR: Cannot create WAV file: %s\n", path.c_str()); return false; }
+    const uint16_t ch = 1, bits = 16, block = ch * bits / 8, fmt = 1;
+    const uint32_t sr = (uint32_t)sample_rate, byte_rate = sr * block, data = (uint32_t)(pcm.size() * block);
+    const uint32_t riff = 36 + data, fmt_size = 16;
+    std::vector<uint8_t> h;
+    auto put = [&](const void *p, size_t n) { h.insert(h.end(), (const uint8_t *)p, (const uint8_t *)p + n); };
+    put("RIFF", 4); put(&riff, 4); put("WAVE", 4);
+    put("fmt ", 4); put(&fmt_size, 4); put(&fmt, 2); put(&ch, 2); put(&sr, 4); put(&byte_rate, 4); put(&block, 2);
+    put(&bits, 2);
+    put("data", 4); put(&data, 4);
+    const bool ok = fwrite(h.data(), 1, h.size(), f) == h.size() &&
+                    (pcm.empty() || fwrite(pcm.data(), 2, pcm.size(), f) == pcm.size());
+    fclose(f);
+    return ok;
+}
+
+bool save_audio_file(const std::string &path, const tts_result &r) {
+    return r.pcm16.empty() ? save_audio_file(path, r.audio, r.sample_rate) : save_audio_file(path, r.pcm16, r.sample_rate);
 }
 
 }  // namespace qwen3_tts

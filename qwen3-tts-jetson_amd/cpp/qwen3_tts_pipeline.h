@@ -20,11 +20,19 @@ struct tts_params {
     bool print_progress = false;
     bool print_timing = true;
     float repetition_penalty = 1.05f;
+    // MI355X extension.  0: float32 at 24 kHz in tts_result::audio, as the reference.  One of 8000, 12000, 16000,
+    // 22050, 24000, 32000, 44100, 48000: the device's output stage (q3t_vocoder_decode_out / _stream_push_out /
+    // _stream_push_batch_out) delivers s16 at that rate in tts_result::pcm16 and audio stays empty; no host
+    // conversion runs.  Needs the whole-utterance vocoder (vocoder_chunk() == 0); in a tts_request it is the
+    // request's own
+    int32_t output_sample_rate = 0;
 };
 
 struct tts_result {
     std::vector<float> audio;
-    int32_t sample_rate = 24000;
+    int32_t sample_rate = 24000;      // the delivered rate: tts_params::output_sample_rate when one was asked for
+    std::vector<int16_t> pcm16;       // the device s16 stream at sample_rate, in place of audio, when one was asked for
+    size_t num_samples() const { return pcm16.empty() ? audio.size() : pcm16.size(); }
     bool success = false;
     std::string error_msg;
     int64_t t_load_ms = 0;
@@ -95,7 +103,7 @@ public:
 
     // false with the reason when the engine would refuse this request's values (language id at or above the codec
     // vocabulary, top_k < 0, a repetition penalty that is not finite and > 0, a temperature that is not finite, an
-    // embedding of the wrong length): such a request fails the whole synthesize_batch / synthesize_queue call it is
+    // embedding of the wrong length, an output_sample_rate the output stage does not have or one beside a chunked vocoder): such a request fails the whole synthesize_batch / synthesize_queue call it is
     // part of, so a server checks each request first and answers it alone.  max_audio_tokens needs no check: the
     // context grows to the longest request
     bool check_request(const tts_request &request, std::string &error) const;
@@ -163,6 +171,10 @@ private:
 bool load_audio_file(const std::string &path, std::vector<float> &samples, int &sample_rate);
 // WAV PCM16 mono, samples clamped to [-1, 1] and scaled by 32767 (qwen3_tts.cpp:708-759)
 bool save_audio_file(const std::string &path, const std::vector<float> &samples, int sample_rate);
+// the same file from s16 samples as they are (the output stage's): no conversion
+bool save_audio_file(const std::string &path, const std::vector<int16_t> &samples, int sample_rate);
+// the result's WAV: pcm16 as it is when the request asked for a sample rate, else audio through the conversion above
+bool save_audio_file(const std::string &path, const tts_result &result);
 // linear resampling used for reference audio (qwen3_tts.cpp:83-101)
 void resample_linear(const float *input, int input_len, int input_rate, std::vector<float> &output, int output_rate);
 

@@ -4,7 +4,8 @@
 //   text<TAB>output.wav<TAB>key=value;...    the same with values of its own for this request
 //
 // Keys of the third field: language (a codec language id, or "nothink"), temperature, top_k, repetition_penalty,
-// max_tokens, speaker (a raw float32 embedding file, loaded like -e).  A request takes the server's command-line values
+// max_tokens, speaker (a raw float32 embedding file, loaded like -e), sample_rate (the rate of this request's WAV: one
+// of 8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000; the device's output stage writes its s16).  A request takes the server's command-line values
 // for every key it does not give.  An empty third field gives none.  A bad field (unknown key, missing '=', malformed
 // or out-of-range number, a key given twice) fails that request alone with the protocol's ERR reply.
 // Header-only and free of the GPU libraries so tests/cpp/test_serve_request.cpp drives it on the CPU.
@@ -23,15 +24,17 @@ struct serve_request {
     std::string text, output;
     // the keys the line gave (has_*) and their values
     bool has_language = false, has_temperature = false, has_top_k = false, has_repetition_penalty = false,
-         has_max_tokens = false, has_speaker = false;
+         has_max_tokens = false, has_speaker = false, has_sample_rate = false;
     int32_t language_id = 2050;   // -1: nothink
     float temperature = 0.0f;
     int32_t top_k = 0;
     float repetition_penalty = 0.0f;
     int32_t max_tokens = 0;
     std::string speaker;          // embedding file
+    int32_t sample_rate = 0;      // Hz, one of the output stage's rates
     bool any() const {
-        return has_language || has_temperature || has_top_k || has_repetition_penalty || has_max_tokens || has_speaker;
+        return has_language || has_temperature || has_top_k || has_repetition_penalty || has_max_tokens || has_speaker ||
+               has_sample_rate;
     }
 };
 
@@ -53,6 +56,12 @@ inline bool parse_float(const std::string &v, float &out) {
     if (errno != 0 || end != v.c_str() + v.size() || !std::isfinite(x)) return false;
     out = x;
     return true;
+}
+// the rates of the output stage (include/q3t_backend.h)
+inline bool known_sample_rate(int32_t r) {
+    for (int32_t k : {8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000})
+        if (r == k) return true;
+    return false;
 }
 }  // namespace serve_detail
 
@@ -100,6 +109,9 @@ inline bool parse_serve_line(const std::string &line, serve_request &r, std::str
             has = &r.has_speaker;
             r.speaker = val;
             ok = !val.empty();
+        } else if (key == "sample_rate") {
+            has = &r.has_sample_rate;
+            ok = serve_detail::parse_int(val, r.sample_rate) && serve_detail::known_sample_rate(r.sample_rate);
         } else {
             error = "unknown request option '" + key + "'";
             return false;

@@ -552,6 +552,88 @@ int32_t q3t_vocoder_stream_last_groups(const q3t_ctx *ctx) {
     return v ? v->stream_last_groups() : -1;
 }
 
+// ---- output stage (pcm_out.h)
+int32_t q3t_pcm_bytes_per_sample(int32_t format) { return q3t::pcm_bytes_per_sample(format); }
+
+int64_t q3t_pcm_num_samples(int64_t n_in_total, int32_t sample_rate, int32_t final) {
+    return q3t::pcm_num_samples(n_in_total, sample_rate, final != 0);
+}
+
+int q3t_pcm_taps(int32_t sample_rate, int32_t *L, int32_t *M, int32_t *K, float *taps, int64_t cap) {
+    GUARD_BEGIN
+    q3t::PcmRate g;
+    std::vector<float> h;
+    if (!q3t::pcm_taps(sample_rate, &g, taps ? &h : nullptr)) {
+        q3t::set_error("output sample rate " + std::to_string(sample_rate) + " is not supported (supported: " +
+                       q3t::pcm_rates_text() + ")");
+        return Q3T_ERR;
+    }
+    if (L) *L = g.L;
+    if (M) *M = g.M;
+    if (K) *K = g.K;
+    if (taps) {
+        if (cap < (int64_t)h.size()) { q3t::set_error("q3t_pcm_taps: cap " + std::to_string(cap) + " < " + std::to_string(h.size()) + " taps"); return Q3T_ERR; }
+        std::copy(h.begin(), h.end(), taps);
+    }
+    return Q3T_OK;
+    GUARD_END
+}
+
+int q3t_vocoder_decode_out(q3t_ctx *ctx, const int32_t *codes, int32_t n_frames, int mode, const q3t_pcm_spec *spec,
+                           void *out, int64_t out_cap_bytes, int64_t *n_samples) {
+    GUARD_BEGIN
+    if (n_samples) *n_samples = 0;
+    CHECK_CTX(ctx);
+    q3t::Vocoder *v = ctx->engine.vocoder();
+    if (!v || !v->loaded()) { q3t::set_error("vocoder not loaded (no tokenizer GGUF given)"); return Q3T_ERR; }
+    if (mode != Q3T_VOCODER_FULL && mode != Q3T_VOCODER_CHUNK40) { q3t::set_error("bad vocoder mode"); return Q3T_ERR; }
+    if (!spec || !n_samples || (n_frames > 0 && !codes)) { q3t::set_error("null argument"); return Q3T_ERR; }
+    q3t::DeviceLock lk(false, ctx->engine.device());   // never beside a persistent grid (devlock.h)
+    const q3t::Vocoder::OutSpec sp{spec->sample_rate, spec->format};
+    return v->decode_out(codes, n_frames, mode, sp, out, out_cap_bytes, n_samples) ? Q3T_OK : Q3T_ERR;
+    GUARD_END
+}
+
+int q3t_vocoder_stream_set_output(q3t_voc_stream *s, const q3t_pcm_spec *spec) {
+    GUARD_BEGIN
+    if (!s) { q3t::set_error("null vocoder stream"); return Q3T_ERR; }
+    q3t::Vocoder::Stream *st = vst(s);
+    q3t::DeviceLock lk(false, st->device);   // as a push: the decoder's stream list is read under the lock
+    q3t::Vocoder::OutSpec sp;
+    if (spec) sp = q3t::Vocoder::OutSpec{spec->sample_rate, spec->format};
+    return st->owner->stream_set_output(st, spec ? &sp : nullptr) ? Q3T_OK : Q3T_ERR;
+    GUARD_END
+}
+
+int q3t_vocoder_stream_push_batch_out(q3t_voc_stream *const *streams, int32_t n_streams, const int32_t *const *codes,
+                                      const int32_t *n_frames, const int32_t *final, void *const *out,
+                                      const int64_t *out_cap_bytes, int64_t *n_samples) {
+    GUARD_BEGIN
+    if (n_samples) for (int32_t j = 0; j < n_streams; ++j) n_samples[j] = 0;
+    if (n_streams <= 0) { q3t::set_error("vocoder stream batch: n_streams must be > 0"); return Q3T_ERR; }
+    if (!streams || !codes || !n_frames || !out || !out_cap_bytes || !n_samples) { q3t::set_error("null argument"); return Q3T_ERR; }
+    for (int32_t j = 0; j < n_streams; ++j)
+        if (!streams[j]) { q3t::set_error("null vocoder stream (entry " + std::to_string(j) + ")"); return Q3T_ERR; }
+    std::vector<int32_t> none;
+    if (!final) { none.assign((size_t)n_streams, 0); final = none.data(); }   // final == NULL: no stream ends
+    q3t::Vocoder::Stream *first = vst(streams[0]);
+    q3t::DeviceLock lk(false, first->device);   // never beside a persistent grid (devlock.h)
+    return first->owner->stream_push_batch_out(n_streams, reinterpret_cast<q3t::Vocoder::Stream *const *>(streams), codes,
+                                               n_frames, final, out, out_cap_bytes, n_samples) ? Q3T_OK : Q3T_ERR;
+    GUARD_END
+}
+
+int q3t_vocoder_stream_push_out(q3t_voc_stream *s, const int32_t *codes, int32_t n_frames, int32_t final, void *out,
+                                int64_t out_cap_bytes, int64_t *n_samples) {
+    int64_t n = 0;
+    const int rc = q3t_vocoder_stream_push_batch_out(&s, 1, &codes, &n_frames, &final, &out, &out_cap_bytes, &n);
+    if (n_samples) *n_samples = n;
+    return rc;
+}
+
+int64_t q3t_vocoder_stream_out_samples(const q3t_voc_stream *s) { return s && cvst(s)->has_out ? cvst(s)->out_samples : -1; }
+int64_t q3t_pcm_out_launches(void) { return q3t::pcm_out_launches(); }
+
 int64_t q3t_vocoder_stream_samples(const q3t_voc_stream *s) { return s ? cvst(s)->samples : -1; }
 int32_t q3t_vocoder_stream_frames(const q3t_voc_stream *s) { return s ? cvst(s)->frames : -1; }
 int32_t q3t_vocoder_stream_halo(const q3t_voc_stream *s) { return s ? cvst(s)->halo : -1; }

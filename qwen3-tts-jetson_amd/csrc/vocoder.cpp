@@ -16,6 +16,8 @@ Vocoder::~Vocoder() {
     for (void *p : scratch_) hipFree(p);
     if (sb_win_) hipFree(sb_win_);
     if (sb_desc_) hipFree(sb_desc_);
+    for (const OutTaps &t : out_taps_) if (t.taps) hipFree(t.taps);
+    for (void *p : {(void *)po_stage_, (void *)po_hist0_, (void *)po_bytes_, (void *)po_desc_}) if (p) hipFree(p);
 }
 
 template <class T>
@@ -821,7 +823,7 @@ void Vocoder::stream_close(Stream *st) {
     if (!st) return;
     streams_.erase(std::remove(streams_.begin(), streams_.end(), st), streams_.end());
     if (stream_) hipStreamSynchronize(stream_);   // a push in flight on the decoder's stream reads the state
-    for (float *p : {st->kc, st->vc, st->rope, st->rvq_tail, st->halo_rows})
+    for (float *p : {st->kc, st->vc, st->rope, st->rvq_tail, st->halo_rows, st->out_hist})
         if (p) hipFree(p);
     delete st;
 }
@@ -831,12 +833,18 @@ bool Vocoder::stream_reset(Stream *st) {
     // pushes synchronise before they return, so nothing in flight reads the counters
     st->frames = 0;
     st->samples = 0;
+    // the output stage keeps its spec and starts over: zero history, no samples, open for pushes again
+    if (st->has_out) Q3T_HIP(hipMemsetAsync(st->out_hist, 0, kPcmMaxHist * sizeof(float), stream_));
+    st->out_samples = 0;
+    st->out_final = false;
+    st->out_stale = false;
     return true;
 }
 
 bool Vocoder::stream_push(Stream *st, const int32_t *codes, int n, float *pcm, int64_t pcm_cap, int64_t *n_out) {
     if (n_out) *n_out = 0;
     if (!st || std::find(streams_.begin(), streams_.end(), st) == streams_.end()) { set_error("vocoder stream: not an open stream"); return false; }
+    if (st->has_out) { set_error("vocoder stream: the stream has an output spec (use q3t_vocoder_stream_push_out)"); return false; }
     if (n <= 0) { set_error("vocoder stream: n_frames must be > 0"); return false; }
     if (!codes || !pcm) { set_error("null argument"); return false; }
     const int P = st->frames;
@@ -873,10 +881,24 @@ bool Vocoder::stream_push(Stream *st, const int32_t *codes, int n, float *pcm, i
 
 bool Vocoder::stream_push_batch(int S, Stream *const *sts, const int32_t *const *codes, const int32_t *n_frames,
                                 float *const *pcm, const int64_t *pcm_cap, int64_t *n_out) {
+    return push_batch(S, sts, codes, n_frames, pcm, pcm_cap, n_out, nullptr);
+}
+
+bool Vocoder::stream_push_batch_out(int S, Stream *const *sts, const int32_t *const *codes, const int32_t *n_frames,
+                                    const int32_t *final, void *const *out, const int64_t *out_cap_bytes, int64_t *n_out) {
+    const OutReq req{final, out, out_cap_bytes};
+    return push_batch(S, sts, codes, n_frames, nullptr, nullptr, n_out, &req);
+}
+
+// oreq == nullptr: the plain batched push (f32 at the native rate into pcm).  oreq: the same launches with the
+// convolution stack's samples kept on the device, then the output stage over all streams
+bool Vocoder::push_batch(int S, Stream *const *sts, const int32_t *const *codes, const int32_t *n_frames,
+                         float *const *pcm, const int64_t *pcm_cap, int64_t *n_out, const OutReq *oreq) {
     last_groups_ = 0;
     if (n_out) for (int j = 0; j < S; ++j) n_out[j] = 0;
     if (S <= 0) { set_error("vocoder stream batch: n_streams must be > 0"); return false; }
-    if (!sts || !codes || !n_frames || !pcm || !pcm_cap || !n_out) { set_error("null argument"); return false; }
+    if (!sts || !codes || !n_frames || !n_out) { set_error("null argument"); return false; }
+    if (oreq ? (!oreq->final || !oreq->out || !oreq->cap) : (!pcm || !pcm_cap)) { set_error("null argument"); return false; }
     // ---- validation: nothing below this block fails on an argument
     struct Item {
         Stream *st;
@@ -884,6 +906,10 @@ bool Vocoder::stream_push_batch(int S, Stream *const *sts, const int32_t *const 
         int row0;                // first of its rows in the packed row-wise buffers
         size_t wa, wh;           // first row of its pre_conv window / convolution-stack window among all windows
         int64_t total, count;    // samples after the push, samples of the push
+        // output stage: its tap table, outputs of the push, first byte in po_bytes_, first sample in po_stage_
+        const OutTaps *ot = nullptr;
+        int64_t out_n = 0;
+        size_t out_off = 0, stage_off = 0;
     };
     std::vector<Item> it((size_t)S);
     {
@@ -897,8 +923,15 @@ bool Vocoder::stream_push_batch(int S, Stream *const *sts, const int32_t *const 
             }
             seen.push_back(st);
             const int n = n_frames[j], P = st->frames;
-            if (n <= 0) { set_error(who + ": n_frames must be > 0"); return false; }
-            if (!codes[j] || !pcm[j]) { set_error(who + ": null argument"); return false; }
+            // an output push of no frames that is final only flushes the filter's tail (an utterance's last queue
+            // delivery may carry no frame): it takes no part in the vocoder's launches, only in the output stage's
+            const bool flush = oreq && n == 0 && oreq->final[j] != 0;
+            if (n <= 0 && !flush) { set_error(who + ": n_frames must be > 0"); return false; }
+            if ((!codes[j] && !flush) || !(oreq ? oreq->out[j] != nullptr : pcm[j] != nullptr)) { set_error(who + ": null argument"); return false; }
+            if (!oreq && st->has_out) { set_error(who + " has an output spec (use q3t_vocoder_stream_push_batch_out)"); return false; }
+            if (oreq && !st->has_out) { set_error(who + " has no output spec (q3t_vocoder_stream_set_output)"); return false; }
+            if (oreq && st->out_stale) { set_error(who + ": an earlier output push failed after its frames were taken (reset the stream first)"); return false; }
+            if (oreq && st->out_final) { set_error(who + ": push after a final push (reset the stream first)"); return false; }
             if ((int64_t)P + n > st->max_frames) {
                 set_error(who + ": push of " + std::to_string(n) + " frames after " + std::to_string(P) +
                           " exceeds max_frames " + std::to_string(st->max_frames));
@@ -908,7 +941,15 @@ bool Vocoder::stream_push_batch(int S, Stream *const *sts, const int32_t *const 
             q.st = st; q.P = P; q.n = n; q.tail = std::min(2, P); q.hrows = std::min(st->halo, P);
             q.total = full_len(P + n);
             q.count = std::max<int64_t>(q.total - st->samples, 0);
-            if (pcm_cap[j] < q.count) {
+            if (oreq) {
+                q.out_n = pcm_num_samples(q.total, st->out_rate, oreq->final[j] != 0) - st->out_samples;
+                const int64_t bytes = q.out_n * pcm_bytes_per_sample(st->out_format);
+                if (oreq->cap[j] < bytes) {
+                    set_error(who + ": out_cap_bytes " + std::to_string(oreq->cap[j]) + " < " + std::to_string(bytes) +
+                              " bytes of this push");
+                    return false;
+                }
+            } else if (pcm_cap[j] < q.count) {
                 set_error(who + ": pcm_cap " + std::to_string(pcm_cap[j]) + " < " + std::to_string(q.count) +
                           " samples of this push");
                 return false;
@@ -923,8 +964,10 @@ bool Vocoder::stream_push_batch(int S, Stream *const *sts, const int32_t *const 
     // ---- groups: streams whose pre_conv window (tail + n rows) and convolution-stack window (hrows + n rows) have the
     // same lengths share those launch sequences, one sequence per grid z.  A window is never padded on the left: the
     // biases make zero rows differ from the true left edge.  A group is split only at batch_frames() window rows.
-    std::vector<int> ord((size_t)S);
-    for (int j = 0; j < S; ++j) ord[j] = j;
+    std::vector<int> act;   // the streams that push frames (all of them, but for flush-only output pushes)
+    for (int j = 0; j < S; ++j) if (it[j].n > 0) act.push_back(j);
+    const int SA = (int)act.size();
+    std::vector<int> ord = act;
     auto key_less = [&](int a, int b) {
         const Item &x = it[a], &y = it[b];
         if (x.n != y.n) return x.n < y.n;
@@ -934,23 +977,23 @@ bool Vocoder::stream_push_batch(int S, Stream *const *sts, const int32_t *const 
     std::stable_sort(ord.begin(), ord.end(), key_less);
     struct Group { int first, nb; };   // ord[first .. first+nb-1]
     std::vector<Group> groups;
-    for (int i = 0; i < S;) {
+    for (int i = 0; i < SA;) {
         const Item &q = it[ord[i]];
         const int cap = std::max(1, batch_frames_ / (q.hrows + q.n));
         int nb = 1;
-        while (i + nb < S && nb < cap && !key_less(ord[i], ord[i + nb])) ++nb;
+        while (i + nb < SA && nb < cap && !key_less(ord[i], ord[i + nb])) ++nb;
         groups.push_back({i, nb});
         i += nb;
     }
     size_t R = 0, WA = 0, WH = 0;   // packed rows, pre_conv window rows, convolution-stack window rows
     int max_n = 0, max_tiles = 0;
-    for (int j = 0; j < S; ++j) {
+    for (int j : act) {
         it[j].row0 = (int)R;
         R += (size_t)it[j].n;
         max_n = std::max(max_n, it[j].n);
         max_tiles = std::max(max_tiles, (it[j].P + it[j].n + 31) / 32 - it[j].P / 32);
     }
-    for (int i = 0; i < S; ++i) {
+    for (int i = 0; i < SA; ++i) {
         Item &q = it[ord[i]];
         q.wa = WA; q.wh = WH;
         WA += (size_t)(q.tail + q.n);
@@ -961,6 +1004,21 @@ bool Vocoder::stream_push_batch(int S, Stream *const *sts, const int32_t *const 
     for (const Group &g : groups) {
         const Item &q = it[ord[g.first]];
         if (!ensure(std::max(q.hrows + q.n, q.n + 2), g.nb, WA)) return false;
+    }
+    if (oreq) {   // the stage's tables and scratch: sized from the windows, every growth before the first launch
+        size_t stage = 0, bytes = 0;
+        for (const Group &g : groups) {
+            const Item &q0 = it[ord[g.first]];
+            const size_t nwin = (size_t)full_len(q0.hrows + q0.n);
+            for (int k = 0; k < g.nb; ++k) it[ord[g.first + k]].stage_off = stage + (size_t)k * nwin;
+            stage += (size_t)g.nb * nwin;
+        }
+        for (Item &q : it) {
+            if (!(q.ot = out_taps(q.st->out_rate))) return false;
+            q.out_off = bytes;
+            bytes += ((size_t)q.out_n * pcm_bytes_per_sample(q.st->out_format) + 15) / 16 * 16;
+        }
+        if (!out_scratch(stage, bytes, (size_t)S)) return false;
     }
     const int VH = hidden_, LAT = latent_;
     const size_t n_copy = 7 * (size_t)S;
@@ -991,33 +1049,33 @@ bool Vocoder::stream_push_batch(int S, Stream *const *sts, const int32_t *const 
         ++spn.count;
         spn.max_n = std::max<int64_t>(spn.max_n, (int64_t)nfl);
     };
-    for (int j = 0; j < S; ++j) {
-        const Item &q = it[j];
+    for (int a = 0; a < SA; ++a) {
+        const Item &q = it[act[a]];
         Stream *st = q.st;
-        sd[j].kc = st->kc; sd[j].vc = st->vc; sd[j].rope = st->rope;
-        sd[j].layer_stride = (int64_t)st->max_frames * LAT;
-        sd[j].P = q.P; sd[j].n = q.n; sd[j].row0 = q.row0;
+        sd[a].kc = st->kc; sd[a].vc = st->vc; sd[a].rope = st->rope;
+        sd[a].layer_stride = (int64_t)st->max_frames * LAT;
+        sd[a].P = q.P; sd[a].n = q.n; sd[a].row0 = q.row0;
     }
-    for (int j = 0; j < S; ++j) {   // 0: [tail | new RVQ rows] windows in A, from the state and the packed rows in C
+    for (int j : act) {   // 0: [tail | new RVQ rows] windows in A, from the state and the packed rows in C
         const Item &q = it[j];
         add(sp[0], q.st->rvq_tail, A + q.wa * VH, (size_t)q.tail * VH);
         add(sp[0], C + (size_t)q.row0 * VH, A + (q.wa + q.tail) * VH, (size_t)q.n * VH);
     }
-    for (int j = 0; j < S; ++j) {   // 1: the next push's tail, the last rows of the window
+    for (int j : act) {   // 1: the next push's tail, the last rows of the window
         const Item &q = it[j];
         const int keep = std::min(2, q.P + q.n);
         add(sp[1], A + (q.wa + q.tail + q.n - keep) * VH, q.st->rvq_tail, (size_t)keep * VH);
     }
-    for (int j = 0; j < S; ++j) {   // 2: pre_conv's rows of the new frames (windows in B), packed into C
+    for (int j : act) {   // 2: pre_conv's rows of the new frames (windows in B), packed into C
         const Item &q = it[j];
         add(sp[2], B + (q.wa + q.tail) * LAT, C + (size_t)q.row0 * LAT, (size_t)q.n * LAT);
     }
-    for (int j = 0; j < S; ++j) {   // 3: [halo rows | new output_proj rows] windows, from the state and the packed rows in C
+    for (int j : act) {   // 3: [halo rows | new output_proj rows] windows, from the state and the packed rows in C
         const Item &q = it[j];
         add(sp[3], q.st->halo_rows, WIN + q.wh * LAT, (size_t)q.hrows * LAT);
         add(sp[3], C + (size_t)q.row0 * LAT, WIN + (q.wh + q.hrows) * LAT, (size_t)q.n * LAT);
     }
-    for (int j = 0; j < S; ++j) {   // 4: the next push's halo, the last rows of the window
+    for (int j : act) {   // 4: the next push's halo, the last rows of the window
         const Item &q = it[j];
         const int keep = std::min(q.st->halo, q.P + q.n);
         add(sp[4], WIN + (q.wh + q.hrows + q.n - keep) * LAT, q.st->halo_rows, (size_t)keep * LAT);
@@ -1032,29 +1090,32 @@ bool Vocoder::stream_push_batch(int S, Stream *const *sts, const int32_t *const 
     hipStream_t s = stream_;
     auto copies = [&](const Span &spn) { return voc_copy_batch(dcd + spn.first, spn.count, spn.max_n, vec4, s); };
     std::vector<int32_t> hc(R * 16);
-    for (int j = 0; j < S; ++j) std::memcpy(hc.data() + (size_t)it[j].row0 * 16, codes[j], (size_t)it[j].n * 16 * 4);
-    Q3T_HIP(hipMemcpyAsync(codes_, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, s));
-    Q3T_HIP(hipMemcpyAsync(sb_desc_, hd.data(), desc_bytes, hipMemcpyHostToDevice, s));
-    // ---- frame-rate half: frame_rows' stages, the row-wise ones over all R rows at once
-    nb_ = 1;
-    if (!rvq_rows(codes_, (int)R, C, s) || !copies(sp[0]) || !copies(sp[1])) return false;
-    for (const Group &g : groups) {
-        const Item &q = it[ord[g.first]];
-        nb_ = g.nb;
-        const bool ok = run_conv(pre_conv_, A + q.wa * VH, q.tail + q.n, 2, 1, nullptr, B + q.wa * LAT, nullptr, 0, s);
+    for (int j : act) std::memcpy(hc.data() + (size_t)it[j].row0 * 16, codes[j], (size_t)it[j].n * 16 * 4);
+    if (SA > 0) {
+        Q3T_HIP(hipMemcpyAsync(codes_, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, s));
+        Q3T_HIP(hipMemcpyAsync(sb_desc_, hd.data(), desc_bytes, hipMemcpyHostToDevice, s));
+        // ---- frame-rate half: frame_rows' stages, the row-wise ones over all R rows at once
         nb_ = 1;
-        if (!ok) return false;
+        if (!rvq_rows(codes_, (int)R, C, s) || !copies(sp[0]) || !copies(sp[1])) return false;
+        for (const Group &g : groups) {
+            const Item &q = it[ord[g.first]];
+            nb_ = g.nb;
+            const bool ok = run_conv(pre_conv_, A + q.wa * VH, q.tail + q.n, 2, 1, nullptr, B + q.wa * LAT, nullptr, 0, s);
+            nb_ = 1;
+            if (!ok) return false;
+        }
+        if (!copies(sp[2])) return false;
+        auto attn = [&](int layer, float *qkv, uint16_t *att) {
+            return voc_kv_append_batch(qkv, dsd, SA, max_n, layer, n_heads_, head_dim_, s) &&
+                   voc_attn_cached_batch(qkv, att, dsd, SA, max_tiles, layer, n_heads_, head_dim_, s);
+        };
+        if (!layer_rows(C, (int)R, C, s, attn) || !copies(sp[3]) || !copies(sp[4])) return false;
     }
-    if (!copies(sp[2])) return false;
-    auto attn = [&](int layer, float *qkv, uint16_t *att) {
-        return voc_kv_append_batch(qkv, dsd, S, max_n, layer, n_heads_, head_dim_, s) &&
-               voc_attn_cached_batch(qkv, att, dsd, S, max_tiles, layer, n_heads_, head_dim_, s);
-    };
-    if (!layer_rows(C, (int)R, C, s, attn) || !copies(sp[3]) || !copies(sp[4])) return false;
     // from here on every stream's state is that of P + n frames
     for (Item &q : it) {
         q.st->frames = q.P + q.n;
         q.st->samples = q.total;
+        if (oreq) q.st->out_stale = true;   // until the stage has run: a failure below leaves the stream in need of a reset
     }
     // ---- convolution half: one launch sequence per group, its windows copied to where conv_stack reads them
     const int64_t rate = full_len(2) - full_len(1);
@@ -1064,22 +1125,180 @@ bool Vocoder::stream_push_batch(int S, Stream *const *sts, const int32_t *const 
         Q3T_HIP(hipMemcpyAsync(B, WIN + q0.wh * LAT, (size_t)g.nb * W * LAT * 4, hipMemcpyDeviceToDevice, s));
         int64_t nwin = 0;
         nb_ = g.nb;
-        const bool ok = conv_stack(W, pcm_, &nwin, s);
+        // with an output stage the group's samples stay on the device, each group in its own part of po_stage_
+        const bool ok = conv_stack(W, oreq ? po_stage_ + q0.stage_off : pcm_, &nwin, s);
         nb_ = 1;
         if (!ok) return false;
         ++last_groups_;
         for (int k = 0; k < g.nb; ++k) {
             const int j = ord[g.first + k];
-            const Item &q = it[j];
+            Item &q = it[j];
             // as in stream_push: the window's decode is the full decode shifted by (P - hrows) * rate samples
             const int64_t off = (q.total - q.count) - (int64_t)(q.P - q.hrows) * rate;
-            if (off < 0 || off + q.count != nwin) { set_error("vocoder stream: window bookkeeping"); return false; }
-            if (q.count)
+            if (off < 0 || off + q.count != nwin || (oreq && nwin != full_len(W))) { set_error("vocoder stream: window bookkeeping"); return false; }
+            if (oreq) q.stage_off += (size_t)off;   // the push's first new sample
+            else if (q.count)
                 Q3T_HIP(hipMemcpyAsync(pcm[j], pcm_ + (size_t)k * nwin + off, (size_t)q.count * 4, hipMemcpyDeviceToHost, s));
         }
     }
+    if (oreq) {
+        // ---- output stage: one launch over every stream's new samples, the history update, the bytes back
+        std::vector<PcmOutDesc> od((size_t)S);
+        int64_t max_out = 0;
+        for (int j = 0; j < S; ++j) {
+            const Item &q = it[j];
+            const Stream *st = q.st;
+            PcmOutDesc &d = od[j];
+            d.x = po_stage_ + q.stage_off; d.hist = st->out_hist; d.taps = q.ot->taps;
+            d.out = po_bytes_ + q.out_off;
+            d.s0 = q.total - q.count; d.n0 = st->out_samples;
+            d.n_in = (int32_t)q.count; d.n_out = (int32_t)q.out_n;
+            d.n_zero = oreq->final[j] ? q.ot->geo.D : 0;
+            d.L = q.ot->geo.L; d.M = q.ot->geo.M; d.K = q.ot->geo.K; d.format = st->out_format;
+            max_out = std::max(max_out, q.out_n);
+        }
+        Q3T_HIP(hipMemcpyAsync(po_desc_, od.data(), od.size() * sizeof(PcmOutDesc), hipMemcpyHostToDevice, s));
+        if (!pcm_out(po_desc_, S, max_out, s) || !pcm_out_hist(po_desc_, S, s)) return false;
+        for (int j = 0; j < S; ++j) {
+            Item &q = it[j];
+            const size_t bytes = (size_t)q.out_n * pcm_bytes_per_sample(q.st->out_format);
+            if (bytes) Q3T_HIP(hipMemcpyAsync(oreq->out[j], po_bytes_ + q.out_off, bytes, hipMemcpyDeviceToHost, s));
+            q.st->out_samples += q.out_n;
+            q.st->out_final = oreq->final[j] != 0;
+        }
+    }
     Q3T_HIP(hipStreamSynchronize(s));
-    for (int j = 0; j < S; ++j) n_out[j] = it[j].count;
+    if (oreq) for (Item &q : it) q.st->out_stale = false;
+    for (int j = 0; j < S; ++j) n_out[j] = oreq ? it[j].out_n : it[j].count;
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------------- output stage
+bool Vocoder::check_spec(const OutSpec &spec) {
+    PcmRate g;
+    if (!pcm_rate(spec.rate, &g)) {
+        set_error("output sample rate " + std::to_string(spec.rate) + " is not supported (supported: " + pcm_rates_text() + ")");
+        return false;
+    }
+    if (!pcm_bytes_per_sample(spec.format)) {
+        set_error("output format " + std::to_string(spec.format) + " is not supported (0 = f32, 1 = s16, 2 = mu-law)");
+        return false;
+    }
+    return true;
+}
+
+// the device tap table of a rate, built once per decoder on first use
+const Vocoder::OutTaps *Vocoder::out_taps(int rate) {
+    for (const OutTaps &t : out_taps_) if (t.rate == rate) return &t;
+    OutTaps t;
+    std::vector<float> h;
+    t.rate = rate;
+    if (!pcm_taps(rate, &t.geo, &h)) { set_error("output sample rate " + std::to_string(rate) + " is not supported"); return nullptr; }
+    if (t.geo.K - 1 > kPcmMaxHist || t.geo.M > 3 * t.geo.L) { set_error("output stage: filter geometry out of range"); return nullptr; }
+    void *p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(h.size() * 4, 16)) != hipSuccess ||
+        (!h.empty() && hipMemcpy(p, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) {
+        (void)hipGetLastError();
+        if (p) hipFree(p);
+        set_error("output stage: tap table upload failed");
+        return nullptr;
+    }
+    t.taps = (float *)p;
+    out_taps_.reserve(8);   // one per supported rate: pointers handed out stay valid
+    out_taps_.push_back(t);
+    return &out_taps_.back();
+}
+
+bool Vocoder::out_scratch(size_t stage_floats, size_t out_bytes, size_t n_desc) {
+    auto grow = [&](void **p, size_t *cap, size_t want, size_t elem) {
+        if (want <= *cap && *p) return true;
+        if (*p) { hipStreamSynchronize(stream_); hipFree(*p); }
+        *p = nullptr; *cap = 0;
+        if (hipMalloc(p, std::max<size_t>(want * elem, 16)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; set_error("output stage: scratch alloc"); return false; }
+        *cap = want;
+        return true;
+    };
+    if (!po_hist0_) {
+        void *p = nullptr;
+        if (hipMalloc(&p, kPcmMaxHist * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); set_error("output stage: scratch alloc"); return false; }
+        po_hist0_ = (float *)p;
+    }
+    return grow((void **)&po_stage_, &po_stage_cap_, stage_floats, 4) && grow((void **)&po_bytes_, &po_bytes_cap_, out_bytes, 1) &&
+           grow((void **)&po_desc_, &po_desc_cap_, n_desc, sizeof(PcmOutDesc));
+}
+
+bool Vocoder::stream_set_output(Stream *st, const OutSpec *spec) {
+    if (!st || std::find(streams_.begin(), streams_.end(), st) == streams_.end()) { set_error("vocoder stream: not an open stream"); return false; }
+    if (st->frames != 0) {
+        set_error("vocoder stream: the output spec can be set only at zero frames (the stream has " + std::to_string(st->frames) + ")");
+        return false;
+    }
+    if (!spec) {
+        st->has_out = false;
+        st->out_samples = 0;
+        st->out_final = false;
+        st->out_stale = false;
+        return true;
+    }
+    if (!check_spec(*spec) || !out_taps(spec->rate)) return false;
+    if (!st->out_hist) {
+        void *p = nullptr;
+        if (hipMalloc(&p, kPcmMaxHist * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); set_error("vocoder stream: output history alloc"); return false; }
+        st->out_hist = (float *)p;
+    }
+    Q3T_HIP(hipMemsetAsync(st->out_hist, 0, kPcmMaxHist * sizeof(float), stream_));
+    st->has_out = true;
+    st->out_rate = spec->rate; st->out_format = spec->format;
+    st->out_samples = 0;
+    st->out_final = false;
+    st->out_stale = false;
+    return true;
+}
+
+bool Vocoder::decode_out(const int32_t *codes, int F, int mode, const OutSpec &spec, void *out, int64_t out_cap_bytes,
+                         int64_t *n_out, int chunk_frames) {
+    if (n_out) *n_out = 0;
+    if (!check_spec(spec)) return false;
+    const OutTaps *ot = out_taps(spec.rate);
+    if (!ot) return false;
+    const int64_t n_in = n_samples(F, mode), n = pcm_num_samples(n_in, spec.rate, true);
+    const size_t bytes = (size_t)n * pcm_bytes_per_sample(spec.format);
+    if (out_cap_bytes < (int64_t)bytes) {
+        set_error("vocoder: out_cap_bytes " + std::to_string(out_cap_bytes) + " < " + std::to_string(bytes) + " bytes of this decode");
+        return false;
+    }
+    if (n > 0 && !out) { set_error("null argument"); return false; }
+    if (n_in >= ((int64_t)1 << 31) - 1) { set_error("vocoder: too many samples for one output-stage launch"); return false; }
+    if (!out_scratch(mode == 0 ? 0 : (size_t)n_in, bytes, 1)) return false;
+    const float *x = nullptr;
+    if (F > 0 && mode == 0) {
+        if (!ensure(F)) return false;
+        Q3T_HIP(hipMemcpyAsync(codes_, codes, (size_t)F * 16 * 4, hipMemcpyHostToDevice, stream_));
+        int64_t got = 0;
+        if (!decode_device(codes_, F, pcm_, &got, stream_)) return false;
+        if (got != n_in) { set_error("vocoder: sample count bookkeeping"); return false; }
+        x = pcm_;
+    } else if (F > 0) {
+        // CHUNK40 assembles its chunks on the host (decode_batch); the stage then runs over the assembled signal
+        std::vector<float> tmp((size_t)n_in);
+        int64_t got = 0;
+        if (!decode(codes, F, mode, tmp.data(), &got, chunk_frames)) return false;
+        if (got != n_in) { set_error("vocoder: sample count bookkeeping"); return false; }
+        Q3T_HIP(hipMemcpyAsync(po_stage_, tmp.data(), (size_t)n_in * 4, hipMemcpyHostToDevice, stream_));
+        x = po_stage_;
+    }
+    if (n > 0) {
+        Q3T_HIP(hipMemsetAsync(po_hist0_, 0, kPcmMaxHist * sizeof(float), stream_));
+        PcmOutDesc d;
+        d.x = x; d.hist = po_hist0_; d.taps = ot->taps; d.out = po_bytes_;
+        d.n_in = (int32_t)n_in; d.n_out = (int32_t)n; d.n_zero = ot->geo.D;
+        d.L = ot->geo.L; d.M = ot->geo.M; d.K = ot->geo.K; d.format = spec.format;
+        Q3T_HIP(hipMemcpyAsync(po_desc_, &d, sizeof d, hipMemcpyHostToDevice, stream_));
+        if (!pcm_out(po_desc_, 1, n, stream_)) return false;
+        Q3T_HIP(hipMemcpyAsync(out, po_bytes_, bytes, hipMemcpyDeviceToHost, stream_));
+    }
+    Q3T_HIP(hipStreamSynchronize(stream_));
+    if (n_out) *n_out = n;
     return true;
 }
 

@@ -9,6 +9,7 @@
 #include "arena.h"
 #include "gguf.h"
 #include "kernels.h"
+#include "pcm_out.h"
 
 namespace q3t {
 
@@ -55,6 +56,14 @@ public:
         float *rope = nullptr;   // [max_frames][head_dim] cos/sin by absolute position
         float *rvq_tail = nullptr;   // [2][hidden] RVQ rows of the last min(2, frames) frames, oldest first (pre_conv k3)
         float *halo_rows = nullptr;  // [halo][latent] output_proj rows of the last min(halo, frames) frames, oldest first
+        // output stage (stream_set_output): the plain pushes refuse a stream that has one, the _out pushes need one
+        bool has_out = false, out_final = false;   // out_final: a final push was made, no output push until a reset
+        // an output push failed after the stream's frames were taken (frames / samples moved, the stage did not):
+        // the next output push would filter samples that are gone, so the stream takes none until it is reset
+        bool out_stale = false;
+        int out_rate = 0, out_format = 0;
+        int64_t out_samples = 0;     // output samples emitted so far = pcm_num_samples(samples, out_rate, out_final)
+        float *out_hist = nullptr;   // [kPcmMaxHist] the stage's carried input history (its last K - 1 samples)
     };
     // look-back of the convolution stack in frames, derived from the loaded shapes (next to full_len)
     int stream_halo() const;
@@ -80,6 +89,27 @@ public:
                            float *const *pcm_host, const int64_t *pcm_cap, int64_t *n_out);
     // convolution-stack launch sequences (groups) of the last stream_push_batch; 0 after one that failed validation
     int stream_last_groups() const { return last_groups_; }
+
+    // ---- output stage (pcm_out.h; DESIGN 2c "Output stage"): a decode's or a stream's f32 samples resampled to
+    // spec.rate and written as spec.format on the device, so that only the client's bytes are copied back.
+    struct OutSpec { int rate = 0, format = 0; };
+    // The stage assumes the decoder's samples are at kPcmNativeRate (24000): the tokenizer GGUF carries no rate, every
+    // shipped geometry runs at it, and q3t_get_config reports the same constant.
+    bool check_spec(const OutSpec &spec);   // false + error naming the rate / format and listing the supported ones
+    // one-shot decode (mode as decode()) through the stage with final = 1: *n_out samples of spec.format into out_host
+    bool decode_out(const int32_t *codes_host, int n_frames, int mode, const OutSpec &spec, void *out_host,
+                    int64_t out_cap_bytes, int64_t *n_out, int chunk_frames = 40);
+    // only at zero frames (a fresh or reset stream); spec == nullptr clears it.  stream_reset keeps the spec and
+    // rewinds the stage (history zeroed, counts 0)
+    bool stream_set_output(Stream *st, const OutSpec *spec);
+    // stream_push_batch through the stage: ONE pcm_out launch (plus the history update) after the launches of the
+    // plain batched push, and device-to-host copies of the output bytes only.  Streams may carry different specs;
+    // final[j] != 0 appends the filter's tail once and closes stream j's output until it is reset; such a push may
+    // carry no frames (n_frames[j] == 0: the tail alone, no part in the vocoder's launches).  Stream j's bytes
+    // are those of pushing it alone.  Validation and the error contract are stream_push_batch's, plus: a stream
+    // without a spec, a stream already final, out_cap_bytes[j] smaller than the push's bytes
+    bool stream_push_batch_out(int n_streams, Stream *const *sts, const int32_t *const *codes_host, const int32_t *n_frames,
+                               const int32_t *final, void *const *out_host, const int64_t *out_cap_bytes, int64_t *n_out);
 
 private:
     struct Conv { uint16_t *w = nullptr; float *b = nullptr; int k = 0, ic = 0, oc = 0; };   // w: [k][oc][ic]
@@ -152,6 +182,19 @@ private:
     void *sb_desc_ = nullptr;
     size_t sb_win_cap_ = 0, sb_desc_cap_ = 0;   // floats, bytes
     int last_groups_ = 0;
+    // output stage: one request per stream of a batched push (null for the plain push), the per-rate tap tables (built
+    // on first use), the f32 staging of a call's samples, its output bytes and its descriptors
+    struct OutReq { const int32_t *final; void *const *out; const int64_t *cap; };
+    bool push_batch(int n_streams, Stream *const *sts, const int32_t *const *codes_host, const int32_t *n_frames,
+                    float *const *pcm_host, const int64_t *pcm_cap, int64_t *n_out, const OutReq *oreq);
+    struct OutTaps { int rate = 0; PcmRate geo; float *taps = nullptr; };
+    const OutTaps *out_taps(int rate);
+    bool out_scratch(size_t stage_floats, size_t out_bytes, size_t n_desc);
+    std::vector<OutTaps> out_taps_;
+    float *po_stage_ = nullptr, *po_hist0_ = nullptr;
+    unsigned char *po_bytes_ = nullptr;
+    PcmOutDesc *po_desc_ = nullptr;
+    size_t po_stage_cap_ = 0, po_bytes_cap_ = 0, po_desc_cap_ = 0;   // floats, bytes, descriptors
 };
 
 }  // namespace q3t

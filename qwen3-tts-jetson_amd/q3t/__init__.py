@@ -134,6 +134,19 @@ _lib.q3t_vocoder_stream_frames.argtypes = [_P]
 _lib.q3t_vocoder_stream_halo.restype = C.c_int32
 _lib.q3t_vocoder_stream_halo.argtypes = [_P]
 _lib.q3t_vocoder_stream_reset.argtypes = [_P]
+_lib.q3t_pcm_bytes_per_sample.restype = C.c_int32
+_lib.q3t_pcm_bytes_per_sample.argtypes = [C.c_int32]
+_lib.q3t_pcm_num_samples.restype = C.c_int64
+_lib.q3t_pcm_num_samples.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+_lib.q3t_pcm_taps.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, C.c_int64]
+_lib.q3t_vocoder_decode_out.argtypes = [_P, _ip, C.c_int32, _I, _P, _P, C.c_int64, C.POINTER(C.c_int64)]
+_lib.q3t_vocoder_stream_set_output.argtypes = [_P, _P]
+_lib.q3t_vocoder_stream_push_out.argtypes = [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]
+_lib.q3t_vocoder_stream_push_batch_out.argtypes = [_P, C.c_int32, _P, _P, _P, _P, _P, _P]
+_lib.q3t_vocoder_stream_out_samples.restype = C.c_int64
+_lib.q3t_vocoder_stream_out_samples.argtypes = [_P]
+_lib.q3t_pcm_out_launches.restype = C.c_int64
+_lib.q3t_pcm_out_launches.argtypes = []
 _lib.q3t_vocoder_stream_close.restype = None
 _lib.q3t_vocoder_stream_close.argtypes = [_P]
 _lib.q3t_speaker_dim.argtypes = [_P]
@@ -165,6 +178,9 @@ EXPORTS = ["q3t_last_error", "q3t_default_params", "q3t_ctx_create", "q3t_ctx_de
            "q3t_tokenizer_decode", "q3t_talker_forward", "q3t_talker_prefill", "q3t_talker_prefill_ragged",
            "q3t_utt_params_from", "q3t_generate_utt", "q3t_generate_queue_utt", "q3t_generate_queue_text",
            "q3t_text_feed_stats", "q3t_generate_queue_open", "q3t_check_utt",
+           "q3t_pcm_bytes_per_sample", "q3t_pcm_num_samples", "q3t_pcm_taps", "q3t_vocoder_decode_out",
+           "q3t_vocoder_stream_set_output", "q3t_vocoder_stream_push_out", "q3t_vocoder_stream_push_batch_out",
+           "q3t_vocoder_stream_out_samples", "q3t_pcm_out_launches",
            "q3t_codepred_frame", "q3t_cb0_select", "q3t_project_text", "q3t_prefill_embd", "gpu_fp32_to_fp16",
            "gpu_argmax_f32", "gpu_embedding_lookup_by_gpu_id", "gpu_sample_topk_f32"]
 
@@ -385,26 +401,89 @@ class ArrivalQueue:
             return out, self._closed and not self._q
 
 
+PCM_F32, PCM_S16, PCM_MULAW = 0, 1, 2
+PCM_RATES = (8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000)
+_PCM_DTYPES = {PCM_F32: np.float32, PCM_S16: np.int16, PCM_MULAW: np.uint8}
+
+
+class PcmSpec(C.Structure):
+    """q3t_pcm_spec: the output stage's sample rate (one of PCM_RATES) and format (PCM_F32 / PCM_S16 / PCM_MULAW)"""
+    _fields_ = [("sample_rate", C.c_int32), ("format", C.c_int32)]
+
+    @classmethod
+    def of(cls, out):
+        """a PcmSpec, or (rate, format)"""
+        return out if isinstance(out, cls) else cls(int(out[0]), int(out[1]))
+
+    @property
+    def dtype(self):
+        return _PCM_DTYPES.get(self.format, np.uint8)
+
+
+def pcm_num_samples(n_in_total, sample_rate, final=False):
+    """output samples after n_in_total vocoder samples (final: with the filter's tail); -1 for an unsupported rate"""
+    return _lib.q3t_pcm_num_samples(int(n_in_total), int(sample_rate), 1 if final else 0)
+
+
+def pcm_taps(sample_rate):
+    """(L, M, K, taps [L][K] float32): the polyphase geometry and the exact tap table of the output stage's kernel"""
+    L, M, K = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _check(_lib.q3t_pcm_taps(int(sample_rate), C.byref(L), C.byref(M), C.byref(K), None, 0))
+    taps = np.zeros((L.value, K.value), np.float32)
+    _check(_lib.q3t_pcm_taps(int(sample_rate), C.byref(L), C.byref(M), C.byref(K), _addr(taps) if taps.size else None, taps.size))
+    return L.value, M.value, K.value, taps
+
+
 class VocoderStream:
     """A streaming FULL vocoder decode (q3t_vocoder_stream_*): push() frames in pieces of any size; the concatenated
-    PCM equals Engine.vocoder(all codes) bit for bit.  Closed with the engine at the latest."""
+    PCM equals Engine.vocoder(all codes) bit for bit.  out=(rate, format) puts the output stage behind it: push()
+    then returns float32, int16 or uint8 at that rate, and the concatenation (the last push final) equals
+    Engine.vocoder(all codes, out=...) byte for byte.  Closed with the engine at the latest."""
 
-    def __init__(self, engine, max_frames=4096):
+    def __init__(self, engine, max_frames=4096, out=None):
         self.engine = engine
+        self.out = None
         h = _P()
         _check(_lib.q3t_vocoder_stream_open(engine.h, int(max_frames), C.byref(h)))
         self.h = h
         engine._streams.add(self)
+        if out is not None:
+            try:
+                self.set_output(out)
+            except Q3TError:
+                self.close()
+                raise
+
+    def set_output(self, out):
+        """the output spec (PcmSpec, (rate, format) or None to clear it); only at zero frames"""
+        spec = None if out is None else PcmSpec.of(out)
+        _check(_lib.q3t_vocoder_stream_set_output(self._handle(), C.byref(spec) if spec is not None else None))
+        self.out = spec
+
+    def _out_cap(self, n_frames, final):
+        """(samples, bytes) of an output push of n_frames"""
+        total = self.engine.vocoder_num_samples(self.frames + n_frames, VOCODER_FULL) if n_frames > 0 else self.samples
+        n = max(pcm_num_samples(total, self.out.sample_rate, final) - self.out_samples, 0)
+        return n, n * _lib.q3t_pcm_bytes_per_sample(self.out.format)
 
     def _handle(self):
         if not getattr(self, "h", None) or not self.engine.h:
             raise Q3TError("vocoder stream is closed")
         return self.h
 
-    def push(self, codes):
-        """codes [n][16] int32 -> the next samples (float32)"""
+    def push(self, codes, final=False):
+        """codes [n][16] int32 -> the next samples: float32 at the vocoder's rate, or the stream's output spec's
+        (final: with the filter's tail; the stream then takes no push until reset())"""
         codes = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
         h, n = self._handle(), codes.shape[0]
+        if self.out is not None:
+            cnt, nbytes = self._out_cap(n, final)
+            buf = np.zeros(max(cnt, 1), self.out.dtype)
+            ns = C.c_int64(0)
+            _check(_lib.q3t_vocoder_stream_push_out(h, _addr(codes), n, 1 if final else 0, _addr(buf), nbytes, C.byref(ns)))
+            return buf[:ns.value]
+        if final:
+            raise Q3TError("final needs an output spec (the plain stream has no tail to flush)")
         cap = max(self.engine.vocoder_num_samples(self.frames + n, VOCODER_FULL) - self.samples, 0) if n > 0 else 0
         pcm = np.zeros(max(cap, 1), np.float32)
         ns = C.c_int64(0)
@@ -422,6 +501,11 @@ class VocoderStream:
     @property
     def samples(self):
         return _lib.q3t_vocoder_stream_samples(self._handle())
+
+    @property
+    def out_samples(self):
+        """output samples so far (-1 without an output spec)"""
+        return _lib.q3t_vocoder_stream_out_samples(self._handle())
 
     @property
     def halo(self):
@@ -850,11 +934,21 @@ class Engine:
         """algorithmic FLOPs of one FULL decode of n_frames"""
         return _lib.q3t_vocoder_flops(self.h, int(n_frames))
 
-    def vocoder(self, codes, mode=VOCODER_FULL):
+    def vocoder(self, codes, mode=VOCODER_FULL, out=None):
+        """PCM of codes [n][16]: float32 at the vocoder's rate, or with out=(rate, format) / a PcmSpec the output
+        stage's float32 / int16 / uint8 at that rate (q3t_vocoder_decode_out, the filter's tail included)"""
         codes = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
         n = self.vocoder_num_samples(codes.shape[0], mode)
         if n < 0:
             raise Q3TError("vocoder not loaded")
+        if out is not None:
+            spec = PcmSpec.of(out)
+            cnt = max(pcm_num_samples(n, spec.sample_rate, True), 0)
+            buf = np.zeros(max(cnt, 1), spec.dtype)
+            ns = C.c_int64(0)
+            _check(_lib.q3t_vocoder_decode_out(self.h, codes, codes.shape[0], int(mode), C.byref(spec), _addr(buf),
+                                               cnt * buf.itemsize, C.byref(ns)))
+            return buf[:ns.value]
         pcm = np.zeros(max(n, 1), np.float32)
         ns = C.c_int64(0)
         _check(_lib.q3t_vocoder_decode(self.h, codes, codes.shape[0], int(mode), pcm, C.byref(ns)))
@@ -881,20 +975,42 @@ class Engine:
         _check(_lib.q3t_vocoder_decode_batch(self.h, n, cp, nf, int(mode), int(chunk_frames), pp, ns))
         return [pcms[i][:ns[i]] for i in range(n)]
 
-    def vocoder_stream(self, max_frames=4096):
-        """a VocoderStream on this context: .push(codes) -> float32 PCM, .frames, .samples, .halo, .close()"""
-        return VocoderStream(self, max_frames)
+    def vocoder_stream(self, max_frames=4096, out=None):
+        """a VocoderStream on this context: .push(codes) -> float32 PCM, .frames, .samples, .halo, .close();
+        out=(rate, format): .push(codes, final) -> that format at that rate"""
+        return VocoderStream(self, max_frames, out)
 
-    def vocoder_stream_push_batch(self, streams, pieces):
+    def vocoder_stream_push_batch(self, streams, pieces, final=None):
         """one push on each of the VocoderStreams `streams` of this context through shared launches
         (q3t_vocoder_stream_push_batch): pieces[j] is stream j's codes [n_j][16].  Returns the list of each stream's
-        next samples (float32), bit-identical to streams[j].push(pieces[j]).  On an error no stream has moved."""
+        next samples (float32), bit-identical to streams[j].push(pieces[j]).  On an error no stream has moved.
+        Streams with an output spec (all of the call, or none) go through q3t_vocoder_stream_push_batch_out: each
+        returns its own format at its own rate, final[j] ends stream j, and one conversion launch serves them all."""
         streams, pieces = list(streams), list(pieces)
         if len(streams) != len(pieces):
             raise ValueError("one piece of codes per stream")
         k = len(streams)
         codes = [np.ascontiguousarray(p, np.int32).reshape(-1, 16) for p in pieces]
         handles = [st._handle() for st in streams]
+        if any(st.out is not None for st in streams):
+            fin = [bool(f) for f in final] if final is not None else [False] * k
+            if len(fin) != k:
+                raise ValueError("one final flag per stream")
+            # a stream without a spec among them: sized as f32, refused by the library with its message
+            caps = [st._out_cap(c.shape[0], f) if st.out is not None else (0, 0) for st, c, f in zip(streams, codes, fin)]
+            bufs = [np.zeros(max(cnt, 1), st.out.dtype if st.out is not None else np.float32)
+                    for st, (cnt, _) in zip(streams, caps)]
+            harr = (C.c_void_p * k)(*[h.value for h in handles])
+            carr = (C.c_void_p * k)(*[c.ctypes.data for c in codes])
+            barr = (C.c_void_p * k)(*[b.ctypes.data for b in bufs])
+            nf = (C.c_int32 * k)(*[c.shape[0] for c in codes])
+            farr = (C.c_int32 * k)(*[1 if f else 0 for f in fin])
+            cap = (C.c_int64 * k)(*[nb for _, nb in caps])
+            ns = (C.c_int64 * k)()
+            _check(_lib.q3t_vocoder_stream_push_batch_out(harr, k, carr, nf, farr, barr, cap, ns))
+            return [b[:ns[j]] for j, b in enumerate(bufs)]
+        if final is not None and any(final):
+            raise Q3TError("final needs an output spec (the plain stream has no tail to flush)")
         caps = [max(self.vocoder_num_samples(st.frames + c.shape[0], VOCODER_FULL) - st.samples, 0) if c.shape[0] > 0 else 0
                 for st, c in zip(streams, codes)]
         pcm = [np.zeros(max(cap, 1), np.float32) for cap in caps]

@@ -422,6 +422,24 @@ int q3t_speaker_dim(const q3t_ctx *ctx);
 /* a context holding only the speaker encoder (AudioTokenizerEncoder::load_model reads only spk_enc.* tensors) */
 int q3t_ctx_create_speaker(const char *tts_gguf, int device, q3t_ctx **out);
 int q3t_speaker_encode(q3t_ctx *ctx, const float *samples, int32_t n_samples, float *embedding);
+/* q3t_speaker_encode_batch: n_clips clips of any lengths through shared launches (one host-to-device copy and one
+ * launch train per group instead of one per clip).
+ * Contract: embeddings[c] equals, bit for bit, what q3t_speaker_encode gives for samples[c] alone -- whatever the other
+ * clips, its position in the batch or the batch size.
+ * Groups: clips are packed in order, 8 rows apart, into groups of at most Q3T_SPK_GROUP_ROWS packed rows (mel frames + 8
+ * per clip; default 4096, about 43 s of audio; the environment variable is read at each call).  The bound keeps every
+ * conv of a group on the kernel instance a clip alone gets; the call checks that on the host for every group and
+ * encodes a group clip by clip if it does not hold.  A clip longer than a group is encoded alone.
+ * Errors: a clip with fewer than 5 mel frames (or fewer than 2 samples, or a NULL pointer) gets ok[c] = 0 and a zeroed
+ * row, takes no device work and does not fail the others (ok[c] = 1).  With ok == NULL such a clip fails the whole
+ * call before any device work; q3t_last_error() names its index.  n_clips == 0 is Q3T_OK.
+ * Takes the device lock as q3t_speaker_encode does, so it may be called from a queue callback on the caller's thread,
+ * and works on a q3t_ctx_create_speaker context.
+ * q3t_speaker_launches: kernel launches of the speaker encoder so far, process-wide (a conv counts 2: its pad launch
+ * and its conv launch); for tests and tools/dev/speaker_batch_bench.py. */
+int q3t_speaker_encode_batch(q3t_ctx *ctx, const float *const *samples, const int32_t *n_samples, int32_t n_clips,
+                             float *embeddings /* [n_clips][q3t_speaker_dim] */, int32_t *ok /* [n_clips] or NULL */);
+int64_t q3t_speaker_launches(void);
 int q3t_speaker_mel(q3t_ctx *ctx, const float *samples, int32_t n_samples, float *mel, int32_t cap_frames,
                     int32_t *n_frames);
 

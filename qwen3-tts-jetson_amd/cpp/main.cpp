@@ -5,9 +5,12 @@
 //   --serve       stdin lines "text<TAB>output.wav" -> stdout "OK<TAB>duration_s<TAB>time_ms<TAB>output.wav" or
 //                 "ERR<TAB>message"; "quit" / "exit" ends (main.cpp:109-163)
 //                 MI355X extension: a third TAB field "key=value;..." gives the request values of its own (language,
-//                 temperature, top_k, repetition_penalty, max_tokens, speaker=<embedding file>; serve_request.h), so
-//                 requests that differ in them still share a --batch or a --queue; a bad field fails that request
-//                 alone with an ERR reply
+//                 temperature, top_k, repetition_penalty, max_tokens, speaker=<embedding file>, reference=<wav>;
+//                 serve_request.h), so requests that differ in them still share a --batch or a --queue; a bad field
+//                 fails that request alone with an ERR reply.  reference= names a clip of the voice: the clips of the
+//                 requests served together are encoded in one batched launch train, and the voices met are kept in a
+//                 small cache (Qwen3TTS::encode_speakers); a clip that cannot be read or is too short fails its
+//                 request alone
 //   -r without -e caches the embedding in <ref>.embd (raw float32, main.cpp:37-91, 246-255)
 // MI355X extensions (no reference counterpart):
 //   --device <n>         GPU ordinal
@@ -87,7 +90,7 @@ void print_usage(const char *program) {
     fprintf(stderr, "  %s -m ./models -e speaker.bin --serve\n", program);
     fprintf(stderr, "  Then send lines: text<TAB>output.wav[<TAB>key=value;...]\n");
     fprintf(stderr, "    per-request keys: language, temperature, top_k, repetition_penalty, max_tokens, speaker,\n");
-    fprintf(stderr, "                      sample_rate\n");
+    fprintf(stderr, "                      sample_rate, reference (a WAV clip of the voice; excludes speaker)\n");
     fprintf(stderr, "  Responds with:   OK<TAB>duration_s<TAB>time_ms<TAB>output.wav\n");
     fprintf(stderr, "  Send 'quit' to exit.\n");
 }
@@ -226,7 +229,10 @@ int run_server(qwen3_tts::Qwen3TTS &tts, const std::vector<float> &speaker_embd,
                 if (q.has_repetition_penalty) t.params.repetition_penalty = q.repetition_penalty;
                 if (q.has_max_tokens) t.params.max_audio_tokens = q.max_tokens;
                 if (q.has_sample_rate) t.params.output_sample_rate = q.sample_rate;
-                if (q.has_speaker) {
+                if (q.has_reference) {   // resolved with the set's other clips, in one batched encode
+                    t.speaker_embedding.clear();
+                    t.reference_audio = q.reference;
+                } else if (q.has_speaker) {
                     t.speaker_embedding = load_embedding(q.speaker);
                     if (t.speaker_embedding.empty()) {
                         fprintf(stdout, "ERR\tcannot read speaker embedding %s\n", q.speaker.c_str());
@@ -313,7 +319,10 @@ int run_server_open(qwen3_tts::Qwen3TTS &tts, const std::vector<float> &speaker_
             if (q.has_max_tokens) t.params.max_audio_tokens = q.max_tokens;
             if (q.has_sample_rate) t.params.output_sample_rate = q.sample_rate;
             std::string why;
-            if (q.has_speaker) {
+            if (q.has_reference) {   // encoded on the main thread, with the other clips of its arrival round
+                t.speaker_embedding.clear();
+                t.reference_audio = q.reference;
+            } else if (q.has_speaker) {
                 t.speaker_embedding = load_embedding(q.speaker);
                 if (t.speaker_embedding.empty()) why = "cannot read speaker embedding " + q.speaker;
             } else if (speaker_embd.empty() && !reference_audio.empty()) {

@@ -15,6 +15,7 @@
 
 #include "q3t_backend.h"
 #include "qwen3_tts_pipeline.h"
+#include "voice_cache.h"
 
 namespace qwen3_tts {
 
@@ -488,6 +489,8 @@ struct OpenQueueState {
     const TextTokenizer *tokenizer = nullptr;
     const std::function<bool(std::vector<tts_request> &, int32_t, bool)> *next_request = nullptr;
     const std::function<void(int32_t, const tts_result &)> *on_result = nullptr;
+    // Qwen3TTS::encode_speakers: the reference clips of one answer, in one batched encode
+    std::function<bool(const std::vector<std::string> &, std::vector<std::vector<float>> &, std::vector<std::string> &)> encode_speakers;
     struct Live {
         int32_t request = 0;              // the caller's number
         int32_t rate = 0;                 // tts_params::output_sample_rate of the request
@@ -540,10 +543,36 @@ struct OpenQueueState {
         const bool more = (*next_request)(reqs, room, idle != 0);
         toks.clear();
         spk.clear();
+        // the reference clips of the requests about to be handed out (the first `room`; the others are refused below),
+        // resolved here, between two frames, in one batched encode.  One that fails is refused: it takes no arrival id
+        // and no room
+        std::vector<std::string> ref_paths, ref_err;
+        std::vector<std::vector<float>> ref_emb;
+        std::vector<int32_t> ref_of(reqs.size(), -1);
+        for (size_t i = 0; i < reqs.size() && (int32_t)i < room; ++i)
+            if (!reqs[i].reference_audio.empty() && reqs[i].speaker_embedding.empty()) {
+                ref_of[i] = (int32_t)ref_paths.size();
+                ref_paths.push_back(reqs[i].reference_audio);
+            }
+        if (!ref_paths.empty() && !(encode_speakers && encode_speakers(ref_paths, ref_emb, ref_err))) {
+            ref_err.resize(ref_paths.size());   // nothing could run: every clip fails with the reason
+            for (std::string &e : ref_err)
+                if (e.empty()) e = "Failed to extract speaker embedding";
+        }
         int32_t m = 0;
-        for (const tts_request &r : reqs) {
+        for (size_t ri = 0; ri < reqs.size(); ++ri) {
+            tts_request &r = reqs[ri];
             const int32_t no = next_request_no++;
-            if (m >= room) { refuse(no, "more requests than the queue has room for"); continue; }
+            if (m >= room || (int32_t)ri >= room) { refuse(no, "more requests than the queue has room for"); continue; }
+            if (!r.reference_audio.empty() && !r.speaker_embedding.empty()) {
+                refuse(no, "a request gives its voice as a speaker embedding or as reference audio, not both");
+                continue;
+            }
+            if (ref_of[ri] >= 0) {
+                const std::string &why = ref_err[ref_of[ri]];
+                if (!why.empty()) { refuse(no, why); continue; }
+                r.speaker_embedding = ref_emb[ref_of[ri]];
+            }
             if (!r.speaker_embedding.empty() && (int32_t)r.speaker_embedding.size() != hidden) {
                 refuse(no, "a speaker embedding must be empty or hold one value per hidden channel");
                 continue;
@@ -823,6 +852,77 @@ bool Qwen3TTS::encode_speaker(const std::string &reference_audio, std::vector<fl
     return true;
 }
 
+bool Qwen3TTS::encode_speakers(const std::vector<std::string> &reference_audios, std::vector<std::vector<float>> &embeddings,
+                               std::vector<std::string> &errors) {
+    embeddings.assign(reference_audios.size(), {});
+    errors.assign(reference_audios.size(), "");
+    if (!models_loaded_) { error_msg_ = "Models not loaded"; errors.assign(errors.size(), error_msg_); return false; }
+    const int32_t dim = q3t_speaker_dim(ctx_);
+    if (dim <= 0) {
+        error_msg_ = "Failed to load speaker encoder: No speaker encoder tensors found in model";
+        errors.assign(errors.size(), error_msg_);
+        return false;
+    }
+    if (!voices_)   // the loader is encode_speaker's: the reference's linear resampling to 24 kHz
+        voices_.reset(new VoiceCache([](const std::string &path, std::vector<float> &samples, std::string &error) {
+            int sr = 0;
+            if (!load_audio_file(path, samples, sr)) { error = "Failed to load reference audio: " + path; return false; }
+            if (sr != kSampleRate) {
+                std::vector<float> rs;
+                resample_linear(samples.data(), (int)samples.size(), sr, rs, kSampleRate);
+                samples.swap(rs);
+            }
+            return true;
+        }));
+    bool ran = true;
+    voices_->resolve(reference_audios, [&](const std::vector<std::vector<float>> &clips, std::vector<std::vector<float>> &emb,
+                                           std::vector<std::string> &err) {
+        const int32_t n = (int32_t)clips.size();
+        std::vector<const float *> ptr(n);
+        std::vector<int32_t> len(n), ok(n, 0);
+        for (int32_t i = 0; i < n; ++i) { ptr[i] = clips[i].data(); len[i] = (int32_t)clips[i].size(); }
+        std::vector<float> flat((size_t)n * dim);
+        emb.assign(n, {});
+        err.assign(n, "");
+        if (q3t_speaker_encode_batch(ctx_, ptr.data(), len.data(), n, flat.data(), ok.data()) != Q3T_OK) {
+            ran = false;
+            error_msg_ = "Failed to extract speaker embedding: " + q3t_error();
+            err.assign(n, error_msg_);
+            return;
+        }
+        for (int32_t i = 0; i < n; ++i) {
+            if (ok[i]) emb[i].assign(flat.begin() + (size_t)i * dim, flat.begin() + (size_t)(i + 1) * dim);
+            else err[i] = "Failed to extract speaker embedding: Audio too short for the speaker encoder";
+        }
+    }, embeddings, errors);
+    return ran;
+}
+
+void Qwen3TTS::resolve_references(const std::vector<tts_request> &requests, std::vector<tts_request> &run,
+                                  std::vector<int32_t> &index, std::vector<std::string> &failed) {
+    failed.assign(requests.size(), "");
+    std::vector<std::string> paths, err;
+    std::vector<int32_t> at(requests.size(), -1);
+    for (size_t i = 0; i < requests.size(); ++i) {
+        if (requests[i].reference_audio.empty()) continue;
+        if (!requests[i].speaker_embedding.empty()) {
+            failed[i] = "a request gives its voice as a speaker embedding or as reference audio, not both";
+            continue;
+        }
+        at[i] = (int32_t)paths.size();
+        paths.push_back(requests[i].reference_audio);
+    }
+    std::vector<std::vector<float>> emb;
+    const bool ran = paths.empty() || encode_speakers(paths, emb, err);
+    for (size_t i = 0; i < requests.size(); ++i) {
+        if (at[i] >= 0) failed[i] = !ran ? error_msg_ : err[at[i]];
+        if (!failed[i].empty()) continue;
+        run.push_back(requests[i]);
+        if (at[i] >= 0) run.back().speaker_embedding = emb[at[i]];
+        index.push_back((int32_t)i);
+    }
+}
+
 tts_result Qwen3TTS::synthesize_with_embedding(const std::string &text, const std::vector<float> &speaker_embedding,
                                                const tts_params &params) {
     tts_result result;
@@ -960,6 +1060,8 @@ bool Qwen3TTS::check_request(const tts_request &r, std::string &error) const {
     else if (!(r.params.repetition_penalty > 0.0f) || !std::isfinite(r.params.repetition_penalty))
         error = "repetition_penalty must be finite and > 0";
     else if (!std::isfinite(r.params.temperature)) error = "temperature must be finite";
+    else if (!r.reference_audio.empty() && !r.speaker_embedding.empty())
+        error = "a request gives its voice as a speaker embedding or as reference audio, not both";
     else if (!r.speaker_embedding.empty() && (int32_t)r.speaker_embedding.size() != hidden_)
         error = "speaker embedding holds " + std::to_string(r.speaker_embedding.size()) + " values, the model needs " +
                 std::to_string(hidden_);
@@ -993,8 +1095,26 @@ std::vector<tts_result> Qwen3TTS::synthesize_batch(const std::vector<std::string
                           bad ? "speaker_embeddings must be empty or hold one entry per text" : "");
 }
 
+static bool any_reference(const std::vector<tts_request> &requests) {
+    for (const tts_request &r : requests)
+        if (!r.reference_audio.empty()) return true;
+    return false;
+}
+
 std::vector<tts_result> Qwen3TTS::synthesize_batch(const std::vector<tts_request> &requests) {
-    return batch_requests(requests, "");
+    if (!models_loaded_ || !any_reference(requests)) return batch_requests(requests, "");
+    // the reference clips of the call in one batched encode; a request whose clip fails ends here, the rest run
+    std::vector<tts_request> run;
+    std::vector<int32_t> index;
+    std::vector<std::string> failed;
+    const int64_t t0 = now_ms();
+    resolve_references(requests, run, index, failed);
+    const int64_t t_enc = now_ms() - t0;
+    std::vector<tts_result> out(requests.size());
+    for (size_t i = 0; i < requests.size(); ++i) out[i].error_msg = failed[i];
+    const std::vector<tts_result> res = batch_requests(run, "");
+    for (size_t j = 0; j < res.size(); ++j) { out[index[j]] = res[j]; out[index[j]].t_encode_ms = t_enc; }
+    return out;
 }
 
 // arg_error: what the caller found wrong with its arguments (reported after the "Models not loaded" check, as before)
@@ -1102,7 +1222,22 @@ std::vector<tts_result> Qwen3TTS::synthesize_queue(const std::vector<std::string
 
 std::vector<tts_result> Qwen3TTS::synthesize_queue(const std::vector<tts_request> &requests,
                                                    const std::function<void(int32_t, const tts_result &)> &on_result) {
-    return queue_requests(requests, on_result, "");
+    if (!models_loaded_ || !any_reference(requests)) return queue_requests(requests, on_result, "");
+    // as synthesize_batch: one batched encode before the queue starts; a failed clip's request is reported at once
+    std::vector<tts_request> run;
+    std::vector<int32_t> index;
+    std::vector<std::string> failed;
+    resolve_references(requests, run, index, failed);
+    std::vector<tts_result> out(requests.size());
+    for (size_t i = 0; i < requests.size(); ++i) {
+        if (failed[i].empty()) continue;
+        out[i].error_msg = failed[i];
+        if (on_result) on_result((int32_t)i, out[i]);
+    }
+    const std::vector<tts_result> res = queue_requests(
+        run, [&](int32_t j, const tts_result &r) { if (on_result) on_result(index[j], r); }, "");
+    for (size_t j = 0; j < res.size(); ++j) out[index[j]] = res[j];
+    return out;
 }
 
 std::vector<tts_result> Qwen3TTS::queue_requests(const std::vector<tts_request> &requests,
@@ -1184,6 +1319,8 @@ bool Qwen3TTS::serve_queue(const std::function<bool(std::vector<tts_request> &, 
     qs.tokenizer = &tokenizer_;
     qs.next_request = &next_request;
     qs.on_result = &on_result;
+    qs.encode_speakers = [this](const std::vector<std::string> &paths, std::vector<std::vector<float>> &emb,
+                                std::vector<std::string> &err) { return encode_speakers(paths, emb, err); };
     qs.zero.assign(hidden_, 0.0f);   // no embedding: a zero speaker row, as in every call of this pipeline
     q3t_default_params(&qs.p);
     qs.p.seed = seed_;

@@ -5,6 +5,7 @@
 #define QWEN3_TTS_PIPELINE_H
 
 #include <functional>
+#include <memory>
 
 #include "qwen3_tts_hip.h"
 
@@ -55,9 +56,15 @@ struct tts_result {
 struct tts_request {
     std::string text;
     std::vector<float> speaker_embedding;
+    // the voice as a reference clip (a WAV file) instead: resampled and encoded like synthesize_with_voice's, through
+    // the voice cache, the clips of one call in one batched encode (Qwen3TTS::encode_speakers).  Empty changes
+    // nothing; giving both it and speaker_embedding is a check_request error
+    std::string reference_audio;
     tts_params params;
     int32_t language_id = 2050;   // < 0: the nothink prompt
 };
+
+class VoiceCache;
 
 class Qwen3TTS {
 public:
@@ -74,6 +81,13 @@ public:
     tts_result synthesize_with_voice(const std::string &text, const float *ref_samples, int32_t n_ref_samples,
                                      const tts_params &params = tts_params());
     bool encode_speaker(const std::string &reference_audio, std::vector<float> &embedding);
+    // MI355X extension: many reference clips at once.  embeddings[i] / errors[i] for reference_audios[i] (errors[i]
+    // empty: embeddings[i] holds the voice, bit for bit encode_speaker's).  The voices met before come from a bounded
+    // LRU cache keyed by (path, file size, modification time) (voice_cache.h, 64 entries); the others are loaded,
+    // resampled to 24 kHz as encode_speaker does, and encoded in ONE q3t_speaker_encode_batch call.  A clip that cannot
+    // be read or is too short fails alone.  False with get_error(): nothing could run (no models, no speaker encoder)
+    bool encode_speakers(const std::vector<std::string> &reference_audios, std::vector<std::vector<float>> &embeddings,
+                         std::vector<std::string> &errors);
     tts_result synthesize_with_embedding(const std::string &text, const std::vector<float> &speaker_embedding,
                                          const tts_params &params = tts_params());
     const std::string &get_error() const { return error_msg_; }
@@ -98,7 +112,9 @@ public:
                                              const std::vector<std::vector<float>> &speaker_embeddings,
                                              const tts_params &params = tts_params());
     // the same with every utterance's own voice, language, sampling values and max_audio_tokens (q3t_generate_utt);
-    // the overload above forwards here with one tts_params for all
+    // the overload above forwards here with one tts_params for all.  The reference clips of the call are resolved in
+    // one encode_speakers call before generating; a request whose clip fails gets a failed result with that message
+    // and the rest run (synthesize_queue over requests does the same)
     std::vector<tts_result> synthesize_batch(const std::vector<tts_request> &requests);
 
     // false with the reason when the engine would refuse this request's values (language id at or above the codec
@@ -137,7 +153,9 @@ public:
     // Requests are numbered from 0 in the order they are handed over; on_result(number, result) fires at a request's
     // final delivery, or at once, alone, for one that is refused (the checks of check_request and of the engine, a text
     // that does not tokenize, more max_audio_tokens than the call's).  max_audio_tokens is the cap of every request of
-    // the call: the context is sized once, before the first request.  Slots, vocoder handling and timings are
+    // the call: the context is sized once, before the first request.  Reference clips (tts_request::reference_audio)
+    // are resolved on the calling thread, between two frames, for exactly the requests about to be handed to the
+    // engine, in one encode_speakers call; a request whose clip fails is refused.  Slots, vocoder handling and timings are
     // synthesize_queue's; a request's codes are those synthesize_queue gives it at the index it has among the accepted
     // requests.  The device lock of the context is held for the whole call, also while next_request blocks.  False with
     // get_error(): an engine error ended the call (every running request got the message).
@@ -148,12 +166,17 @@ private:
     tts_result synthesize_internal(const std::string &text, const float *speaker_embedding, const tts_params &params,
                                    tts_result &result);
     bool ensure_slots(int32_t slots, int32_t max_len);
+    // the requests of a closed-set call with their references resolved (run: the ones to generate, index: their
+    // places in `requests`); failed[i] non-empty: request i's clip failed, or it gives a clip and an embedding
+    void resolve_references(const std::vector<tts_request> &requests, std::vector<tts_request> &run,
+                            std::vector<int32_t> &index, std::vector<std::string> &failed);
     std::vector<tts_result> batch_requests(const std::vector<tts_request> &requests, const std::string &arg_error);
     std::vector<tts_result> queue_requests(const std::vector<tts_request> &requests,
                                            const std::function<void(int32_t, const tts_result &)> &on_result,
                                            const std::string &arg_error);
 
     TextTokenizer tokenizer_;
+    std::unique_ptr<VoiceCache> voices_;
     q3t_ctx *ctx_ = nullptr;
     int device_ = 0;
     uint64_t seed_ = 0;

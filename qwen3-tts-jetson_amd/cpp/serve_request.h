@@ -4,7 +4,8 @@
 //   text<TAB>output.wav<TAB>key=value;...    the same with values of its own for this request
 //
 // Keys of the third field: language (a codec language id, or "nothink"), temperature, top_k, repetition_penalty,
-// max_tokens, speaker (a raw float32 embedding file, loaded like -e), sample_rate (the rate of this request's WAV: one
+// max_tokens, speaker (a raw float32 embedding file, loaded like -e), reference (a WAV clip of the voice, resampled and
+// encoded like -r; the server keeps the voices it has met in a small cache; it excludes speaker), sample_rate (the rate of this request's WAV: one
 // of 8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000; the device's output stage writes its s16).  A request takes the server's command-line values
 // for every key it does not give.  An empty third field gives none.  A bad field (unknown key, missing '=', malformed
 // or out-of-range number, a key given twice) fails that request alone with the protocol's ERR reply.
@@ -24,17 +25,18 @@ struct serve_request {
     std::string text, output;
     // the keys the line gave (has_*) and their values
     bool has_language = false, has_temperature = false, has_top_k = false, has_repetition_penalty = false,
-         has_max_tokens = false, has_speaker = false, has_sample_rate = false;
+         has_max_tokens = false, has_speaker = false, has_sample_rate = false, has_reference = false;
     int32_t language_id = 2050;   // -1: nothink
     float temperature = 0.0f;
     int32_t top_k = 0;
     float repetition_penalty = 0.0f;
     int32_t max_tokens = 0;
     std::string speaker;          // embedding file
+    std::string reference;        // reference clip (WAV)
     int32_t sample_rate = 0;      // Hz, one of the output stage's rates
     bool any() const {
         return has_language || has_temperature || has_top_k || has_repetition_penalty || has_max_tokens || has_speaker ||
-               has_sample_rate;
+               has_sample_rate || has_reference;
     }
 };
 
@@ -109,6 +111,10 @@ inline bool parse_serve_line(const std::string &line, serve_request &r, std::str
             has = &r.has_speaker;
             r.speaker = val;
             ok = !val.empty();
+        } else if (key == "reference") {
+            has = &r.has_reference;
+            ok = !val.empty();
+            if (ok && !r.has_reference) r.reference = val;
         } else if (key == "sample_rate") {
             has = &r.has_sample_rate;
             ok = serve_detail::parse_int(val, r.sample_rate) && serve_detail::known_sample_rate(r.sample_rate);
@@ -119,6 +125,7 @@ inline bool parse_serve_line(const std::string &line, serve_request &r, std::str
         if (!ok) { error = "bad value '" + val + "' for request option '" + key + "'"; return false; }
         if (*has) { error = "request option '" + key + "' given twice"; return false; }
         *has = true;
+        if (r.has_speaker && r.has_reference) { error = "request options 'speaker' and 'reference' exclude each other"; return false; }
     }
     return true;
 }

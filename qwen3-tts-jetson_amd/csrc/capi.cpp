@@ -679,6 +679,21 @@ int q3t_speaker_encode(q3t_ctx *ctx, const float *samples, int32_t n_samples, fl
     GUARD_END
 }
 
+int q3t_speaker_encode_batch(q3t_ctx *ctx, const float *const *samples, const int32_t *n_samples, int32_t n_clips,
+                             float *embeddings, int32_t *ok) {
+    GUARD_BEGIN
+    CHECK_CTX(ctx);
+    q3t::SpeakerEncoder *s = ctx->engine.speaker();
+    if (!s || !s->loaded()) { q3t::set_error("Model not loaded (no speaker encoder tensors in the TTS GGUF)"); return Q3T_ERR; }
+    if (n_clips < 0 || (n_clips > 0 && (!samples || !n_samples || !embeddings))) { q3t::set_error("null argument"); return Q3T_ERR; }
+    if (n_clips == 0) return Q3T_OK;
+    q3t::DeviceLock lk(false, ctx->engine.device());   // never beside a persistent grid (devlock.h)
+    return s->encode_batch(samples, n_samples, n_clips, embeddings, ok) ? Q3T_OK : Q3T_ERR;
+    GUARD_END
+}
+
+int64_t q3t_speaker_launches(void) { return q3t::speaker_launches(); }
+
 int q3t_speaker_mel(q3t_ctx *ctx, const float *samples, int32_t n_samples, float *mel, int32_t cap_frames,
                     int32_t *n_frames) {
     GUARD_BEGIN

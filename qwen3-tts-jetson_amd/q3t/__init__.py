@@ -152,6 +152,9 @@ _lib.q3t_vocoder_stream_close.argtypes = [_P]
 _lib.q3t_speaker_dim.argtypes = [_P]
 _lib.q3t_ctx_create_speaker.argtypes = [C.c_char_p, _I, C.POINTER(_P)]
 _lib.q3t_speaker_encode.argtypes = [_P, _fp, C.c_int32, _fp]
+_lib.q3t_speaker_encode_batch.argtypes = [_P, C.POINTER(C.POINTER(C.c_float)), _ip, C.c_int32, _fp, _P]
+_lib.q3t_speaker_launches.restype = C.c_int64
+_lib.q3t_speaker_launches.argtypes = []
 _lib.q3t_speaker_mel.argtypes = [_P, _fp, C.c_int32, _P, C.c_int32, C.POINTER(C.c_int32)]
 _lib.q3t_tokenizer_load.argtypes = [C.c_char_p, C.POINTER(_P)]
 _lib.q3t_tokenizer_free.argtypes = [_P]
@@ -174,6 +177,7 @@ EXPORTS = ["q3t_last_error", "q3t_default_params", "q3t_ctx_create", "q3t_ctx_de
            "q3t_vocoder_stream_open", "q3t_vocoder_stream_push", "q3t_vocoder_stream_push_batch",
            "q3t_vocoder_stream_last_groups", "q3t_vocoder_stream_samples",
            "q3t_vocoder_stream_frames", "q3t_vocoder_stream_halo", "q3t_vocoder_stream_close", "q3t_vocoder_stream_reset", "q3t_speaker_dim", "q3t_ctx_create_speaker", "q3t_speaker_encode", "q3t_speaker_mel",
+           "q3t_speaker_encode_batch", "q3t_speaker_launches",
            "q3t_tokenizer_load", "q3t_tokenizer_free", "q3t_tokenizer_info", "q3t_tokenizer_encode",
            "q3t_tokenizer_decode", "q3t_talker_forward", "q3t_talker_prefill", "q3t_talker_prefill_ragged",
            "q3t_utt_params_from", "q3t_generate_utt", "q3t_generate_queue_utt", "q3t_generate_queue_text",
@@ -1042,6 +1046,22 @@ class Engine:
         emb = np.zeros(max(self.speaker_dim(), 1), np.float32)
         _check(_lib.q3t_speaker_encode(self.h, x, len(x), emb))
         return emb
+
+    def encode_speakers(self, clips, strict=True):
+        """q3t_speaker_encode_batch: many 24 kHz clips of any lengths through shared launches.  Returns (emb [n][dim],
+        ok [n] bool); row c is bit for bit encode_speaker(clips[c]).  A clip too short for the encoder (< 5 mel
+        frames) gets a zeroed row and ok False; with strict it raises instead, naming the clip's index."""
+        xs = [np.ascontiguousarray(c, np.float32).ravel() for c in clips]
+        n = len(xs)
+        emb = np.zeros((n, max(self.speaker_dim(), 1)), np.float32)
+        ok = np.zeros(n, np.int32)
+        if n:
+            ptrs = (C.POINTER(C.c_float) * n)(*[x.ctypes.data_as(C.POINTER(C.c_float)) for x in xs])
+            lens = np.array([len(x) for x in xs], np.int32)
+            _check(_lib.q3t_speaker_encode_batch(self.h, ptrs, lens, n, emb, None if strict else _addr(ok)))
+            if strict:
+                ok[:] = 1
+        return emb, ok.astype(bool)
 
     def speaker_mel(self, samples):
         """the speaker encoder's log-mel front end, [n_frames][128] (time-major)"""
